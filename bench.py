@@ -7,9 +7,13 @@ nPlayers=10, Full obs, noise 0, 4096 envs per GPU (weak scaling over GPUs, env i
 all-gather of the packed obs|reward|done slab per step when N > 1).  Inputs (actions) are resident in HBM before
 the timed region; lock-step episode resets (every 600 steps) are inside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
   N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
          or plain `python bench.py --gpus N`: without WORLD_SIZE in the environment the script starts that launcher itself, as a child
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs if --dump-outputs is given and prints the
+line.  --full adds everything else after the timed region: the whole-episode roofline leg, the other configurations, the batch-size
+sweep, the configs[0] plumbing leg, the arranger leg, the CPU baselines, and (N > 1) the lock-step gather leg and the shard check.
 """
 import argparse
 import json
@@ -408,6 +412,31 @@ def arranger_leg(torch, device, E, seed, feat=128, reps=30):
                          "traffic_source": tdetail.get("traffic_source")}}
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(torch, dirname, env, env_id_offset, budget=DUMP_BUDGET_BYTES):
+    """What the last step_flat() call handed its caller - obs [E, T, A, D] float32, rewards [E, A] float64, dones [E] (uint8, written
+    as float32), and terminal_obs when that step ended the episode (auto-reset: obs is then the reset observation) - as DIR/<name>.npy,
+    plus env_ids.npy (float64), the global environment ids of the rows written.  All environments while they fit in `budget` bytes,
+    else a fixed sample (numpy default_rng(0), sorted): the files of two runs with the same arguments are comparable row for row."""
+    import numpy as np
+    outs = {"obs": env.obs, "rewards": env.rewards, "dones": env.dones}
+    if getattr(env, "last_done", False) and env.terminal_obs is not None:
+        outs["terminal_obs"] = env.terminal_obs
+    E = env.num_envs
+    per_env = 8 + sum(t[0].numel() * (8 if t.dtype == torch.float64 else 4) for t in outs.values())
+    k = min(E, (budget - 4096 * (len(outs) + 1)) // per_env)   # (4 KB per file for the .npy headers)
+    ids = np.arange(E) if k == E else np.sort(np.random.default_rng(0).choice(E, size=k, replace=False))
+    sel = torch.from_numpy(ids).to(env.obs.device)
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outs.items():
+        a = t.index_select(0, sel).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+    np.save(os.path.join(dirname, "env_ids.npy"), (ids + env_id_offset).astype(np.float64))
+    return {"dir": dirname, "files": sorted(list(outs) + ["env_ids"]), "envs_written": int(k), "envs": E}
+
+
 def launch_ranks(n):
     """Start `python -m torch.distributed.run --nnodes=1 --nproc-per-node n --master-addr 127.0.0.1 --master-port P bench.py
     <the same arguments>` as a child process; -> its return code.  stdout of the job is rank 0's one JSON line (every rank diverts
@@ -437,20 +466,26 @@ def launch_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1200)   # 2 full episodes
-    ap.add_argument("--warmup", type=int, default=600)   # 1 full episode
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 2 whole episodes of the workload)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps (default: 1 whole episode of the workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: a fixed sample of the environments where all of them would not fit)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the roofline, other-configuration, batch-size, plumbing, arranger and "
+                         "CPU-baseline legs (N > 1: the lock-step gather leg and the shard check)")
     ap.add_argument("--envs", type=int, default=4096, help="environments per GPU")
     ap.add_argument("--players", type=int, default=None)
     ap.add_argument("--workload", choices=["driving", "robocup", "driving_partial", "robocup_partial"], default="driving",
                     help="driving = BASELINE configs[1] (the headline metric); robocup = configs[2]; driving_partial = "
                          "configs[3] (Partial obs + Realistic noise magnitude 3); the latter two are reported on request")
     ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the whole-episode leg, the other BASELINE configurations and the configs[0] plumbing leg (N = 1 only)")
+                    help="with --full: skip the other BASELINE configurations, the batch-size, plumbing and arranger legs (N = 1 only)")
     ap.add_argument("--roofline-only", action="store_true",
-                    help="profiling runs (tools/profile_round.sh): skip the warm-up and the timed window and run only the whole-episode "
-                         "roofline leg, so that every launch a profiler sees belongs to it; the line says so in `mode`")
+                    help="profiling runs (tools/profile_round.sh; implies --full): skip the warm-up and the timed window and run only the "
+                         "whole-episode roofline leg, so that every launch a profiler sees belongs to it; the line says so in `mode`")
     ap.add_argument("--no-gather", action="store_true", help="skip the end-of-step all-gather (data-parallel consumer)")
     ap.add_argument("--force-gather", action="store_true",
                     help="rehearsal on a one-GPU box: run the N > 1 code path (slab, pack, all-gather, unpack) with world_size 1")
@@ -511,8 +546,10 @@ def main():
     env_type = DynEnvType.ROBO_CUP if robocup else DynEnvType.DRIVE
     E = args.envs
     A = 2 * n_players if robocup else n_players
-    if args.steps == 1200 and robocup:
-        args.steps, args.warmup = 480, 240  # 2 + 1 episodes of 240 steps
+    if args.steps is None:
+        args.steps = 2 * WORKLOADS[args.workload][3]
+    if args.warmup is None:
+        args.warmup = WORKLOADS[args.workload][3]
     slab = gather = None
     out_buffers = None
     obs_kw = {}
@@ -572,7 +609,9 @@ def main():
             gather.start(k)
 
     if args.roofline_only:
-        args.steps, args.warmup, args.no_extra_legs, args.no_cpu_baseline = 0, 0, True, True
+        args.steps, args.warmup, args.no_extra_legs, args.no_cpu_baseline, args.full = 0, 0, True, True, True
+    if args.dump_outputs and args.steps <= 0:
+        raise SystemExit("bench.py: --dump-outputs needs at least one timed step")
     env.reset_flat()
     for i in range(args.warmup):
         one_step(i)
@@ -666,6 +705,8 @@ def main():
                 gpu_ms += eb0.elapsed_time(eb1)
             timed_at.append("%d steps as %d blocks %s of one episode, barrier + synchronize around each block"
                             % (n_spread, n_blocks, [(a, a + n - 1) for a, n in zip(starts, sizes)]))
+    # the last step above was the last timed one: its buffers still hold what it returned
+    dumped = dump_outputs(torch, args.dump_outputs, env, rank * E) if args.dump_outputs and rank == 0 else None
     per_rank = None
     if dist is not None:
         # every rank's own wall clock and GPU time of the timed region: the line is self-checking (value uses the MAX)
@@ -678,7 +719,7 @@ def main():
 
     # the lock-step variant in the same line (N > 1): the global view of step k is awaited before step k + 1 is launched
     sync_leg = None
-    if gather is not None and not args.sync_gather:
+    if args.full and gather is not None and not args.sync_gather:
         n_sync = min(args.steps, 100)
         env.use_buffers(slab.obs, slab.rewards, slab.dones)
         for i in range(3):
@@ -705,10 +746,10 @@ def main():
     full = None
     ep_steps = WORKLOADS[args.workload][3]
     shard_check = None
-    if rank == 0 or dist is not None:
+    if args.full and (rank == 0 or dist is not None):
         full = episode_leg(torch, device, args.workload, E, args.seed, n_players=n_players, env_id_offset=rank * E)
         roofline = full.get("roofline")
-    if dist is not None:
+    if args.full and dist is not None:
         mine = torch.tensor([float(env.cfg.env_id_offset), full["value"], full["ms_per_step"], float(env.num_envs)], dtype=torch.float64, device=device)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
@@ -755,6 +796,8 @@ def main():
             "sync_gather": sync_leg,
             "kernel_error_flags": err,
             "roofline": roofline,
+            "full": args.full,
+            "dumped_outputs": dumped,
         }
         if full is not None:  # the same kernel over one whole episode: the mean a training run sees
             out["ms_per_step_full_episode"] = full["ms_per_step"]  # (N > 1: rank 0's kernel alone, no transport)
@@ -765,7 +808,7 @@ def main():
                 # the same episode on the plain grid: what SIMD isolation (3072 < E <= 4096 on a 256-CU device) is worth
                 noiso = episode_leg(torch, device, args.workload, E, args.seed, n_players=n_players, no_isolation=True)
                 out["value_no_isolation"], out["ms_per_step_no_isolation"] = noiso["value"], noiso["ms_per_step"]
-        if world == 1 and not args.no_extra_legs and gather is None:
+        if args.full and world == 1 and not args.no_extra_legs and gather is None:
             env.close()
             out["other_configs"] = [episode_leg(torch, device, w, E, args.seed) for w in WORKLOADS if w != args.workload]
             if not args.no_cpu_baseline:   # the CPU port beside every MI355X figure, a bounded sample each
@@ -778,7 +821,7 @@ def main():
             out["plumbing_config0"] = plumbing_leg(torch, device, args.seed)
             if args.workload == "driving":
                 out["arranger"] = arranger_leg(torch, device, E, args.seed)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(E, n_players, A, args.seed, robocup, partial=partial)
             # BASELINE.md section 3 / SURVEY 8d name threads = os.cpu_count(): the same sample with one thread per logical CPU of the box
             # (on a GPU box whose cgroup grants 16 cores of an EPYC this OVERSUBSCRIBES the share; both figures are in the line)
@@ -798,7 +841,7 @@ def main():
                     over, note="%d OpenMP threads (min of os.cpu_count() and the affinity mask) on a cgroup share of %d cores: OVERSUBSCRIBED %.0fx, run in a child "
                                "process with OMP_WAIT_POLICY=passive. Not a measurement of %d cores - read cpu_baseline (threads = the share) for the host's rate"
                                % (allc, share, allc / share, allc))
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = None
         sys.stdout.flush()
         os.dup2(real_stdout, 1)

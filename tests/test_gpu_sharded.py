@@ -306,7 +306,7 @@ def test_bench_rehearsal_with_four_ranks_on_this_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--steps", "8", "--warmup", "3", "--envs", "512", "--rehearse-one-gpu"], cwd=root, env=env,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--steps", "8", "--warmup", "3", "--envs", "512", "--rehearse-one-gpu", "--full"], cwd=root, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     err = r.stderr.decode()
     assert r.returncode == 0, err[-2000:]
@@ -332,7 +332,7 @@ def test_bench_launched_like_the_driver_with_two_ranks_on_this_gpu(how):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    tail = ["bench.py", "--gpus", "2", "--steps", "8", "--warmup", "3", "--envs", "256", "--rehearse-one-gpu"]
+    tail = ["bench.py", "--gpus", "2", "--steps", "8", "--warmup", "3", "--envs", "256", "--rehearse-one-gpu", "--full"]
     cmd = [sys.executable] + tail if how == "as_typed" else \
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", str(port)] + tail

@@ -36,12 +36,12 @@ def test_library_exports_every_declared_symbol(capi):
     assert lib.dynenv_abi_version() == capi.DYNENV_ABI_VERSION == 3
 
 
-def test_struct_sizes_match_the_header(capi):
+def test_struct_sizes_match_the_header(capi, tmp_path):
     # sizes the C compiler gives the blob structs (compiled on the fly with gcc)
     src = '#include <stdio.h>\n#include "dynenv.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(dynenv_cfg_t), ' \
           'sizeof(dynenv_layout_t), sizeof(dynenv_car_state_t), sizeof(dynenv_ped_state_t), sizeof(dynenv_driving_state_t), ' \
           'sizeof(dynenv_robocup_state_t));return 0;}'
-    exe = "/tmp/dynenv_sizes"
+    exe = str(tmp_path / "dynenv_sizes")
     subprocess.run(["gcc", "-x", "c", "-", "-I" + os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     sizes = [int(x) for x in subprocess.run([exe], capture_output=True, check=True).stdout.split()]
     assert sizes == [C.sizeof(capi.Cfg), C.sizeof(capi.Layout), C.sizeof(capi.CarState), C.sizeof(capi.PedState),

@@ -13,7 +13,7 @@ TAG=${1:-rXX}
 WORKLOADS=${2:-"driving robocup driving_partial robocup_partial hbm"}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-B="--roofline-only"
+B="--full --roofline-only"
 for W in $WORKLOADS; do
   case $W in robocup*) STEPS=240;; *) STEPS=600;; esac
   D=gpurun_out/${TAG}_prof_$W

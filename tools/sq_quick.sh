@@ -4,7 +4,7 @@ W=${1:-robocup}; T=${2:-x}
 export TMPDIR=/tmp
 D=gpurun_out/sq_quick_$T
 rm -rf $D
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_WAVES --output-format csv -d $D -- python3 bench.py --workload $W --roofline-only > /dev/null 2> $D.err || exit 1
+rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_WAVES --output-format csv -d $D -- python3 bench.py --workload $W --full --roofline-only > /dev/null 2> $D.err || exit 1
 python3 - "$D" "$T" <<'PY'
 import csv, glob, sys, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
