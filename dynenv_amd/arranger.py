@@ -107,8 +107,16 @@ class GpuInOutArranger(object):
         masks = list over time of bool [P, maxCount]) like models.py:252-274."""
         torch = self._torch
         _, max_count, _, slots, mask = countArr
+        if len(outs) != self.nObjectTypes:
+            raise ValueError("rearrange_outputs: %d outputs for %d object types" % (len(outs), self.nObjectTypes))
+        # a type without any object has out = None in the reference (:262); its counts are all zero, so it shifts nothing.
+        # None for a type WITH objects would make the reference pack the later types to the left (:259-266) where the kernels
+        # leave a gap of zeros: refused.
+        for i, o in enumerate(outs):
+            if o is None and int(slots[i].shape[0]):
+                raise ValueError("rearrange_outputs: outs[%d] is None but object type %d has %d objects"
+                                 % (i, i, int(slots[i].shape[0])))
         F = next(int(o.shape[1]) for o in outs if o is not None)
-        # a type without any object has out = None in the reference (:262); its counts are all zero, so it shifts nothing
         ok = F % 4 == 0 and all(o is None or (o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and
                                               o.shape[1] == F and o.data_ptr() % 16 == 0) for o in outs)
         n_obj = sum(int(o.shape[0]) for o in outs if o is not None)

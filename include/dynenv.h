@@ -280,6 +280,9 @@ int dynenv_checkpoint_load(dynenv_t* h, const void* buf_host, size_t nbytes);
 #define DYNENV_ARR_COUNT_CONST 0 /* every (env, time, agent) row holds `count_value` objects of the type */
 #define DYNENV_ARR_COUNT_ENV 1   /* count = count_env[env * count_stride + count_index]   (dynenv_counts() layout) */
 #define DYNENV_ARR_COUNT_ROW 2   /* count = (int) obs_row[count_index]   (Driving Partial keeps list lengths in the row tail) */
+/* In every mode the count used is clamp(count, 0, cap): a negative count is 0 objects, a count above the row capacity is
+ * `cap` objects (the rows past cap do not exist).  COUNT_ROW converts the float with a C cast, i.e. truncates toward zero
+ * (2.9 -> 2, -0.5 -> 0) before the clamp. */
 typedef struct dynenv_arr_type {
   int32_t offset, feat, cap; /* block inside an observation row: float offset, features per object, row capacity */
   int32_t count_mode, count_value, count_index, count_stride, reserved;
