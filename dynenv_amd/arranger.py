@@ -12,35 +12,15 @@ import ctypes as C
 import os
 
 from . import _capi
-from .enums import DynEnvType, ObservationType
+from .obs_layout import row_groups
 
 
 def groups_for(env):
     """The object-type groups of an environment's observation, as the reference splits them into obs[..., 0] (movable
-    objects) and obs[..., 1] (self / static rows): DrivingEnvironment.py:121-124, :977; RoboCupEnvironment.py:440-443.
+    objects) and obs[..., 1] (self / static rows); see obs_layout.row_groups.
     Returns {"movable": [ArrType...], "static": [ArrType...]}."""
-    L = env.layout
-    off, rows, feat = list(L.block_offset), list(L.block_rows), list(L.block_feat)
-    A, D = env.n_agents, env.obs_dim
-
-    def ty(offset, f, cap, mode=_capi.ARR_COUNT_CONST, value=0, index=0, stride=0):
-        return _capi.ArrType(offset, f, cap, mode, value, index, stride, 0)
-
-    if env.env_type == DynEnvType.ROBO_CUP and env.observationType == ObservationType.PARTIAL:
-        t = off[6]  # tail: list lengths of balls, robots, goals, crosses, line crosses, lines
-        mk = lambda k: ty(off[k], feat[k], rows[k], _capi.ARR_COUNT_ROW, index=t + k)
-        return {"movable": [mk(0), mk(1)], "static": [mk(2), mk(3), mk(4), mk(5)]}
-    if env.env_type == DynEnvType.ROBO_CUP:  # row = [ball 4 | self 8 | robots (A-1) x 6], see vec_env._compat_obs
-        return {"movable": [ty(0, 4, 1, value=1), ty(12, 6, A - 1, value=A - 1)], "static": [ty(4, 8, 1, value=1)]}
-    if env.observationType == ObservationType.PARTIAL:  # list lengths live in the last four floats of the row
-        return {"movable": [ty(off[1], 7, rows[1], _capi.ARR_COUNT_ROW, index=D - 4),
-                            ty(off[2], 6, rows[2], _capi.ARR_COUNT_ROW, index=D - 3),
-                            ty(off[3], 2, rows[3], _capi.ARR_COUNT_ROW, index=D - 2)],
-                "static": [ty(0, 9, 1, value=1), ty(off[4], 4, rows[4], _capi.ARR_COUNT_ROW, index=D - 1)]}
-    return {"movable": [ty(off[1], feat[1], rows[1], value=rows[1]),                       # the other A-1 cars
-                        ty(off[2], feat[2], rows[2], _capi.ARR_COUNT_ENV, index=0, stride=2),  # obstacles of the env
-                        ty(off[3], feat[3], rows[3], _capi.ARR_COUNT_ENV, index=1, stride=2)],  # pedestrians
-            "static": [ty(off[0], 9, 1, value=1), ty(off[4], feat[4], rows[4], value=rows[4])]}
+    groups = row_groups(env.layout, env.env_type, env.observationType)
+    return {name: [_capi.ArrType(*ty, 0) for ty in groups[name]] for name in ("movable", "static")}
 
 
 class GpuInOutArranger(object):

@@ -22,7 +22,9 @@ import numpy as np
 
 from . import _capi
 from . import spaces as sp
+from .compat import CompatBuilder, LazyInfo, LazyInfos, LazyObsArray
 from .enums import DynEnvType, NoiseType, ObservationType
+from .obs_layout import row_groups
 
 
 @dataclass
@@ -130,191 +132,6 @@ def _robocup_spaces(obs_type, allow_head_turn):
     return observation_space, action_space, reco
 
 
-def _to_host(t):
-    """Device tensor -> numpy through a PINNED staging tensor: torch's caching host allocator hands the block of the previous
-    step back (no 38 MB of fresh page faults per step, ~20 ms at 4096 envs) and the copy runs at PCIe speed.  The numpy array
-    keeps the tensor alive; every step gets its own block, as the reference returns fresh arrays."""
-    import torch
-    h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-    h.copy_(t)
-    return h.numpy()
-
-
-class LazyInfo(dict):
-    """The per-environment `info` dict of the reference (subproc_vec_env.py:17-23, DrivingEnvironment.py:306-316) whose two
-    expensive entries - 'Full State' and 'Recon States', lists of per-agent arrays - are built from the step's single
-    host copy of the observations only when somebody reads them.  Everything else of the dict protocol
-    behaves as if they had been there all along."""
-    LAZY = ("Full State", "Recon States")
-
-    def __init__(self, make, eager=None):
-        dict.__init__(self, eager or {})
-        self._make = make
-
-    def _materialise(self):
-        if self._make is not None:
-            full, recon = self._make()
-            self._make = None
-            dict.__setitem__(self, "Full State", full)
-            dict.__setitem__(self, "Recon States", recon)
-
-    def __missing__(self, key):
-        if key in self.LAZY and self._make is not None:
-            self._materialise()
-            return dict.__getitem__(self, key)
-        raise KeyError(key)
-
-    def get(self, key, default=None):
-        if key in self.LAZY:
-            self._materialise()
-        return dict.get(self, key, default)
-
-    def __contains__(self, key):
-        return key in self.LAZY or dict.__contains__(self, key)
-
-    def __iter__(self):
-        self._materialise()
-        return dict.__iter__(self)
-
-    def __len__(self):
-        self._materialise()
-        return dict.__len__(self)
-
-    def keys(self):
-        self._materialise()
-        return dict.keys(self)
-
-    def items(self):
-        self._materialise()
-        return dict.items(self)
-
-    def values(self):
-        self._materialise()
-        return dict.values(self)
-
-    def __repr__(self):
-        self._materialise()
-        return dict.__repr__(self)
-
-
-class LazyObsArray(object):
-    """The reference's observation `np.ndarray(dtype=object)` of shape [E, T, A, 3] (subproc_vec_env.py:201 over
-    DrivingEnvironment.py:123 / RoboCupEnvironment.py:442) without the E*T*A Python objects: it keeps the step's dense host
-    copy [E, T, A, D] and builds an element - `(movable-object arrays, static/self arrays, seen info)` - when it is indexed.
-    Indexing follows numpy's basic rules (ints, slices, Ellipsis); a sub-array is again lazy (`obs[..., :-1]`,
-    `obs[..., -1]` as models/train.py:67-68 does); `np.asarray(obs)` / `obs.materialize()` gives the reference's eager object array."""
-    dtype = np.dtype(object)
-
-    def __init__(self, owner, dense, counts, sel=None, box=None):
-        # `dense`: the step's observations [E, T, A, D] - a numpy array, or a device tensor (a snapshot the step made in HBM)
-        # that is copied to the host the first time an element is looked at; `box` shares that copy among sub-arrays
-        self._owner, self._counts = owner, counts
-        self._box = box if box is not None else [dense]
-        E, T, A, _ = dense.shape
-        self._sel = sel if sel is not None else (range(E), range(T), range(A), range(3))  # per axis: range (kept) or int (dropped)
-
-    @property
-    def _dense(self):
-        d = self._box[0]
-        if not isinstance(d, np.ndarray):
-            d = self._box[0] = _to_host(d)
-        return d
-
-    @property
-    def shape(self):
-        return tuple(len(s) for s in self._sel if not isinstance(s, int))
-
-    @property
-    def ndim(self):
-        return len(self.shape)
-
-    def __len__(self):
-        sh = self.shape
-        if not sh:
-            raise TypeError("len() of unsized object")
-        return sh[0]
-
-    def _element(self, e, t, a, k):
-        return self._owner._compat_element(self._dense, self._counts, e, t, a)[k]
-
-    def __getitem__(self, idx):
-        if not isinstance(idx, tuple):
-            idx = (idx,)
-        kept = [i for i, s in enumerate(self._sel) if not isinstance(s, int)]
-        if any(i is Ellipsis for i in idx):
-            p = [i for i, x in enumerate(idx) if x is Ellipsis][0]
-            idx = idx[:p] + (slice(None),) * (len(kept) - (len(idx) - 1)) + idx[p + 1:]
-        if len(idx) > len(kept):
-            raise IndexError("too many indices for array")
-        idx = idx + (slice(None),) * (len(kept) - len(idx))
-        sel = list(self._sel)
-        for ax, i in zip(kept, idx):
-            r = sel[ax]
-            if isinstance(i, slice):
-                sel[ax] = r[i]
-            else:
-                sel[ax] = r[int(i)]   # IndexError like numpy when out of range
-        if all(isinstance(x, int) for x in sel):
-            return self._element(*sel)
-        return LazyObsArray(self._owner, self._box[0], self._counts, tuple(sel), self._box)
-
-    def __iter__(self):
-        for i in range(len(self)):
-            yield self[i]
-
-    def materialize(self):
-        """The eager object ndarray of this (sub-)array, element for element what the reference returns."""
-        E, T, A, _ = self._dense.shape
-        if all(isinstance(x, range) and x == range(n) for x, n in zip(self._sel, (E, T, A, 3))) and hasattr(self._owner, "_compat_obs_bulk"):
-            return self._owner._compat_obs_bulk(self._dense, self._counts)  # the whole array: the bulk builder
-        axes = [([s] if isinstance(s, int) else list(s)) for s in self._sel]
-        out = np.empty(tuple(len(a) for a in axes), dtype=object)
-        for ie, e in enumerate(axes[0]):
-            for it, t in enumerate(axes[1]):
-                for ia, a in enumerate(axes[2]):
-                    el = self._owner._compat_element(self._dense, self._counts, e, t, a)
-                    for ik, k in enumerate(axes[3]):
-                        out[ie, it, ia, ik] = el[k]
-        return out.reshape(self.shape)
-
-    def __array__(self, dtype=None, copy=None):
-        return self.materialize()
-
-    def tolist(self):
-        return self.materialize().tolist()
-
-    def __repr__(self):
-        return "LazyObsArray(shape=%r, dtype=object)" % (self.shape,)
-
-
-class LazyInfos(object):
-    """The per-environment `info` dicts of one step as a read-only sequence (the reference returns a tuple of dicts,
-    subproc_vec_env.py:109-111): a dict is built when it is asked for and kept, so a consumer that never looks at
-    `info` pays nothing for 4096 of them."""
-
-    def __init__(self, n, make):
-        self._n, self._make, self._cache = n, make, {}
-
-    def __len__(self):
-        return self._n
-
-    def __getitem__(self, i):
-        if isinstance(i, slice):
-            return tuple(self[k] for k in range(*i.indices(self._n)))
-        i = int(i)
-        if i < 0:
-            i += self._n
-        if not 0 <= i < self._n:
-            raise IndexError(i)
-        d = self._cache.get(i)
-        if d is None:
-            d = self._cache[i] = self._make(i)
-        return d
-
-    def __iter__(self):
-        return (self[i] for i in range(self._n))
-
-
 class BatchedDynEnv(object):
     """All `num_envs` environments of one GPU shard behind the reference's VecEnv surface."""
 
@@ -374,6 +191,7 @@ class BatchedDynEnv(object):
             self.obs, self.rewards, self.dones = out_buffers
         self.allow_head_turn = env_type == DynEnvType.ROBO_CUP and bool(self.flags & _capi.FLAG_ALLOW_HEAD_TURN)
         self.full_obs_dim = int(self._lib.dynenv_full_obs_dim(self._h))
+        self._builder = CompatBuilder(row_groups(self.layout, env_type, observationType))
         self._counts_np = None
         self.terminal_obs = None
         self._episode_step = 0
@@ -576,168 +394,24 @@ class BatchedDynEnv(object):
         return self.obs
 
     # ------------------------------------------------------------------ reference-compatible (legacy) path
-    def _compat_obs(self, obs_t, counts):
-        """dense [E,T,A,D] -> object ndarray [E,T,A,3] of ((cars, obstacles, peds), (self, lanes), (1,1,1))"""
-        o = obs_t if isinstance(obs_t, np.ndarray) else obs_t.detach().cpu().numpy()
-        E, T, A, D = o.shape
-        L = self.layout
-        off, rows, feat = list(L.block_offset), list(L.block_rows), list(L.block_feat)
-        out = np.empty((E, T, A, 3), dtype=object)
-        if self.env_type == DynEnvType.ROBO_CUP and self.observationType == ObservationType.PARTIAL:
-            # getAgentVision: ((balls, robots), (goals, crosses, line crosses, lines), (numLandMarks, robotsSeen, ballsSeen))
-            tail = off[6]
-            for e in range(E):
-                for t in range(T):
-                    for a in range(A):
-                        r = o[e, t, a]
-                        n = [int(x) for x in r[tail:tail + 6]]
-                        lists = [r[off[k]:off[k] + n[k] * feat[k]].reshape(n[k], feat[k]) for k in range(6)]
-                        out[e, t, a, 0] = [lists[0], lists[1]]
-                        out[e, t, a, 1] = [lists[2], lists[3], lists[4], lists[5]]
-                        out[e, t, a, 2] = (int(r[tail + 6]), r[tail + 8:tail + 8 + (A - 1)].astype("uint8"), bool(r[tail + 7]))
-            return out
-        # Views into `o` (a fresh host copy per step), blocks reshaped once for the whole batch: the per-(env, time, agent)
-        # Python work is only the assembly of the reference's nested lists.
-        ones = (1, 1, 1)
-        if self.env_type == DynEnvType.ROBO_CUP:  # ((ball, robots), (self,), (1,1,1)) RoboCupEnvironment.py:440-443
-            ball = o[..., 0:4].reshape(E, T, A, 1, 4)
-            selfr = o[..., 4:12].reshape(E, T, A, 1, 8)
-            robs = o[..., 12:12 + (A - 1) * 6].reshape(E, T, A, A - 1, 6)
-            for e in range(E):
-                for t in range(T):
-                    for a in range(A):
-                        out[e, t, a, 0] = [ball[e, t, a], robs[e, t, a]]
-                        out[e, t, a, 1] = [selfr[e, t, a], ]
-                        out[e, t, a, 2] = ones
-            return out
-        if self.observationType == ObservationType.PARTIAL:  # ragged rows of getAgentVision, lengths in the last 4 floats
-            cars = o[..., off[1]:off[1] + rows[1] * 7].reshape(E, T, A, rows[1], 7)
-            obst = o[..., off[2]:off[2] + rows[2] * 6].reshape(E, T, A, rows[2], 6)
-            peds = o[..., off[3]:off[3] + rows[3] * 2].reshape(E, T, A, rows[3], 2)
-            lanes = o[..., off[4]:off[4] + rows[4] * 4].reshape(E, T, A, rows[4], 4)
-            selfr = o[..., 0:9].reshape(E, T, A, 1, 9)
-            n = o[..., D - 4:].astype(np.int64)
-            for e in range(E):
-                for t in range(T):
-                    for a in range(A):
-                        nc, no, npd, nl = n[e, t, a]
-                        out[e, t, a, 0] = [cars[e, t, a, :nc], obst[e, t, a, :no], peds[e, t, a, :npd]]
-                        out[e, t, a, 1] = [selfr[e, t, a], lanes[e, t, a, :nl]]
-                        out[e, t, a, 2] = ones
-            return out
-        selfr = o[..., off[0]:off[0] + 9].reshape(E, T, A, 1, 9)
-        cars = o[..., off[1]:off[1] + rows[1] * 7].reshape(E, T, A, rows[1], 7)
-        obst = o[..., off[2]:off[2] + rows[2] * 4].reshape(E, T, A, rows[2], 4)
-        peds = o[..., off[3]:off[3] + rows[3] * 2].reshape(E, T, A, rows[3], 2)
-        lanes = o[..., off[4]:off[4] + rows[4] * 5].reshape(E, T, A, rows[4], 5)
-        for e in range(E):
-            n_obst, n_ped = int(counts[e, 0]), int(counts[e, 1])
-            for t in range(T):
-                for a in range(A):
-                    out[e, t, a, 0] = [cars[e, t, a], obst[e, t, a, :n_obst], peds[e, t, a, :n_ped]]
-                    out[e, t, a, 1] = [selfr[e, t, a], lanes[e, t, a]]
-                    out[e, t, a, 2] = ones
-        return out
-
-    def _compat_obs_bulk(self, obs_t, counts):
-        """`_compat_obs` without a Python-level loop over (env, time, agent): the per-agent arrays of a type are made by iterating
-        the type's block once in C (`np.fromiter(iter(block), object)`: one view per row), ragged blocks grouped by their row
-        count, and the reference's nested lists by `zip`.  Element for element what `_compat_obs` builds (the test compares
-        them); ~1 us per agent instead of 2.6 (five ndarray objects and two lists per agent remain - the reference's format)."""
-        import gc
-        import itertools
-        o = obs_t if isinstance(obs_t, np.ndarray) else _to_host(obs_t.detach())
-        E, T, A, D = o.shape
-        N = E * T * A
-        gc_was_on = gc.isenabled()
-        gc.disable()  # ~8 N container objects are about to be allocated: every 700th would trigger a collection pass over them
-        try:
-            return self._compat_obs_bulk_build(o, counts, E, T, A, D, N)
-        finally:
-            if gc_was_on:
-                gc.enable()
-
-    def _compat_obs_bulk_build(self, o, counts, E, T, A, D, N):
-        import itertools
-        L = self.layout
-        off, rows, feat = list(L.block_offset), list(L.block_rows), list(L.block_feat)
-        flat = o.reshape(N, D)
-
-        def views(lo, cap, f, lens=None, dtype=None):
-            block = flat[:, lo:lo + cap * f].reshape(N, cap, f)
-            if dtype is not None:
-                block = block.astype(dtype)
-            if lens is None:
-                return np.fromiter(iter(block), dtype=object, count=N)
-            res = np.empty(N, dtype=object)
-            for n in np.unique(lens):
-                pos = np.nonzero(lens == n)[0]
-                res[pos] = np.fromiter(iter(block[pos, :int(n)]), dtype=object, count=len(pos))
-            return res
-
-        def lists(*cols):
-            return np.fromiter(map(list, zip(*cols)), dtype=object, count=N)
-        out = np.empty((N, 3), dtype=object)
-        ones = np.fromiter(itertools.repeat((1, 1, 1), N), dtype=object, count=N)
-        if self.env_type == DynEnvType.ROBO_CUP and self.observationType == ObservationType.PARTIAL:
-            tail = off[6]
-            n = flat[:, tail:tail + 6].astype(np.int64)
-            v = [views(off[k], rows[k], feat[k], n[:, k]) for k in range(6)]
-            seen = np.fromiter(iter(flat[:, tail + 8:tail + 8 + (A - 1)].astype("uint8")), dtype=object, count=N)
-            out[:, 0] = lists(v[0], v[1])
-            out[:, 1] = lists(v[2], v[3], v[4], v[5])
-            out[:, 2] = np.fromiter(zip(flat[:, tail + 6].astype(np.int64).tolist(), seen, (flat[:, tail + 7] != 0).tolist()),
-                                    dtype=object, count=N)
-        elif self.env_type == DynEnvType.ROBO_CUP:
-            out[:, 0] = lists(views(0, 1, 4), views(12, A - 1, 6))
-            out[:, 1] = lists(views(4, 1, 8))
-            out[:, 2] = ones
-        elif self.observationType == ObservationType.PARTIAL:
-            n = flat[:, D - 4:].astype(np.int64)
-            out[:, 0] = lists(views(off[1], rows[1], 7, n[:, 0]), views(off[2], rows[2], 6, n[:, 1]), views(off[3], rows[3], 2, n[:, 2]))
-            out[:, 1] = lists(views(0, 1, 9), views(off[4], rows[4], 4, n[:, 3]))
-            out[:, 2] = ones
-        else:
-            c = np.asarray(counts).astype(np.int64)
-            n_obst, n_ped = np.repeat(c[:, 0], T * A), np.repeat(c[:, 1], T * A)
-            out[:, 0] = lists(views(off[1], rows[1], 7), views(off[2], rows[2], 4, n_obst), views(off[3], rows[3], 2, n_ped))
-            out[:, 1] = lists(views(off[0], 1, 9), views(off[4], rows[4], 5))
-            out[:, 2] = ones
-        return out.reshape(E, T, A, 3)
-
-    def _compat_element(self, o, counts, e, t, a):
-        """One element [e, t, a] of the reference's observation array: [movable-object arrays, static / self arrays, seen info]
-        (the same views / values `_compat_obs` assembles for the whole batch)."""
-        L = self.layout
-        off, rows, feat = list(L.block_offset), list(L.block_rows), list(L.block_feat)
-        A, D = self.n_agents, self.obs_dim
-        r = o[e, t, a]
-        if self.env_type == DynEnvType.ROBO_CUP and self.observationType == ObservationType.PARTIAL:
-            tail = off[6]
-            n = [int(x) for x in r[tail:tail + 6]]
-            lists = [r[off[k]:off[k] + n[k] * feat[k]].reshape(n[k], feat[k]) for k in range(6)]
-            return [[lists[0], lists[1]], [lists[2], lists[3], lists[4], lists[5]],
-                    (int(r[tail + 6]), r[tail + 8:tail + 8 + (A - 1)].astype("uint8"), bool(r[tail + 7]))]
-        if self.env_type == DynEnvType.ROBO_CUP:
-            return [[r[0:4].reshape(1, 4), r[12:12 + (A - 1) * 6].reshape(A - 1, 6)], [r[4:12].reshape(1, 8), ], (1, 1, 1)]
-        if self.observationType == ObservationType.PARTIAL:
-            nc, no, npd, nl = [int(x) for x in r[D - 4:]]
-            return [[r[off[1]:off[1] + rows[1] * 7].reshape(rows[1], 7)[:nc], r[off[2]:off[2] + rows[2] * 6].reshape(rows[2], 6)[:no],
-                     r[off[3]:off[3] + rows[3] * 2].reshape(rows[3], 2)[:npd]],
-                    [r[0:9].reshape(1, 9), r[off[4]:off[4] + rows[4] * 4].reshape(rows[4], 4)[:nl]], (1, 1, 1)]
-        n_obst, n_ped = int(counts[e, 0]), int(counts[e, 1])
-        return [[r[off[1]:off[1] + rows[1] * 7].reshape(rows[1], 7), r[off[2]:off[2] + rows[2] * 4].reshape(rows[2], 4)[:n_obst],
-                 r[off[3]:off[3] + rows[3] * 2].reshape(rows[3], 2)[:n_ped]],
-                [r[off[0]:off[0] + 9].reshape(1, 9), r[off[4]:off[4] + rows[4] * 5].reshape(rows[4], 5)], (1, 1, 1)]
-
     def _host_counts(self):
         """(n_obstacles, n_pedestrians) per environment on the host: they change at a reset only, so one copy per episode."""
         if self._counts_np is None:
             self._counts_np = self.counts().cpu().numpy()
         return self._counts_np
 
-    def _wrap_obs(self, obs_np, counts):
-        return self._compat_obs_bulk(obs_np, counts) if self.eager_compat else LazyObsArray(self, obs_np, counts)
+    def _snapshot(self):
+        """self.obs as the compat containers keep it (self.obs is rewritten by the next step): a clone in HBM that is copied to the
+        host when somebody looks at an element, or - eager_compat - the host copy now."""
+        return self.obs.cpu().numpy() if self.eager_compat else self.obs.clone()
+
+    def _compat(self, dense, counts):
+        return self._builder.array(dense, counts) if self.eager_compat else LazyObsArray(self._builder, dense, counts)
+
+    def _compat_obs(self, obs_t, counts):
+        """dense [E,T,A,D] (numpy or device tensor) -> the eager object ndarray [E,T,A,3]: the name earlier callers know, kept over
+        the one builder."""
+        return self._builder.array(obs_t, counts)
 
     def _full_states(self, full_np, counts, e, glob_np=None):
         """info['Full State'] / info['Recon States'] (DrivingEnvironment.py:306-307, RoboCupEnvironment.py:511-512) of env e from
@@ -769,7 +443,7 @@ class BatchedDynEnv(object):
 
     def reset(self):
         self.reset_flat()
-        return self._wrap_obs(self.obs.clone() if not self.eager_compat else self.obs.cpu().numpy(), self._host_counts())
+        return self._compat(self._snapshot(), self._host_counts())
 
     def step_async(self, actions):
         self._pending = actions
@@ -783,13 +457,15 @@ class BatchedDynEnv(object):
         full_dev = self.full_state_obs() if self.observationType != ObservationType.FULL else None
         glob_dev = self.global_state() if self.env_type == DynEnvType.ROBO_CUP else None  # 252 B per environment, one short launch
         rewards = self.rewards.cpu().numpy().copy()
-        if self.observationType == ObservationType.PARTIAL and self.error_flags() & 8:
+        robocup, partial = self.env_type == DynEnvType.ROBO_CUP, self.observationType == ObservationType.PARTIAL
+        flags = self.error_flags() if robocup or partial else 0  # one read: each is a device synchronisation and a copy of the flags
+        if partial and flags & 8:
             # the reference's observation lists have no cap (DrivingEnvironment.py:816-890); the dense layout has, and rows beyond it were
             # dropped: not the reference's observation any more - never silently (include/dynenv.h, error bit 3)
             raise _capi.DynEnvError("Partial observation: a list had more rows than the dense layout's capacity; rows were dropped (error bit 3)")
-        if self.env_type == DynEnvType.ROBO_CUP and self.error_flags() & 32:
+        if robocup and flags & 32:
             raise _capi.DynEnvError("RoboCup: a velocity or joint impulse left the finite range (error bit 5): the state is not the reference's any more")
-        if self.env_type == DynEnvType.ROBO_CUP and self.error_flags() & 16:
+        if robocup and flags & 16:
             # two capsule cores exactly collinear / exactly touching: the sign of the contact normal is a convention there
             # (Robot.py:38-52; include/dynenv.h, error bit 4) - possibly not pymunk's trajectory from here on, never silently
             raise _capi.DynEnvError("RoboCup: the cores of two feet are exactly collinear / touching: the contact normal's sign is a convention "
@@ -799,12 +475,13 @@ class BatchedDynEnv(object):
         # The step's observations stay in HBM (a snapshot: self.obs is rewritten by the next step) until somebody looks at them:
         # ONE device->host copy then serves obs and infos alike.  (A fresh 38 MB host buffer per step costs ~20 ms of page
         # faults at 4096 envs - more than the step.)
-        lazy_obs = LazyObsArray(self, self.obs.clone() if not self.eager_compat else self.obs.cpu().numpy(), counts)
+        dense = self._snapshot()
+        step_obs = self._compat(dense, counts)
         cache = {}
 
         def full_np():
             if "full" not in cache:
-                cache["full"] = full_dev.cpu().numpy() if full_dev is not None else lazy_obs._dense[:, -1]
+                cache["full"] = full_dev.cpu().numpy() if full_dev is not None else (dense if self.eager_compat else step_obs._dense)[:, -1]
             return cache["full"]
 
         def glob_np():
@@ -816,7 +493,7 @@ class BatchedDynEnv(object):
         stats = term = None
         if done:
             stats = [x.cpu().numpy() for x in self.episode_stats()]
-            term = self._compat_obs(lazy_obs._dense, counts)
+            term = np.asarray(step_obs)  # every element: the bulk builder on the step's host copy
 
         def make_info(e):
             eager = {}
@@ -832,11 +509,8 @@ class BatchedDynEnv(object):
             infos = tuple(infos)
         if done:
             self.terminal_obs = self.obs.clone()
-            self.reset_flat()
-            obs = self._wrap_obs(self.obs.clone() if not self.eager_compat else self.obs.cpu().numpy(), self._host_counts())
-        else:
-            obs = self._compat_obs_bulk(lazy_obs._dense, counts) if self.eager_compat else lazy_obs
-        return obs, rewards, dones, infos
+            return self.reset(), rewards, dones, infos  # SubprocVecEnv worker semantics (subproc_vec_env.py:19-22)
+        return step_obs, rewards, dones, infos
 
     def step(self, actions):
         self.step_async(actions)

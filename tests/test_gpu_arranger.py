@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, ROOT)
 import arranger as oa  # noqa: E402
+from compat_ref import compat_obs_of  # noqa: E402
 from test_oracle_golden_arranger import CASES, G, ragged_from_golden  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -91,7 +92,7 @@ def test_gpu_arranger_on_real_observations(cfg):
         act = np.stack([rng.integers(0, k, (E, env.n_agents)) for k in hi], -1).astype(np.int32)
         obs, _, _ = env.step_flat(torch.tensor(act, device="cuda"), auto_reset=False)
     count_env = env.counts() if env.env_type == DynEnvType.DRIVE else None
-    compat = env._compat_obs(obs, count_env.cpu().numpy() if count_env is not None else None)
+    compat = compat_obs_of(env, obs, count_env)  # the independent loop: groups_for and the product's builders share one description
     for gi, gname in enumerate(("movable", "static")):
         types = groups_for(env)[gname]
         arr = GpuInOutArranger(types, E, env.n_agents, env.n_time_steps, env.obs_dim)

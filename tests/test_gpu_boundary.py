@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+from compat_ref import compat_obs_of
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +55,7 @@ def test_lazy_compat_equals_eager_element_for_element(gpu, kind, n, obs):
     lazy = env.reset()
     for s in range(3):
         lazy, rew, dones, infos = env.step(_acts(rng, env))
-    eager = env._compat_obs(lazy._dense, lazy._counts)      # the round-1 eager builder on the same host copy
+    eager = compat_obs_of(env, lazy._dense, lazy._counts)   # the plain triple loop (tests/compat_ref.py) on the same host copy
     assert lazy.shape == eager.shape == (E, env.n_time_steps, env.n_agents, 3) and lazy.dtype == object
     full = np.asarray(lazy)
     assert full.dtype == object and full.shape == eager.shape
@@ -73,6 +74,101 @@ def test_lazy_compat_equals_eager_element_for_element(gpu, kind, n, obs):
     assert len(infos) == E and set(infos[0]) >= {"Full State", "Recon States"}
     assert infos[E - 1] is infos[-1]
     env.close()
+
+
+def _part(obs):
+    from dynenv_amd import NoiseType, ObservationType
+    return dict(observationType=ObservationType.PARTIAL, noiseType=NoiseType.REALISTIC, noiseMagnitude=3) if obs else {}
+
+
+def _same_array(got, ref):
+    """an object array [..., 3] of the compat path against the reference loop's, element for element"""
+    assert got.shape == ref.shape and got.dtype == object
+    for idx in np.ndindex(*ref.shape):
+        _same(got[idx], ref[idx])
+
+
+@pytest.mark.parametrize("kind,n", [("DRIVE", 10), ("ROBO_CUP", 5)])
+def test_compat_step_across_an_episode_end(gpu, kind, n):
+    """SubprocVecEnv worker semantics (subproc_vec_env.py:17-23) of the compat step() at the end of a whole episode: every environment
+    is done, info carries the terminal observation and the episode's statistics, and the observation returned is the reset one.
+    A second handle with the same seed and actions, stepped with step_flat(auto_reset=False), stands where the first stood before
+    it reset."""
+    dynenv_amd, torch, _ = gpu
+    E = 4
+    env = dynenv_amd.BatchedDynEnv(getattr(dynenv_amd.DynEnvType, kind), E, n, seed=23)
+    twin = dynenv_amd.BatchedDynEnv(getattr(dynenv_amd.DynEnvType, kind), E, n, seed=23)
+    env.reset()
+    twin.reset_flat()
+    rng = np.random.default_rng(11)
+    S, T, A = env.steps_per_episode, env.n_time_steps, env.n_agents
+    assert S == (600 if kind == "DRIVE" else 240)
+    for s in range(S):
+        a = _acts(rng, env)
+        obs, rew, dones, infos = env.step(a)
+        _, rew_t, _ = twin.step_flat(a, auto_reset=False)
+        if s < S - 1:
+            assert not dones.any() and "terminal_observation" not in infos[0], "step %d" % s
+    assert dones.dtype == bool and dones.shape == (E,) and dones.all()
+    np.testing.assert_array_equal(rew, rew_t.cpu().numpy())
+    assert torch.equal(env.terminal_obs, twin.obs)
+    term = compat_obs_of(env, env.terminal_obs, twin.counts())      # the scene of the episode that ended: the twin still has it
+    stats = [x.cpu().numpy() for x in twin.episode_stats()]
+    assert len(infos) == E
+    for e in range(E):
+        info = infos[e]
+        tobs = info["terminal_observation"]
+        assert type(tobs) is list and len(tobs) == T
+        for t in range(T):
+            assert type(tobs[t]) is list and len(tobs[t]) == A
+            for ag in range(A):
+                assert len(tobs[t][ag]) == 3
+                for k in range(3):
+                    _same(tobs[t][ag][k], term[e, t, ag, k])
+        for key, ref in (("episode_r", stats[0][e]), ("episode_p_r", stats[1][e]), ("episode_o_r", stats[2][e])):
+            assert len(info[key]) == A
+            np.testing.assert_array_equal(np.asarray(info[key], np.float64), ref, err_msg=key)
+        assert info["episode_g"] == [int(stats[3][e, 0]), int(stats[3][e, 1])]
+        assert "Full State" in info and "Recon States" in info
+    assert np.abs(stats[0]).max() > 0, "an episode of random actions collects some reward"
+    # the observation returned is the one of the reset that followed
+    assert obs.shape == (E, T, A, 3)
+    _same_array(np.asarray(obs), compat_obs_of(env, env.obs, env.counts()))
+    assert torch.equal(env.obs, twin.reset_flat()) and env._episode_step == 0
+    env.close(); twin.close()
+
+
+@pytest.mark.parametrize("kind,n,obs", CONFIGS)
+def test_eager_compat_equals_lazy_and_the_reference_loop(gpu, kind, n, obs):
+    """eager_compat=True returns the reference's own containers - an object ndarray and a tuple of dicts - with the same content
+    as the lazy forms of a handle that ran the same seed and actions, and as the plain triple loop on the step's observations"""
+    dynenv_amd, torch, _ = gpu
+    E = 5
+    mk = lambda **kw: dynenv_amd.BatchedDynEnv(getattr(dynenv_amd.DynEnvType, kind), E, n, seed=31, **dict(_part(obs), **kw))
+    lazy_env, eager_env = mk(), mk(eager_compat=True)
+    lo, eo = lazy_env.reset(), eager_env.reset()
+    rng = np.random.default_rng(12)
+    for s in range(5):
+        if s:
+            a = _acts(rng, lazy_env)
+            lo, lr, ld, li = lazy_env.step(a)
+            eo, er, ed, ei = eager_env.step(a)
+            assert type(ei) is tuple and len(ei) == len(li) == E and all(isinstance(d, dict) for d in ei)
+            assert er.dtype == lr.dtype and ed.dtype == ld.dtype == bool
+            np.testing.assert_array_equal(er, lr)
+            np.testing.assert_array_equal(ed, ld)
+            for e in (0, E - 1):
+                assert set(ei[e]) == set(li[e]) >= {"Full State", "Recon States"}
+                _same(ei[e]["Full State"], li[e]["Full State"])
+                _same(ei[e]["Recon States"], li[e]["Recon States"])
+        assert type(eo) is np.ndarray and eo.dtype == object and not isinstance(lo, np.ndarray), "step %d" % s
+        assert torch.equal(lazy_env.obs, eager_env.obs)
+        ref = compat_obs_of(eager_env, eager_env.obs, eager_env.counts())
+        _same_array(eo, ref)
+        _same_array(np.asarray(lo), ref)
+        for idx in ((0, 0, 0, 0), (E - 1, -1, -1, 1), (2, 0, 1, 2)):
+            _same(lo[idx], eo[idx])
+    lazy_env.close(); eager_env.close()
 
 
 @pytest.mark.parametrize("kind,n", [("DRIVE", 10), ("DRIVE", 4), ("ROBO_CUP", 5), ("ROBO_CUP", 2)])

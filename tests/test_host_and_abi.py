@@ -163,17 +163,23 @@ def test_lazy_obs_array_indexes_like_the_object_ndarray():
     """LazyObsArray (the compat observation of step() / reset()) follows numpy's basic indexing on [E, T, A, 3]"""
     from dynenv_amd.vec_env import LazyInfos, LazyObsArray
 
-    class Owner(object):
-        def _compat_element(self, dense, counts, e, t, a):
+    class Builder(object):  # the interface LazyObsArray builds through (compat.CompatBuilder): one element; the whole array
+        def element(self, dense, counts, e, t, a):
             return [("mov", e, t, a), ("stat", e, t, a), (1, 1, 1)]
+
+        def array(self, dense, counts):
+            out = np.empty(dense.shape[:3] + (3,), dtype=object)
+            for e, t, a in np.ndindex(*dense.shape[:3]):
+                out[e, t, a] = self.element(dense, counts, e, t, a)
+            return out
     E, T, A = 4, 2, 3
     dense = np.zeros((E, T, A, 7), np.float32)
-    lazy = LazyObsArray(Owner(), dense, None)
+    lazy = LazyObsArray(Builder(), dense, None)
     ref = np.empty((E, T, A, 3), dtype=object)
     for e in range(E):
         for t in range(T):
             for a in range(A):
-                for k, v in enumerate(Owner()._compat_element(dense, None, e, t, a)):
+                for k, v in enumerate(Builder().element(dense, None, e, t, a)):
                     ref[e, t, a, k] = v
     assert lazy.shape == ref.shape and lazy.ndim == 4 and lazy.dtype == object and len(lazy) == E
     full = np.asarray(lazy)
@@ -257,14 +263,17 @@ def _deep_same(a, b):
         assert type(a) is type(b) and a == b, (a, b)
 
 
-@pytest.mark.parametrize("env_type,n,partial", [(1, 10, False), (1, 4, True), (0, 5, False), (0, 3, True)])
+@pytest.mark.parametrize("env_type,n,partial", [(1, 10, False), (1, 4, True), (0, 5, False), (0, 3, True),
+                                                (1, 1, False), (1, 1, True), (0, 1, False), (0, 1, True)])  # 1: "other cars / robots" has capacity 0
 def test_bulk_compat_builder_equals_the_loop_builder(oracle_built, env_type, n, partial):
-    """the reference's ragged object array [E, T, A, 3] built without a Python loop over agents (vec_env._compat_obs_bulk) is
-    element for element - container types, dtypes, shapes, values - what the plain triple loop (_compat_obs) builds, on real
+    """the reference's ragged object array [E, T, A, 3] built without a Python loop over agents (compat.CompatBuilder.array) is
+    element for element - container types, dtypes, shapes, values - what the plain triple loop (tests/compat_ref.py) builds, on real
     observations of all four layouts (the oracle's: same dense layout as the library's)"""
     import oracle_lib as ol
+    from compat_ref import compat_obs
+    from dynenv_amd.compat import CompatBuilder
     from dynenv_amd.enums import DynEnvType, ObservationType
-    from dynenv_amd.vec_env import BatchedDynEnv
+    from dynenv_amd.obs_layout import row_groups
     E = 9
     kw = dict(obs_type=1, noise_type=1, noise_magnitude=3.0) if partial else {}
     ora = ol.OracleEnv(env_type=env_type, num_envs=E, n_players=n, seed=3, flags=ol.ROBOCUP_DEFAULT_FLAGS if env_type == 0 else 0, **kw)
@@ -273,16 +282,16 @@ def test_bulk_compat_builder_equals_the_loop_builder(oracle_built, env_type, n, 
     hi = (5, 3, 3, 7) if env_type == 0 else (3, 3)
     for _ in range(6):
         obs, _, _ = ora.step(np.stack([rng.integers(0, k, (E, ora.A)) for k in hi], -1).astype(np.int32))
-    host = BatchedDynEnv.__new__(BatchedDynEnv)   # the builders only read the layout (no device, no handle)
-    host.layout, host.env_type = ora.layout, DynEnvType(env_type)
-    host.observationType = ObservationType.PARTIAL if partial else ObservationType.FULL
-    host.n_agents, host.obs_dim, host.closed = ora.A, ora.D, True
+    env_type, obs_type = DynEnvType(env_type), ObservationType.PARTIAL if partial else ObservationType.FULL
+    builder = CompatBuilder(row_groups(ora.layout, env_type, obs_type))   # reads the layout only (no device, no handle)
     counts = ora.counts()
-    loop = host._compat_obs(obs.copy(), counts)
-    bulk = host._compat_obs_bulk(obs.copy(), counts)
+    loop = compat_obs(ora.layout, env_type, obs_type, ora.A, obs.copy(), counts)
+    bulk = builder.array(obs.copy(), counts)
     assert bulk.shape == loop.shape == (E, ora.T, ora.A, 3) and bulk.dtype == object
     for idx in np.ndindex(*loop.shape):
         _deep_same(bulk[idx], loop[idx])
+    for e, t, ag in np.ndindex(*loop.shape[:3]):   # and the builder of one element, as LazyObsArray indexes it
+        _deep_same(builder.element(obs, counts, e, t, ag), list(loop[e, t, ag]))
     if not partial and env_type == 1:
         assert len({bulk[e, 0, 0, 0][1].shape[0] for e in range(E)}) > 1, "ragged obstacle lists must differ between environments"
 

@@ -11,6 +11,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
@@ -22,6 +23,7 @@ def main():
     import numpy as np
     import torch
     import arranger as oa
+    from compat_ref import compat_obs_of
     from dynenv_amd import BatchedDynEnv, DynEnvType, GpuInOutArranger, NoiseType, ObservationType, groups_for
     E = args.envs
     for cfg in ("driving_full", "robocup", "driving_partial"):
@@ -64,7 +66,7 @@ def main():
         b_out = sum(n_obj) * args.feat * 4 + padded.numel() * 4  # embeddings read once + every padded element written once
         # CPU: the numpy restatement of the reference arranger on a bounded sample of the same observations
         Es = min(E, 128)
-        compat = env._compat_obs(obs[:Es], count_env[:Es].cpu().numpy() if count_env is not None else None)
+        compat = compat_obs_of(env, obs[:Es], count_env[:Es] if count_env is not None else None)
         x = [[[list(compat[e, t, p, 0]) for p in range(env.n_agents)] for t in range(env.n_time_steps)] for e in range(Es)]
         t0 = time.perf_counter()
         o_in, o_cnt = oa.rearrange_inputs(x, len(types), Es * env.n_agents, env.n_time_steps)

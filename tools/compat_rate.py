@@ -5,9 +5,12 @@ import os
 import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, ROOT)
 import numpy as np
 import torch
+from compat_ref import compat_obs_of
 from dynenv_amd import DynEnvType, NoiseType, ObservationType, make_dyn_env
 
 
@@ -32,7 +35,7 @@ for E in (1024, 4096):
     dense, counts = obs._dense, obs._counts
     t2 = time.perf_counter()
     for _ in range(3):
-        loop = venv._compat_obs(dense, counts)
+        loop = compat_obs_of(venv, dense, counts)
     loop_ms = (time.perf_counter() - t2) / 3
     del loop
     venv.close()
