@@ -77,7 +77,46 @@ EXPORTS = ["dynenv_abi_version", "dynenv_last_error", "dynenv_create", "dynenv_d
            "dynenv_arrange_gather", "dynenv_arrange_scatter", "dynenv_arrange_pad", "dynenv_checkpoint_size",
            "dynenv_checkpoint_save", "dynenv_checkpoint_load", "dynenv_obs_pack", "dynenv_obs_unpack", "dynenv_obs_unpack_ranks",
            "dynenv_obs_pack_peers", "dynenv_obs_unpack_peers_ranks", "dynenv_step_head", "dynenv_full_obs", "dynenv_full_obs_dim",
-           "dynenv_global_state", "dynenv_global_state_dim", "dynenv_set_step_events"]
+           "dynenv_global_state", "dynenv_global_state_dim", "dynenv_set_step_events", "dynenv_get_states", "dynenv_set_states",
+           "dynenv_error_flags_env"]
+
+ERR_BAD_BLOB = 64  # error bit 6: a blob given to dynenv_set_states did not fit the handle and was not written
+SET_WRITTEN, SET_REJECTED, SET_BAD_INDEX = 0, 1, 2  # dynenv_set_states' per-blob status
+
+
+def state_struct(env_type):
+    """The ctypes struct of an environment type's canonical state blob (DynEnvType or its int: 0 RoboCup, 1 Driving)."""
+    return DrivingState if int(env_type) == 1 else RoboCupState
+
+
+def state_dtype(env_type):
+    """The numpy structured dtype of the blob - np.dtype of the ctypes struct, so offsets, pads and the item size are the C compiler's:
+    fields are edited with numpy (`blobs["cars"]["px"][:, 0] += 1`) instead of ctypes."""
+    import numpy as np
+    return np.dtype(state_struct(env_type))
+
+
+def blobs_as_states(blobs, env_type):
+    """uint8 [n, state_size] (or one blob [state_size]) -> structured array [n] (or [1]) of state_dtype(env_type): a view of the same
+    memory when `blobs` is C-contiguous, so edits land in it."""
+    import numpy as np
+    dt = state_dtype(env_type)
+    b = np.ascontiguousarray(blobs, dtype=np.uint8)
+    if b.ndim not in (1, 2) or b.shape[-1] != dt.itemsize:
+        raise ValueError("expected uint8 [n, %d], got %s" % (dt.itemsize, (b.shape,)))
+    return b.reshape(-1, dt.itemsize).view(dt).reshape(-1)
+
+
+def states_as_blobs(states):
+    """structured array [n] of a state_dtype (or a ctypes DrivingState / RoboCupState, or a list of them) -> uint8 [n, state_size]: a
+    view for a contiguous structured array, a copy for ctypes structs."""
+    import numpy as np
+    if isinstance(states, C.Structure):
+        states = [states]
+    if isinstance(states, (list, tuple)):
+        return np.stack([np.frombuffer(bytes(s), dtype=np.uint8) for s in states]) if len(states) else np.zeros((0, 0), np.uint8)
+    a = np.ascontiguousarray(states)
+    return a.reshape(-1).view(np.uint8).reshape(a.size, a.dtype.itemsize)
 
 ARR_MAX_TYPES = 4
 ARR_COUNT_CONST, ARR_COUNT_ENV, ARR_COUNT_ROW = 0, 1, 2
@@ -148,6 +187,9 @@ def load():
     lib.dynenv_state_size.argtypes = [vp]
     lib.dynenv_get_state.argtypes = [vp, C.c_int32, vp, C.c_size_t]
     lib.dynenv_set_state.argtypes = [vp, C.c_int32, vp, C.c_size_t]
+    lib.dynenv_get_states.argtypes = [vp, vp, C.c_int32, vp, vp]
+    lib.dynenv_set_states.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
+    lib.dynenv_error_flags_env.argtypes = [vp, vp, vp]
     lib.dynenv_sync.argtypes = [vp, vp]
     lib.dynenv_math_selftest.argtypes = [vp, vp, C.c_int32, vp, C.c_int32]
     lib.dynenv_error_flags.argtypes = [vp, C.POINTER(C.c_int32)]

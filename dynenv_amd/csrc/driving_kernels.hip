@@ -2175,3 +2175,132 @@ extern "C" __global__ void math_selftest_kernel(const double* x, const double* y
   out[5 * i + 0] = s; out[5 * i + 1] = c; out[5 * i + 2] = dm_atan2(y[i], x[i]);
   out[5 * i + 3] = dm_sqrt(dm_abs(x[i])); out[5 * i + 4] = (y[i] != 0.0) ? x[i] / y[i] : 0.0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// batched state transfer (dynenv_get_states / dynenv_set_states / dynenv_error_flags_env): the canonical blob of include/dynenv.h for
+// many environments in ONE launch, device memory on both sides.  One wave per listed environment (grid n), lane = body slot as in the
+// step kernels.  The blob travels between HBM and an LDS tile as contiguous 8-byte words across the wave (a blob is 8-byte aligned, no
+// more: dynenv.h); the lanes then read / write their own car or pedestrian struct in LDS, and every access to the field-major arrays is
+// one whole row of the environment per instruction ([e][32] doubles = one 256-byte segment).  No lane strides over the 128- / 64-byte
+// structs in global memory.  Same bytes as the per-environment host path of driving_tu.hip (get_state / set_state), which stays.
+// ------------------------------------------------------------------------------------------------
+#define DRV_BLOB_WORDS ((int)(sizeof(dynenv_driving_state_t) / 8))
+static_assert(sizeof(dynenv_driving_state_t) % 8 == 0, "the blob moves as 8-byte words");
+union DrvBlobTile {
+  dynenv_driving_state_t st;
+  unsigned long long q[DRV_BLOB_WORDS];
+};
+
+// idx == nullptr: environments 0..n-1.  An index outside [0, E) leaves its blob untouched.
+extern "C" __global__ void __launch_bounds__(64)
+drv_get_states_kernel(DrvState S, const int* __restrict__ idx, unsigned long long* __restrict__ blobs) {
+  __shared__ DrvBlobTile T;
+  const int lane = threadIdx.x, k = blockIdx.x, A = S.A;
+  const int e = idx ? uniform_i(idx[k]) : k;
+  if (e < 0 || e >= S.E) return;
+  const size_t E = (size_t)S.E, row = (size_t)e * DRV_NB;
+  for (int q = lane; q < DRV_BLOB_WORDS; q += 64) T.q[q] = 0ull;  // pads and unused car / pedestrian / obstacle slots read 0
+  const int ev = lane < EI_COUNT ? S.envi[(size_t)e * EI_COUNT + lane] : 0;
+  const int nPedRaw = bcast_i(ev, EI_NPED), nObstRaw = bcast_i(ev, EI_NOBST);
+  const int nPed = nPedRaw < 0 ? 0 : (nPedRaw > DRV_MAXP ? DRV_MAXP : nPedRaw), nObst = nObstRaw < 0 ? 0 : (nObstRaw > DRV_MAXO ? DRV_MAXO : nObstRaw);
+  double b[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, cx[CF_COUNT] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, ox = 0.0, oy = 0.0, er = 0.0, epos = 0.0;
+  int fl = 0, ax = 0;
+  if (lane < DRV_NB) {
+#pragma unroll
+    for (int f = 0; f < 6; ++f) b[f] = S.body[(size_t)f * E * DRV_NB + row + lane];  // BF_PX .. BF_W
+    fl = S.flags[row + lane]; ax = S.aux[row + lane];
+  }
+  if (lane < 16) {
+#pragma unroll
+    for (int f = 0; f < CF_COUNT; ++f) cx[f] = S.carx[(size_t)f * E * 16 + (size_t)e * 16 + lane];
+    er = S.epr[(size_t)e * 16 + lane]; epos = S.epr[E * 16 + (size_t)e * 16 + lane];
+  }
+  if (lane < DRV_MAXO) { ox = S.obst[(size_t)e * DRV_MAXO + lane]; oy = S.obst[E * DRV_MAXO + (size_t)e * DRV_MAXO + lane]; }
+  __syncthreads();
+  const int elapsed = bcast_i(ev, EI_ELAPSED), allFin = bcast_i(ev, EI_ALLFIN), episode = bcast_i(ev, EI_EPISODE);
+  if (lane == 0) {
+    T.st.elapsed = elapsed; T.st.all_finished = allFin; T.st.n_cars = A;
+    T.st.n_peds = nPedRaw; T.st.n_obst = nObstRaw; T.st.episode = episode;
+  }
+  if (lane < DYNENV_MAX_CARS) { T.st.episode_r[lane] = er; T.st.episode_pos_r[lane] = epos; }
+  if (lane < A) {
+    dynenv_car_state_t& c = T.st.cars[lane];
+    c.px = b[BF_PX]; c.py = b[BF_PY]; c.vx = b[BF_VX]; c.vy = b[BF_VY]; c.angle = b[BF_ANG]; c.w = b[BF_W];
+    c.dirx = cx[CF_DIRX]; c.diry = cx[CF_DIRY]; c.prevx = cx[CF_PREVX]; c.prevy = cx[CF_PREVY]; c.goalx = cx[CF_GOALX]; c.goaly = cx[CF_GOALY];
+    c.type = fl & 3; c.team = (fl >> 2) & 3; c.finished = (fl >> 4) & 1; c.crashed = (fl >> 5) & 1; c.fric = (fl >> 6) & 1; c.lane_pos = (fl >> 8) & 7;
+  }
+  if (lane >= DRV_SLOT_PED && lane < DRV_SLOT_PED + nPed) {
+    dynenv_ped_state_t& p = T.st.peds[lane - DRV_SLOT_PED];
+    p.px = b[BF_PX]; p.py = b[BF_PY]; p.vx = b[BF_VX]; p.vy = b[BF_VY];
+    p.road = fl & 1; p.side = (fl >> 1) & 1; p.dead = (fl >> 2) & 1; p.crossing = (fl >> 3) & 1; p.begin_crossing = (fl >> 4) & 1;
+    p.speed = (fl >> 8) & 15; p.moving = ax;
+  }
+  if (lane < nObst) { T.st.obst_x[lane] = ox; T.st.obst_y[lane] = oy; }
+  __syncthreads();
+  unsigned long long* out = blobs + (size_t)k * DRV_BLOB_WORDS;
+  for (int q = lane; q < DRV_BLOB_WORDS; q += 64) out[q] = T.q[q];
+}
+
+// status (may be nullptr): 0 written, 1 blob rejected (error bit 6 raised on the environment, nothing else touched), 2 index outside [0, E)
+extern "C" __global__ void __launch_bounds__(64)
+drv_set_states_kernel(DrvState S, const int* __restrict__ idx, const unsigned long long* __restrict__ blobs, int* __restrict__ status) {
+  __shared__ DrvBlobTile T;
+  const int lane = threadIdx.x, k = blockIdx.x, A = S.A;
+  const int e = idx ? uniform_i(idx[k]) : k;
+  if (e < 0 || e >= S.E) { if (status && lane == 0) status[k] = 2; return; }
+  const size_t E = (size_t)S.E, row = (size_t)e * DRV_NB;
+  const unsigned long long* in = blobs + (size_t)k * DRV_BLOB_WORDS;
+  for (int q = lane; q < DRV_BLOB_WORDS; q += 64) T.q[q] = in[q];
+  __syncthreads();
+  const int nPed = uniform_i(T.st.n_peds), nObst = uniform_i(T.st.n_obst);
+  if (uniform_i(T.st.n_cars) != A || nPed < 0 || nPed > DRV_MAXP || nObst < 0 || nObst > DRV_MAXO) {
+    if (lane == 0) { atomicOr(&S.envi[(size_t)e * EI_COUNT + EI_ERR], 64); if (status) status[k] = 1; }
+    return;
+  }
+  if (lane < DRV_NB) {
+    double b[BF_COUNT];
+#pragma unroll
+    for (int f = 0; f < BF_COUNT; ++f) b[f] = 0.0;
+    int fl = 0, ax = 0;
+    if (lane < A) {
+      const dynenv_car_state_t& c = T.st.cars[lane];
+      b[BF_PX] = c.px; b[BF_PY] = c.py; b[BF_VX] = c.vx; b[BF_VY] = c.vy; b[BF_ANG] = c.angle; b[BF_W] = c.w;
+      fl = CARF_PACK(c.type & 3, c.team & 3, c.finished & 1, c.crashed & 1, c.fric & 1, c.lane_pos & 7);
+    } else if (lane >= DRV_SLOT_PED && lane < DRV_SLOT_PED + nPed) {
+      const dynenv_ped_state_t& p = T.st.peds[lane - DRV_SLOT_PED];
+      b[BF_PX] = p.px; b[BF_PY] = p.py; b[BF_VX] = p.vx; b[BF_VY] = p.vy;
+      fl = PEDF_PACK(p.road & 1, p.side & 1, p.dead & 1, p.crossing & 1, p.begin_crossing & 1, p.speed & 15);
+      ax = p.moving;
+    }
+#pragma unroll
+    for (int f = 0; f < BF_COUNT; ++f) S.body[(size_t)f * E * DRV_NB + row + lane] = b[f];
+    S.flags[row + lane] = fl; S.aux[row + lane] = ax;
+  }
+  if (lane < 16) {
+    double cx[CF_COUNT] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (lane < A) {
+      const dynenv_car_state_t& c = T.st.cars[lane];
+      cx[CF_DIRX] = c.dirx; cx[CF_DIRY] = c.diry; cx[CF_PREVX] = c.prevx; cx[CF_PREVY] = c.prevy; cx[CF_GOALX] = c.goalx; cx[CF_GOALY] = c.goaly;
+    }
+#pragma unroll
+    for (int f = 0; f < CF_COUNT; ++f) S.carx[(size_t)f * E * 16 + (size_t)e * 16 + lane] = cx[f];
+    S.epr[(size_t)e * 16 + lane] = lane < DYNENV_MAX_CARS ? T.st.episode_r[lane] : 0.0;
+    S.epr[E * 16 + (size_t)e * 16 + lane] = lane < DYNENV_MAX_CARS ? T.st.episode_pos_r[lane] : 0.0;
+  }
+  if (lane < DRV_MAXO) {
+    S.obst[(size_t)e * DRV_MAXO + lane] = lane < nObst ? T.st.obst_x[lane] : 0.0;
+    S.obst[E * DRV_MAXO + (size_t)e * DRV_MAXO + lane] = lane < nObst ? T.st.obst_y[lane] : 0.0;
+  }
+  if (lane < EI_COUNT) {  // the whole row: contact-cache occupancy, error word, shortcut bits and the diagnostics start over at 0
+    const int v = lane == EI_ELAPSED ? T.st.elapsed : lane == EI_ALLFIN ? T.st.all_finished : lane == EI_NPED ? nPed :
+                  lane == EI_NOBST ? nObst : lane == EI_EPISODE ? T.st.episode : 0;
+    S.envi[(size_t)e * EI_COUNT + lane] = v;
+  }
+  S.lastcand[(size_t)e * 64 + lane] = -1;  // quiescent shortcut state unknown
+  if (status && lane == 0) status[k] = 0;
+}
+
+extern "C" __global__ void drv_error_flags_env_kernel(DrvState S, int* __restrict__ flags) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < S.E) flags[e] = S.envi[(size_t)e * EI_COUNT + EI_ERR];
+}

@@ -389,6 +389,20 @@ struct HOST_LOCAL DrvHandle final : dynenv {
     return DYNENV_OK;
   }
 
+  // many environments in one launch, device memory on both sides (drv_get_states_kernel / drv_set_states_kernel: one wave per blob)
+  int get_states(const int32_t* idx, int32_t n, void* blobs, hipStream_t st) override {
+    hipLaunchKernelGGL(drv_get_states_kernel, dim3(n), dim3(64), 0, st, S, (const int*)idx, (unsigned long long*)blobs);
+    return launched();
+  }
+  int set_states(const int32_t* idx, int32_t n, const void* blobs, int32_t* status, hipStream_t st) override {
+    hipLaunchKernelGGL(drv_set_states_kernel, dim3(n), dim3(64), 0, st, S, (const int*)idx, (const unsigned long long*)blobs, (int*)status);
+    return launched();
+  }
+  int error_flags_env(int32_t* flags, hipStream_t st) override {
+    hipLaunchKernelGGL(drv_error_flags_env_kernel, dim3((S.E + 63) / 64), dim3(64), 0, st, S, (int*)flags);
+    return launched();
+  }
+
   // the scheduler's lists describe the timing of the steps this handle ran, not the state just restored: start them over
   // (a list that keeps ids from before the restore could be appended to without having been cleared - ADVICE r3)
   int checkpoint_loaded() override {

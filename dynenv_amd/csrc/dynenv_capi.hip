@@ -182,6 +182,32 @@ int dynenv_set_state(dynenv_t* h, int32_t env, const void* blob, size_t nbytes) 
   return h->set_state(env, blob);
 }
 
+// the batched, device-side forms: ordered on `stream`, no host synchronisation, no allocation, no host copy
+static int states_args(const dynenv_t* h, const int32_t* idx, int32_t n, const void* blobs) {
+  if (!h || (!blobs && n != 0)) return fail(DYNENV_ERR_ARG, "null argument");
+  if (n < 0) return fail(DYNENV_ERR_ARG, "negative blob count");
+  if (!idx && n > h->cfg.num_envs) return fail(DYNENV_ERR_ARG, "more blobs than environments and no index list");
+  if ((uintptr_t)blobs % 8) return fail(DYNENV_ERR_ARG, "the blobs must be 8-byte aligned");
+  return DYNENV_OK;
+}
+int dynenv_get_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, void* blobs_dev, void* stream) {
+  if (int rc = states_args(h, env_idx_dev, n, blobs_dev)) return rc;
+  if (n == 0) return DYNENV_OK;
+  ON_DEVICE(h);
+  return h->get_states(env_idx_dev, n, blobs_dev, (hipStream_t)stream);
+}
+int dynenv_set_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const void* blobs_dev, int32_t* status_dev, void* stream) {
+  if (int rc = states_args(h, env_idx_dev, n, blobs_dev)) return rc;
+  if (n == 0) return DYNENV_OK;
+  ON_DEVICE(h);
+  return h->set_states(env_idx_dev, n, blobs_dev, status_dev, (hipStream_t)stream);
+}
+int dynenv_error_flags_env(dynenv_t* h, int32_t* flags_dev, void* stream) {
+  if (!h || !flags_dev) return fail(DYNENV_ERR_ARG, "null argument");
+  ON_DEVICE(h);
+  return h->error_flags_env(flags_dev, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------------
 // ragged -> padded arranger (arranger_kernels.hip); replaces InOutArranger (reference models/models.py:208-274)
 // ------------------------------------------------------------------------------------------------

@@ -67,6 +67,12 @@ struct HOST_LOCAL dynenv {
   virtual int episode_stats(double* ep_r, double* ep_pos_r, double* ep_obs_r, int32_t* goals, hipStream_t st) = 0;
   virtual int get_state(int32_t env, void* blob) = 0;        // (env and the blob's size are checked by the entry point)
   virtual int set_state(int32_t env, const void* blob) = 0;
+  // the batched, device-side forms: n blobs state_bytes apart in device memory, one launch on `st`, no host synchronisation, allocation
+  // or copy.  idx (device, may be nullptr: environments 0..n-1) and n are checked by the entry point as far as the host can see them;
+  // the kernels skip an index outside [0, E).  status (may be nullptr): int32 [n] = 0 written, 1 blob rejected, 2 index out of range
+  virtual int get_states(const int32_t* idx, int32_t n, void* blobs, hipStream_t st) = 0;
+  virtual int set_states(const int32_t* idx, int32_t n, const void* blobs, int32_t* status, hipStream_t st) = 0;
+  virtual int error_flags_env(int32_t* flags, hipStream_t st) = 0;  // int32 [E]: every environment's error word
   virtual int debug_counters(int64_t* out16) = 0;
   virtual int debug_placement(uint32_t*, int32_t) { return 0; }  // (Driving's SIMD isolation only: 0 words recorded)
   virtual int checkpoint_loaded() { return DYNENV_OK; }      // behind dynenv_checkpoint_load's copies

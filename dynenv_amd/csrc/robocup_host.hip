@@ -278,4 +278,18 @@ struct HOST_LOCAL RcHandle final : dynenv {
     HIP_OK(hipMemcpy(R.envd + (size_t)env * RD_COUNT, envd, sizeof(envd), hipMemcpyHostToDevice));
     return DYNENV_OK;
   }
+
+  // many environments in one launch, device memory on both sides (rc_get_states_kernel / rc_set_states_kernel: one wave per blob)
+  int get_states(const int32_t* idx, int32_t n, void* blobs, hipStream_t st) override {
+    hipLaunchKernelGGL(rc_get_states_kernel, dim3(n), dim3(64), 0, st, R, (const int*)idx, (unsigned long long*)blobs);
+    return launched();
+  }
+  int set_states(const int32_t* idx, int32_t n, const void* blobs, int32_t* status, hipStream_t st) override {
+    hipLaunchKernelGGL(rc_set_states_kernel, dim3(n), dim3(64), 0, st, R, (const int*)idx, (const unsigned long long*)blobs, (int*)status);
+    return launched();
+  }
+  int error_flags_env(int32_t* flags, hipStream_t st) override {
+    hipLaunchKernelGGL(rc_error_flags_env_kernel, dim3((R.E + 63) / 64), dim3(64), 0, st, R, (int*)flags);
+    return launched();
+  }
 };

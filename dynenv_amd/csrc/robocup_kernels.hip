@@ -2305,3 +2305,178 @@ extern "C" __global__ void rc_stats_kernel(RcState S, double* ep_r, double* ep_p
 
 #define RC_PARTIAL_FUNCTIONS
 #include "robocup_partial.hip"
+
+// ------------------------------------------------------------------------------------------------
+// batched state transfer (dynenv_get_states / dynenv_set_states / dynenv_error_flags_env), behind everything the step launches run so
+// that the step code keeps its addresses (rc_layout_pad above).  One wave per listed environment (grid n), lane = body slot (feet 2r,
+// 2r + 1 of robot r, the ball at RC_BALL) or robot.  The blob (2552 bytes: 8-byte aligned, not 16) travels between HBM and an LDS tile
+// as contiguous 8-byte words across the wave; the lanes read / write their robot's struct in LDS, and every access to the field-major
+// arrays is one whole row of the environment per instruction.  Same bytes as the per-environment host path of robocup_host.hip.
+// ------------------------------------------------------------------------------------------------
+#define RC_BLOB_WORDS ((int)(sizeof(dynenv_robocup_state_t) / 8))
+static_assert(sizeof(dynenv_robocup_state_t) % 8 == 0, "the blob moves as 8-byte words");
+static_assert(RE_COUNT <= 64 && RD_COUNT <= 64, "an environment's int / double row is one access of the wave");
+union RcBlobTile {
+  dynenv_robocup_state_t st;
+  unsigned long long q[RC_BLOB_WORDS];
+};
+// the twelve doubles a robot's struct starts with: left foot px py vx vy angle w, right foot the same
+DE_DEV double* rc_blob_foot(dynenv_robot_state_t& r, int side) { return reinterpret_cast<double*>(&r) + 6 * side; }
+static_assert(offsetof(dynenv_robot_state_t, rpx) == 6 * sizeof(double) && offsetof(dynenv_robot_state_t, head_angle) == 12 * sizeof(double), "foot blocks");
+
+// idx == nullptr: environments 0..n-1.  An index outside [0, E) leaves its blob untouched.
+extern "C" __global__ void __launch_bounds__(64)
+rc_get_states_kernel(RcState S, const int* __restrict__ idx, unsigned long long* __restrict__ blobs) {
+  __shared__ RcBlobTile T;
+  __shared__ int envi[64];
+  __shared__ double envd[RD_COUNT];
+  const int lane = threadIdx.x, k = blockIdx.x, R = S.R;
+  const int e = idx ? uniform_i(idx[k]) : k;
+  if (e < 0 || e >= S.E) return;
+  const size_t E = (size_t)S.E, row = (size_t)e * RC_NB, r16 = (size_t)e * 16;
+  for (int q = lane; q < RC_BLOB_WORDS; q += 64) T.q[q] = 0ull;  // the pads and the slots of robots this handle does not have read 0
+  envi[lane] = lane < RE_COUNT ? S.envi[(size_t)e * RE_COUNT + lane] : 0;
+  if (lane < RD_COUNT) envd[lane] = S.envd[(size_t)e * RD_COUNT + lane];
+  double b[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, rr[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, er = 0.0, epos = 0.0;
+  int ri[RI_COUNT] = {0, 0, 0};
+  if (lane < RC_NB) {
+#pragma unroll
+    for (int f = 0; f < 6; ++f) b[f] = S.body[(size_t)f * E * RC_NB + row + lane];  // RB_PX .. RB_W
+  }
+  if (lane < 16) {
+#pragma unroll
+    for (int f = 0; f < 9; ++f) rr[f] = S.rob[(size_t)f * E * 16 + r16 + lane];  // RR_HEAD .. RR_MOVET
+#pragma unroll
+    for (int f = 0; f < RI_COUNT; ++f) ri[f] = S.robi[(size_t)f * E * 16 + r16 + lane];
+    er = S.epr[r16 + lane]; epos = S.epr[E * 16 + r16 + lane];
+  }
+  __syncthreads();
+  if (lane < 2 * R) {
+    double* d = rc_blob_foot(T.st.robots[lane >> 1], lane & 1);
+    d[0] = b[RB_PX]; d[1] = b[RB_PY]; d[2] = b[RB_VX]; d[3] = b[RB_VY]; d[4] = b[RB_ANG]; d[5] = b[RB_W];
+  }
+  if (lane == RC_BALL) { T.st.bpx = b[RB_PX]; T.st.bpy = b[RB_PY]; T.st.bvx = b[RB_VX]; T.st.bvy = b[RB_VY]; T.st.bw = b[RB_W]; }
+  if (lane < R) {
+    dynenv_robot_state_t& s = T.st.robots[lane];
+    const int f = ri[RI_FLAGS];
+    s.head_angle = rr[RR_HEAD]; s.head_moving = rr[RR_HEADMOV]; s.prevx = rr[RR_PREVX]; s.prevy = rr[RR_PREVY];
+    s.initx = rr[RR_INITX]; s.inity = rr[RR_INITY]; s.penal_time = rr[RR_PENALT]; s.fall_time = rr[RR_FALLT]; s.move_time = rr[RR_MOVET];
+    s.team = (f & RF_TEAMPOS) ? 1 : -1; s.penalized = !!(f & RF_PENAL); s.touching = !!(f & RF_TOUCH); s.might_push = !!(f & RF_PUSH);
+    s.fallen = !!(f & RF_FALLEN); s.kicking = !!(f & RF_KICK); s.foot = !!(f & RF_FOOT); s.joint_removed = !!(f & RF_JREM);
+    s.touch_cntr = ri[RI_TOUCHC]; s.fall_cntr = ri[RI_FALLC];
+  }
+  if (lane < DYNENV_MAX_ROBOTS) { T.st.episode_r[lane] = er; T.st.episode_pos_r[lane] = epos; }
+  if (lane < 2) {  // the defenders are a set on the device: reported as an ascending id list
+    int n = 0;
+    for (int i = 0; i < DYNENV_MAX_ROBOTS; ++i) if (envi[RE_DEF0 + lane] & (1 << i)) T.st.defenders[lane][n++] = i;
+    T.st.n_def[lane] = n;
+    T.st.penal_times[lane] = envd[RD_PT0 + lane];
+    T.st.goals[lane] = envi[RE_GOAL0 + lane]; T.st.closest[lane] = envi[RE_CLOSE0 + lane];
+  }
+  if (lane < 4) T.st.last_kicked[lane] = lane < envi[RE_NLK] ? envi[RE_LK0 + lane] : 0;
+  if (lane == 0) {
+    T.st.elapsed = envi[RE_ELAPSED]; T.st.n_robots = R; T.st.ball_owned = envi[RE_OWNED]; T.st.n_last_kicked = envi[RE_NLK];
+    T.st.episode = envi[RE_EPISODE];
+    T.st.ball_free_cntr = envd[RD_FREECNT]; T.st.grace_period = envd[RD_GRACE]; T.st.bprevx = envd[RD_BPREVX]; T.st.bprevy = envd[RD_BPREVY];
+  }
+  __syncthreads();
+  unsigned long long* out = blobs + (size_t)k * RC_BLOB_WORDS;
+  for (int q = lane; q < RC_BLOB_WORDS; q += 64) out[q] = T.q[q];
+}
+
+// status (may be nullptr): 0 written, 1 blob rejected (error bit 6 raised on the environment, nothing else touched), 2 index outside [0, E)
+extern "C" __global__ void __launch_bounds__(64)
+rc_set_states_kernel(RcState S, const int* __restrict__ idx, const unsigned long long* __restrict__ blobs, int* __restrict__ status) {
+  __shared__ RcBlobTile T;
+  __shared__ int envi[64];
+  const int lane = threadIdx.x, k = blockIdx.x, R = S.R;
+  const int e = idx ? uniform_i(idx[k]) : k;
+  if (e < 0 || e >= S.E) { if (status && lane == 0) status[k] = 2; return; }
+  const size_t E = (size_t)S.E, row = (size_t)e * RC_NB, r16 = (size_t)e * 16;
+  const unsigned long long* in = blobs + (size_t)k * RC_BLOB_WORDS;
+  for (int q = lane; q < RC_BLOB_WORDS; q += 64) T.q[q] = in[q];
+  envi[lane] = 0;
+  __syncthreads();
+  {
+    const int nd0 = uniform_i(T.st.n_def[0]), nd1 = uniform_i(T.st.n_def[1]);
+    bool bad = uniform_i(T.st.n_robots) != R || nd0 < 0 || nd0 > DYNENV_MAX_ROBOTS || nd1 < 0 || nd1 > DYNENV_MAX_ROBOTS;
+    bool badId = false;
+    if (lane < 2 * DYNENV_MAX_ROBOTS) {
+      const int t = lane / DYNENV_MAX_ROBOTS, i = lane - t * DYNENV_MAX_ROBOTS, id = T.st.defenders[t][i];
+      badId = i < (t ? nd1 : nd0) && (id < 0 || id >= DYNENV_MAX_ROBOTS);
+    }
+    if (bad || wave_ballot(badId) != 0ull) {
+      if (lane == 0) { atomicOr(&S.envi[(size_t)e * RE_COUNT + RE_ERR], 64); if (status) status[k] = 1; }
+      return;
+    }
+  }
+  if (lane < RC_NB) {
+    double b[RB_COUNT + 4];
+#pragma unroll
+    for (int f = 0; f < RB_COUNT + 4; ++f) b[f] = 0.0;  // velocity biases, forces and torque (a pending fall force) start over at 0
+    if (lane < 2 * R) {
+      const double* d = rc_blob_foot(T.st.robots[lane >> 1], lane & 1);
+      b[RB_PX] = d[0]; b[RB_PY] = d[1]; b[RB_VX] = d[2]; b[RB_VY] = d[3]; b[RB_ANG] = d[4]; b[RB_W] = d[5];
+      const DevSC sc = dev_sincos_inl(b[RB_ANG]);  // shape cache = geometry at cpSpaceAddShape time; dm_sincos, as the host path
+      b[RB_COUNT + 0] = b[RB_PX]; b[RB_COUNT + 1] = b[RB_PY]; b[RB_COUNT + 2] = sc.c; b[RB_COUNT + 3] = sc.s;
+    } else if (lane == RC_BALL) {
+      b[RB_PX] = T.st.bpx; b[RB_PY] = T.st.bpy; b[RB_VX] = T.st.bvx; b[RB_VY] = T.st.bvy; b[RB_W] = T.st.bw;
+      b[RB_COUNT + 0] = T.st.bpx; b[RB_COUNT + 1] = T.st.bpy; b[RB_COUNT + 2] = 1.0;
+    }
+#pragma unroll
+    for (int f = 0; f < RB_COUNT + 4; ++f) S.body[(size_t)f * E * RC_NB + row + lane] = b[f];
+  }
+  bool jrem = false;
+  if (lane < 16) {
+    double rr[RR_COUNT];
+#pragma unroll
+    for (int f = 0; f < RR_COUNT; ++f) rr[f] = 0.0;  // RR_JX, RR_JY, RR_JROT: the joints' accumulated impulses start over at 0
+    int ri[RI_COUNT] = {0, 0, 0};
+    if (lane < R) {
+      const dynenv_robot_state_t& s = T.st.robots[lane];
+      rr[RR_HEAD] = s.head_angle; rr[RR_HEADMOV] = s.head_moving; rr[RR_PREVX] = s.prevx; rr[RR_PREVY] = s.prevy;
+      rr[RR_INITX] = s.initx; rr[RR_INITY] = s.inity; rr[RR_PENALT] = s.penal_time; rr[RR_FALLT] = s.fall_time; rr[RR_MOVET] = s.move_time;
+      ri[RI_FLAGS] = (s.team > 0 ? RF_TEAMPOS : 0) | (s.penalized ? RF_PENAL : 0) | (s.touching ? RF_TOUCH : 0) | (s.might_push ? RF_PUSH : 0) |
+                     (s.fallen ? RF_FALLEN : 0) | (s.kicking ? RF_KICK : 0) | (s.foot ? RF_FOOT : 0) | (s.joint_removed ? RF_JREM : 0);
+      ri[RI_TOUCHC] = s.touch_cntr; ri[RI_FALLC] = s.fall_cntr;
+      jrem = s.joint_removed != 0;
+    }
+#pragma unroll
+    for (int f = 0; f < RR_COUNT; ++f) S.rob[(size_t)f * E * 16 + r16 + lane] = rr[f];
+#pragma unroll
+    for (int f = 0; f < RI_COUNT; ++f) S.robi[(size_t)f * E * 16 + r16 + lane] = ri[f];
+    S.epr[r16 + lane] = lane < DYNENV_MAX_ROBOTS ? T.st.episode_r[lane] : 0.0;
+    S.epr[E * 16 + r16 + lane] = lane < DYNENV_MAX_ROBOTS ? T.st.episode_pos_r[lane] : 0.0;
+  }
+  // the environment's int row, built in LDS.  Constraint order: robot r's pivot joint (2r; absent once removed) then its rotary limit
+  // (2r + 1), robots in id order - the entries in front of robot r are 2r minus the removed joints below it
+  const uint64_t jremMask = wave_ballot(jrem);
+  if (lane < R) {
+    int at = RE_CORDER + 2 * lane - __popcll(jremMask & lanemask_lt());
+    if (!jrem) envi[at++] = 2 * lane;
+    envi[at] = 2 * lane + 1;
+  }
+  if (lane < 2) {
+    int m = 0;
+    for (int i = 0; i < T.st.n_def[lane]; ++i) m |= 1 << T.st.defenders[lane][i];
+    envi[RE_DEF0 + lane] = m; envi[RE_GOAL0 + lane] = T.st.goals[lane]; envi[RE_CLOSE0 + lane] = T.st.closest[lane];
+  }
+  if (lane < 4) envi[RE_LK0 + lane] = T.st.last_kicked[lane];
+  if (lane == 0) {
+    envi[RE_ELAPSED] = T.st.elapsed; envi[RE_OWNED] = T.st.ball_owned; envi[RE_NLK] = T.st.n_last_kicked;
+    envi[RE_NCON] = 2 * R - __popcll(jremMask); envi[RE_EPISODE] = T.st.episode;  // RE_OCC, RE_ERR, RE_PIVFIRST: 0
+  }
+  __syncthreads();
+  if (lane < RE_COUNT) S.envi[(size_t)e * RE_COUNT + lane] = envi[lane];
+  if (lane < RD_COUNT) {
+    const double v = lane == RD_FREECNT ? T.st.ball_free_cntr : lane == RD_GRACE ? T.st.grace_period : lane == RD_PT0 ? T.st.penal_times[0] :
+                     lane == RD_PT1 ? T.st.penal_times[1] : lane == RD_BPREVX ? T.st.bprevx : lane == RD_BPREVY ? T.st.bprevy : 0.0;
+    S.envd[(size_t)e * RD_COUNT + lane] = v;
+  }
+  if (status && lane == 0) status[k] = 0;
+}
+
+extern "C" __global__ void rc_error_flags_env_kernel(RcState S, int* __restrict__ flags) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < S.E) flags[e] = S.envi[(size_t)e * RE_COUNT + RE_ERR];
+}

@@ -347,6 +347,106 @@ class BatchedDynEnv(object):
         self._needs_reset = False
         self._episode_step = step
 
+    # ------------------------------------------------------------------ batched, device-side state transfer
+    @property
+    def state_size(self):
+        """bytes of one canonical state blob (_capi.state_dtype(self.env_type).itemsize)"""
+        return int(self._lib.dynenv_state_size(self._h))
+
+    def _env_ids(self, env_ids, unique=False):
+        """-> (int32 [n] tensor on the device or None = environments 0..n-1, n).  A list / numpy array / host tensor is uploaded with one
+        copy and, with `unique`, checked for duplicates first; ids that already live on the device are taken as they are (nothing is
+        read back: an id outside [0, E) is skipped by the kernels, dynenv_set_states reports it in its status)."""
+        torch = self._torch
+        if env_ids is None:
+            return None, self.num_envs
+        if isinstance(env_ids, torch.Tensor) and env_ids.device.type != "cpu":
+            ids = env_ids.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+            return ids, int(ids.numel())
+        host = np.asarray(env_ids.numpy() if isinstance(env_ids, torch.Tensor) else env_ids).reshape(-1).astype(np.int64)
+        if unique and np.unique(host).size != host.size:
+            raise _capi.DynEnvError("set_states: an environment id is listed twice (its state would be unspecified)")
+        if host.size and (host.min() < -2 ** 31 or host.max() >= 2 ** 31):
+            raise _capi.DynEnvError("environment ids must fit int32")
+        return torch.as_tensor(host.astype(np.int32)).to(self.device), int(host.size)
+
+    def get_states(self, env_ids=None):
+        """The canonical state blobs of `env_ids` (a list, a numpy array or a device tensor; None = all environments, in order) as a
+        torch.uint8 [n, state_size] tensor on the device: ONE launch on torch's current stream, nothing is waited for and nothing
+        touches the host.  Row k holds exactly the bytes get_state(env_ids[k]) returns; `_capi.blobs_as_states(t.cpu().numpy(),
+        env_type)` views them as a numpy structured array.  An id outside [0, num_envs) leaves its row as allocated (unspecified)."""
+        ids, n = self._env_ids(env_ids)
+        out = self._torch.empty((n, self.state_size), dtype=self._torch.uint8, device=self.device)
+        _capi.check(self._lib.dynenv_get_states(self._h, C.c_void_p(ids.data_ptr() if ids is not None and n else None), n,
+                                                C.c_void_p(out.data_ptr() if n else None), self._stream()), "dynenv_get_states")
+        return out
+
+    def set_states(self, env_ids, blobs, episode_step=None):
+        """Write blobs[k] into environment env_ids[k] (None = environments 0..n-1), all in ONE launch on torch's current stream.  `blobs`
+        is a uint8 [n, state_size] device tensor (used in place) or a numpy array - uint8 [n, state_size] or a structured array of
+        `_capi.state_dtype` - uploaded with one copy.  Each environment ends up exactly as set_state() leaves it: whole field rows
+        rewritten, contact cache and error word cleared.  Returns the per-blob status as an int32 [n] device tensor (not read here):
+        0 written, 1 blob rejected - it does not fit this handle; the environment is untouched and carries error bit 6 until it is
+        reset or validly set, step() raises on it -, 2 id outside [0, num_envs).
+
+        Episodes are lock-step: `dones` and the auto-reset follow ONE host-side position in the episode.  Unlike set_state,
+        which moves that position to the blob's `elapsed`, this call reads nothing back and leaves it where it is unless `episode_step`
+        says where the batch now stands; blobs whose `elapsed` differs from it keep their own time on the device, and `dones` is not
+        meaningful for them.  On a handle that was never reset there is no position to keep: pass `episode_step` then.
+        Duplicate ids in one call are an error (raised when the ids live on the host, unspecified state otherwise)."""
+        torch = self._torch
+        if self._needs_reset and episode_step is None:
+            raise _capi.DynEnvError("set_states before the first reset(): pass episode_step (the batch's position in its lock-step episode)")
+        ids, n = self._env_ids(env_ids, unique=True)
+        size = self.state_size
+        if isinstance(blobs, torch.Tensor):
+            b = blobs
+            if b.dtype != torch.uint8:
+                raise _capi.DynEnvError("set_states: blobs must be uint8 [n, %d]" % size)
+            if b.device != self.device or not b.is_contiguous():
+                b = b.to(self.device).contiguous()
+        else:
+            host = blobs if isinstance(blobs, np.ndarray) and blobs.dtype == np.uint8 else _capi.states_as_blobs(blobs)
+            b = torch.as_tensor(np.ascontiguousarray(host)).to(self.device)
+        if b.dim() != 2 or b.shape[1] != size:
+            raise _capi.DynEnvError("set_states: blobs must be uint8 [n, %d], got shape %s" % (size, tuple(b.shape)))
+        if ids is None:
+            n = int(b.shape[0])  # environments 0..n-1
+            if n > self.num_envs:
+                raise _capi.DynEnvError("set_states: %d blobs for %d environments" % (n, self.num_envs))
+        elif int(b.shape[0]) != n:
+            raise _capi.DynEnvError("set_states: %d environment ids but %d blobs" % (n, int(b.shape[0])))
+        status = torch.empty((n,), dtype=torch.int32, device=self.device)
+        _capi.check(self._lib.dynenv_set_states(self._h, C.c_void_p(ids.data_ptr() if ids is not None and n else None), n,
+                                                C.c_void_p(b.data_ptr() if n else None), C.c_void_p(status.data_ptr() if n else None),
+                                                self._stream()), "dynenv_set_states")
+        self._counts_np = None  # the scenes (obstacle / pedestrian counts) may have changed
+        if episode_step is not None:
+            self._episode_step = int(episode_step)
+            self._needs_reset = False
+        return status
+
+    def fork(self, src_ids, dst_ids):
+        """Copy the state of environment src_ids[k] over environment dst_ids[k] - set_states(dst_ids, get_states(src_ids)): two launches,
+        no host copy.  One source may be listed many times (branch one state into many environments), a destination once.  Like
+        set_state, the copy drops the contact cache (warm-started impulses), so source and copy are the same canonical state, not the
+        same checkpoint.  A forked environment keeps its OWN random stream: draws are keyed by the environment's global id, the
+        episode counter and the time inside the episode, and the id is the destination's - so the copy's later random events
+        (pedestrian starts, observation noise, ...) are its own, not a replay of the source's.  Returns set_states' status tensor."""
+        return self.set_states(dst_ids, self.get_states(src_ids))
+
+    def error_flags_per_env(self):
+        """Every environment's error word (the bits of include/dynenv.h's dynenv_error_flags) as an int32 [num_envs] device tensor: one
+        launch, nothing waited for.  Its OR over the environments is error_flags()."""
+        f = self._torch.empty((self.num_envs,), dtype=self._torch.int32, device=self.device)
+        _capi.check(self._lib.dynenv_error_flags_env(self._h, C.c_void_p(f.data_ptr()), self._stream()), "dynenv_error_flags_env")
+        return f
+
+    def _first_env_with(self, bit):
+        """lowest id of an environment whose error word has `bit` (the compat step names it so that the caller can repair that one)"""
+        hit = np.nonzero(self.error_flags_per_env().cpu().numpy() & bit)[0]
+        return int(hit[0]) if hit.size else -1
+
     # ------------------------------------------------------------------ exact checkpoint (SURVEY §8 f4)
     def checkpoint(self):
         """Every device array of the handle, bit for bit, as a numpy uint8 array (contact cache, shortcut state, episode
@@ -458,18 +558,25 @@ class BatchedDynEnv(object):
         glob_dev = self.global_state() if self.env_type == DynEnvType.ROBO_CUP else None  # 252 B per environment, one short launch
         rewards = self.rewards.cpu().numpy().copy()
         robocup, partial = self.env_type == DynEnvType.ROBO_CUP, self.observationType == ObservationType.PARTIAL
-        flags = self.error_flags() if robocup or partial else 0  # one read: each is a device synchronisation and a copy of the flags
+        flags = self.error_flags()  # ONE read per step: it is a device synchronisation and a copy of the flags
         if partial and flags & 8:
             # the reference's observation lists have no cap (DrivingEnvironment.py:816-890); the dense layout has, and rows beyond it were
             # dropped: not the reference's observation any more - never silently (include/dynenv.h, error bit 3)
-            raise _capi.DynEnvError("Partial observation: a list had more rows than the dense layout's capacity; rows were dropped (error bit 3)")
+            raise _capi.DynEnvError("Partial observation: a list had more rows than the dense layout's capacity; rows were dropped (error bit 3), "
+                                    "first in environment %d" % self._first_env_with(8))
         if robocup and flags & 32:
-            raise _capi.DynEnvError("RoboCup: a velocity or joint impulse left the finite range (error bit 5): the state is not the reference's any more")
+            raise _capi.DynEnvError("RoboCup: a velocity or joint impulse left the finite range (error bit 5): the state is not the reference's any more; "
+                                    "first in environment %d" % self._first_env_with(32))
         if robocup and flags & 16:
             # two capsule cores exactly collinear / exactly touching: the sign of the contact normal is a convention there
             # (Robot.py:38-52; include/dynenv.h, error bit 4) - possibly not pymunk's trajectory from here on, never silently
             raise _capi.DynEnvError("RoboCup: the cores of two feet are exactly collinear / touching: the contact normal's sign is a convention "
-                                    "(error bit 4); reset() or set_state() clears it")
+                                    "(error bit 4); reset() or set_state() clears it; first in environment %d (set_states() repairs that one alone)"
+                                    % self._first_env_with(16))
+        if flags & _capi.ERR_BAD_BLOB:
+            # a blob that did not fit the handle was refused by set_states: that environment still holds its OLD state - never silently
+            raise _capi.DynEnvError("set_states: a blob did not fit this handle and was not written (error bit 6): environment %d still holds its "
+                                    "earlier state; a valid set_states() of it or reset() clears the bit" % self._first_env_with(_capi.ERR_BAD_BLOB))
         done = bool(self.last_done)
         dones = np.full((self.num_envs,), done, dtype=bool)
         # The step's observations stay in HBM (a snapshot: self.obs is rewritten by the next step) until somebody looks at them:

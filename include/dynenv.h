@@ -207,6 +207,21 @@ size_t dynenv_state_size(const dynenv_t* h);
 int dynenv_get_state(dynenv_t* h, int32_t env_idx, void* host_blob, size_t nbytes);
 int dynenv_set_state(dynenv_t* h, int32_t env_idx, const void* host_blob, size_t nbytes);
 
+/* The same for MANY environments in one launch, device memory on both sides: blobs_dev holds n canonical blobs dynenv_state_size(h)
+ * bytes apart, 8-byte aligned (no more: the RoboCup blob is 2552 bytes); env_idx_dev int32 [n] names the environment of each blob,
+ * NULL = environments 0..n-1.  Ordered on `stream`: no host synchronisation, no allocation, no host copy.
+ *   dynenv_get_states  writes, per listed environment, exactly the bytes dynenv_get_state writes (pads and unused car / pedestrian /
+ *                      obstacle / robot slots zeroed, RoboCup defenders as an ascending id list).  An index outside [0, E) leaves its
+ *                      blob untouched.
+ *   dynenv_set_states  leaves every device array of the handle in exactly the bytes dynenv_set_state produces for a valid blob (whole
+ *                      field rows rewritten, contact cache and the environment's error word cleared).  A blob that does not fit -
+ *                      Driving: n_cars != A, n_peds / n_obst outside 0..20; RoboCup: n_robots != R, an n_def[t] outside 0..10, a
+ *                      listed defender id outside 0..9 - leaves its environment untouched and raises error bit 6 on it.
+ *                      status_dev (may be NULL) int32 [n]: 0 written, 1 blob rejected, 2 index outside [0, E) (entry skipped).
+ *                      The same index twice in one call is a caller error: that environment's state is unspecified then. */
+int dynenv_get_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, void* blobs_dev, void* stream);
+int dynenv_set_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const void* blobs_dev, int32_t* status_dev, void* stream);
+
 int dynenv_sync(dynenv_t* h, void* stream);
 
 /* OR over all environments of the kernels' error flags (bit 0: contact cache overflow, a pair was dropped; bit 1: an action
@@ -224,8 +239,13 @@ int dynenv_sync(dynenv_t* h, void* stream);
  * set_state; the host mirror's step() raises on it; bit 5 (value 32):
  * RoboCup, a foot velocity or a joint impulse left the finite range during a solve (never seen): the joints' arithmetic drops
  * products that are zeros for finite operands only, so that substep is not the reference's - reported like bit 4.
+ * bit 6 (value 64): a blob given to dynenv_set_states did not fit the handle's layout and was NOT written; sticky on that environment until
+ * the next reset or the next valid set_state / set_states of it; the host mirror's step() raises on it.
  * Synchronises the device. */
 int dynenv_error_flags(dynenv_t* h, int32_t* out);
+/* The per-environment error words themselves (the bits above): flags_dev int32 [E], ordered on `stream`, no synchronisation - to
+ * name the environment a sticky bit belongs to and repair only that one. */
+int dynenv_error_flags_env(dynenv_t* h, int32_t* flags_dev, void* stream);
 
 /* Diagnostics (Driving), summed over environments since the last reset: out16 = {substeps on the no-contact fast path,
  * on the quiescent shortcut, on the full contact path, sum of live contact-cache slots, contact-path substeps caused by
