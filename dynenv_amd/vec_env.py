@@ -335,6 +335,7 @@ class BatchedDynEnv(object):
         position follows the blob's `elapsed` - like restore() - so a blob with an edited `elapsed` moves host and device together.
         (Blobs that put different environments at different times make `dones` meaningless; the device keeps stepping them.)"""
         _capi.check(self._lib.dynenv_set_state(self._h, env, C.byref(st), C.sizeof(st)), "dynenv_set_state")
+        self._counts_np = None  # the scene (obstacle / pedestrian counts) may have changed
         step = int(st.elapsed) // self._substeps()
         if not self._needs_reset and step != self._episode_step and self.num_envs > 1 and not getattr(self, "_set_state_moved", False):
             # ONE blob with another `elapsed` than the batch's moves the host's episode position - and with it `dones` and the auto-reset of
@@ -559,6 +560,11 @@ class BatchedDynEnv(object):
         rewards = self.rewards.cpu().numpy().copy()
         robocup, partial = self.env_type == DynEnvType.ROBO_CUP, self.observationType == ObservationType.PARTIAL
         flags = self.error_flags()  # ONE read per step: it is a device synchronisation and a copy of the flags
+        if flags & 1:
+            # the reference's arbiter set has no cap; the contact tables have (DRV_NS / RC_NS slots, 128 candidate pairs a substep), and a
+            # pair beyond them was dropped: not the reference's state any more - never silently (include/dynenv.h, error bit 0)
+            raise _capi.DynEnvError("contact cache or candidate list overflow: a colliding pair was dropped (error bit 0): the state is not the "
+                                    "reference's any more; reset() or set_state() clears it; first in environment %d" % self._first_env_with(1))
         if partial and flags & 8:
             # the reference's observation lists have no cap (DrivingEnvironment.py:816-890); the dense layout has, and rows beyond it were
             # dropped: not the reference's observation any more - never silently (include/dynenv.h, error bit 3)

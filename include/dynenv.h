@@ -224,7 +224,10 @@ int dynenv_set_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const 
 
 int dynenv_sync(dynenv_t* h, void* stream);
 
-/* OR over all environments of the kernels' error flags (bit 0: contact cache overflow, a pair was dropped; bit 1: an action
+/* OR over all environments of the kernels' error flags (bit 0: contact cache or candidate list overflow - an environment had
+ * more arbiters at once than its slot table holds (24 Driving, 16 RoboCup) or more than 128 candidate pairs in a substep - and a pair was
+ * DROPPED: the reference has no such cap, so from that substep on the environment is not the reference's; sticky until the next reset /
+ * set_state of it; the host mirror's step() raises on it; bit 1: an action
  * outside the action space was seen - the reference raises there, DrivingEnvironment.py:365-368 / RoboCupEnvironment.py:543-550;
  * here that agent's action is ignored for the step and the flag stays up until the next reset; bit 3: a Partial observation
  * list had more rows than its capacity in the layout and the rows beyond it were DROPPED - the reference's lists have no cap

@@ -818,14 +818,16 @@ void cpSpaceStep(cpSpace* s, double dt) {
   }
   /* cpSpaceArbiterSetFilter in canonical pair order: separate callbacks + expiry */
   {
-    int order[CP_MAX_ARBITERS], n = 0, k;
+    int order[CP_MAX_ARBITERS], n = 0, k, tracked = 0;
     for (i = 0; i < CP_MAX_ARBITERS; ++i)
       if (s->pool[i].used) {
         int key = pair_key(&s->pool[i]);
         k = n++;
         while (k > 0 && pair_key(&s->pool[order[k - 1]]) > key) { order[k] = order[k - 1]; --k; }
         order[k] = i;
+        if (!s->pool[i].handler->untracked) ++tracked;
       }
+    if (tracked > s->peak_arbiters) s->peak_arbiters = tracked; /* the pool at its fullest: this step's new arbiters are in, none has expired yet */
     for (k = 0; k < n; ++k) {
       cpArbiter* arb = &s->pool[order[cp_lite_test_reverse_order ? n - 1 - k : k]];
       int ticks = s->stamp - arb->stamp;

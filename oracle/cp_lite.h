@@ -85,6 +85,8 @@ typedef struct cpHandler {
   cpArbFunc post_solve;
   cpArbFunc separate;
   void* data;
+  int untracked; /* tests only: arbiters of this handler are left out of cpSpace.peak_arbiters - pairs whose `begin` rejects unconditionally
+                    and has no effect, which the kernels never enumerate (Driving: pedestrian-pedestrian, pedestrian-static) */
 } cpHandler;
 
 typedef struct cpArbiter {
@@ -134,6 +136,9 @@ typedef struct cpSpace {
   cpHandler handlers[CP_MAX_HANDLERS];
   cpHandler default_handler;
   int overflow; /* set if a fixed capacity was exceeded */
+  int peak_arbiters; /* tests only, not simulation state: the most `used` pool entries (of tracked handlers) a step has seen, sampled after the collision phase and
+                        before the expiry filter releases any - where the pool is fullest, and where the kernels' slot tables (DRV_NS, RC_NS)
+                        have handed out this substep's slots and freed none yet.  cpSpaceInit (reset, set_state) clears it */
   int degenerate; /* set (until the space is rebuilt) when two capsule CORES were exactly collinear / exactly touching: the sign of the
                      minimum-translation normal segment_to_segment takes for crossing cores is a convention there (cores_crossing_normal in
                      cp_lite.c); error bit 4 of dynenv_error_flags */

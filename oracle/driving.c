@@ -366,8 +366,9 @@ static void build_space(DrivingEnv* e) {
   int i;
   cpSpaceInit(&e->space); /* environment_base.py:126-128 */
   /* DrivingEnvironment.py:65-74 */
-  h = cpSpaceAddHandler(&e->space, CT_Pedestrian, CT_Pedestrian); h->begin = ignore_collision; h->data = e;
-  h = cpSpaceAddHandler(&e->space, CT_Pedestrian, CT_Obstacle); h->begin = ignore_collision; h->data = e;
+  /* (the kernels enumerate car pairs only: these two handlers' arbiters hold no slot there and stay out of peak_arbiters) */
+  h = cpSpaceAddHandler(&e->space, CT_Pedestrian, CT_Pedestrian); h->begin = ignore_collision; h->data = e; h->untracked = 1;
+  h = cpSpaceAddHandler(&e->space, CT_Pedestrian, CT_Obstacle); h->begin = ignore_collision; h->data = e; h->untracked = 1;
   h = cpSpaceAddHandler(&e->space, CT_Car, CT_Car); h->begin = car_crash_cb; h->data = e;
   h = cpSpaceAddHandler(&e->space, CT_Car, CT_Pedestrian); h->begin = ped_hit_cb; h->data = e;
   h = cpSpaceAddHandler(&e->space, CT_Car, CT_Obstacle); h->begin = car_hit_cb; h->data = e;

@@ -228,6 +228,9 @@ void oracle_drv_vision(oracle_t* o, int env, int agent, float* out) {
   DrivingEnv* d = &o->drv[env];
   d->obsOverflow |= drv_agent_vision(d, agent, d->noiseType, d->noiseMagnitude, out) & 0xFF;
 }
+/* the most arbiters the environment's pool has held at once since its last reset / set_state (cpSpace.peak_arbiters): what the kernels'
+ * slot tables are bound by */
+int oracle_peak_arbiters(oracle_t* o, int32_t env) { return o->drv ? o->drv[env].space.peak_arbiters : o->rc[env].space.peak_arbiters; }
 int oracle_active_contacts(oracle_t* o, int32_t env) { return o->drv ? o->drv[env].space.n_active : o->rc[env].space.n_active; }
 
 /* ---- unit entry points for the golden tests (tests/test_oracle_golden.py) ---- */

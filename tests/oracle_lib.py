@@ -194,6 +194,11 @@ class OracleEnv:
     def degenerate_env(self, env):
         return self.l.oracle_degenerate_env(self.h, env)
 
+    def peak_arbiters(self, env=0):
+        """the most arbiters the environment's pool held at once (after a substep's collision phase, before its expiry) since the last
+        reset / set_state: the load the kernels' slot tables (DRV_NS = 24, RC_NS = 16) must hold"""
+        return self.l.oracle_peak_arbiters(self.h, env)
+
     def active_contacts(self, env=0):
         return self.l.oracle_active_contacts(self.h, env)
 
