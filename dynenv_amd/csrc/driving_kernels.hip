@@ -684,7 +684,8 @@ DE_DEV bool cb_begin(DrvLds& L, int i, int j, int lane) {
 
 // ------------------------------------------------------------------------------------------------
 // The contact path of one substep (drv_contact_path below): narrowphase -> contact cache -> callbacks -> prestep, velocity
-// update and solve (drv_prestep_solve, out of line; the sweeps of a general multi-level solve in drv_solve_general_split).
+// update and solve (drv_prestep_solve / drv_prestep_solve_multi, out of line; the sweeps of a general multi-level solve in
+// drv_solve_general_split and its verdicts in drv_split_verdicts, both called by the kernel).
 // Operates on the LDS tile; returns the few scalars it changes.  First the solver's building blocks.
 // ------------------------------------------------------------------------------------------------
 // cpArbiterApplyCachedImpulse for the (up to two) contacts of one arbiter
@@ -797,8 +798,8 @@ DE_DEV int body_wr(int idx) { return idx < DRV_SLOT_OBST ? idx : DRV_SINK_SLOT; 
 // 95 fp64 instructions per contact and pass.  Same operations on the same operands in the same order as arb_apply_impulse,
 // chain by chain (the two only meet in memory, in different fields): bit-identical.  The mirror lanes fetch their arbiter's
 // scalars from the slot lane (ds_bpermute) and rebuild r1, r2, n from the mailbox exactly as the prestep did.
-// (Inside drv_prestep_solve this form needs more registers than the function has: 16 spills on every call, measured.  Here only
-// the solves that take this path pay for what their caller keeps across the call.)
+// (Inside the solve function this form needs more registers than the function has: 16 spills on every call, measured.  The kernel
+// calls it with what drv_prestep_solve_multi hands back; lane, levels and the packed slot state arrive as arguments.)
 // ------------------------------------------------------------------------------------------------
 struct DrvSplitRet { double jn0, jn1, jb0, jb1, jt0, jt1; int pk, pair, bits; };
 DE_OOL DrvSplitRet drv_solve_general_split(int lane, int myLevel_, int bodyAB, int lvl_, double nMass0, double nMass1, double bias0, double bias1,
@@ -886,20 +887,79 @@ DRV_PROF(DE_DEV int prof_any(int v) { const uint64_t m = wave_ballot(v != 0); re
 // Which half of a substep is out of line: the COMMON part (game logic, position update, broadphase: drv_light_substep, a leaf
 // with nothing to save) is a function; the contact path is inlined into the kernel, which as the outermost frame never saves a
 // register (round 1 had it the other way round and paid the save / restore of 47 callee-saved VGPRs per call: 3/4 of that
-// kernel's HBM traffic).  Its solver is a function again (drv_prestep_solve), entered with nothing of the contact cache live.
+// kernel's HBM traffic).  Its solver is a set of functions again (drv_prestep_solve ...), all leaves, entered with nothing of the
+// contact cache live.
 #ifndef DRV_CONTACT_INLINE
 #define DRV_CONTACT_INLINE __forceinline__
 #endif
 
 // pk: a_state | a_count << 8 | a_age << 16 | touched << 24 | freeMe << 25 | hashSame << 26 | prevInert << 27 | skipped << 28 | slotOcc << 29 | active << 30
-DE_OOL int drv_prestep_solve(int lane, int nCarPed, int pk, int a_pair, int bodyA, int bodyB, int myLevel,
-                                             int maxLevel_, int anyActive_, double jn0, double jn1, double jt0, double jt1) {
+// The end of a solve, once for both of its callers (drv_prestep_solve: every solve whose sweeps ran inside it; drv_split_verdicts:
+// after drv_solve_general_split): the steady / inert verdicts of the slots and the slot record.  restIn: both bodies exactly at rest
+// when the arbiter was prestepped; biasZ0 / biasZ1: bias[c] == 0.0.  Returns allInert << 1 | allSteady << 2 | tookSplit << 3.
+DE_DEV int drv_slot_verdicts(int lane, int pk, int a_pair, bool restIn, bool biasZ0, bool biasZ1, double jn0, double jn1, double jt0, double jt1,
+                             double jBias0, double jBias1, bool tookSplit) {
+  DrvLds& L = g_L;
+  int a_state = pk & 0xFF;
+  const int a_count = (pk >> 8) & 0xFF, a_age = (pk >> 16) & 0xFF;
+  const bool touched = (pk >> 24) & 1, freeMe = (pk >> 25) & 1, hashSame = (pk >> 26) & 1, prevInert = (pk >> 27) & 1;
+  const bool skipped = (pk >> 28) & 1, slotOcc = (pk >> 29) & 1, active = (pk >> 30) & 1;
+  // arbiters that were active this step are NORMAL from the next step on (cpSpaceStep resets the state)
+  const bool wasNormal = a_state == ARB_NORMAL;  // i.e. not a first contact in this substep
+  if (active && a_state == ARB_FIRST) a_state = ARB_NORMAL;
+  // steady: re-running this slot on identical inputs (same frozen positions, bodies at rest) reproduces this substep
+  // bit for bit: the slot record is unchanged (same contact ids, same accumulated impulses, NORMAL before and after, or
+  // ignored) and both bodies were at rest before the prestep and after the solve.  See DESIGN.md "steady replay".
+  bool steady = true;
+  if (slotOcc && !skipped) {
+    steady = touched && !freeMe && hashSame;
+    if (steady && a_state != ARB_IGNORE) {
+      steady = a_state == ARB_NORMAL && wasNormal && restIn && L.s_jn0[lane] == jn0 && L.s_jt0[lane] == jt0 &&
+               L.s_jn1[lane] == jn1 && L.s_jt1[lane] == jt1;
+      if (steady) {
+        const int i = a_pair >> 8, j = a_pair & 0xFF;
+        steady = L.vx[i] == 0.0 && L.vy[i] == 0.0 && L.w[i] == 0.0;
+        if (j < DRV_SLOT_OBST) steady = steady && L.vx[j] == 0.0 && L.vy[j] == 0.0 && L.w[j] == 0.0;
+      }
+    }
+  }
+  const bool allSteady = wave_ballot(!steady) == 0ull;
+  // inert: touched, not first contact, and (ignored | zero bias and zero accumulated impulses on every contact)
+  bool inert = true;
+  if (slotOcc && skipped) inert = prevInert;
+  else if (slotOcc) {
+    inert = touched && !freeMe &&
+            (a_state == ARB_IGNORE ||
+             (a_state == ARB_NORMAL && wasNormal && biasZ0 && biasZ1 && jn0 == 0.0 && jt0 == 0.0 &&
+              jn1 == 0.0 && jt1 == 0.0 && jBias0 == 0.0 && jBias1 == 0.0));
+  }
+  if (slotOcc) {
+    if (freeMe) L.s_pair[lane] = 0xFFFF;
+    L.s_meta[lane] = a_state | (a_count << 8) | (a_age << 16) | (steady ? (1 << 24) : 0) | (inert ? (1 << 25) : 0);
+    if (touched) { L.s_jn0[lane] = jn0; L.s_jt0[lane] = jt0; L.s_jn1[lane] = jn1; L.s_jt1[lane] = jt1; }
+  }
+  const bool allInert = wave_ballot(!inert) == 0ull;
+  return (allInert ? 2 : 0) | (allSteady ? 4 : 0) | (tookSplit ? 8 : 0);
+}
+// What drv_prestep_solve_multi hands back, in registers (a vector: an aggregate of more than 16 words would come back through
+// scratch).  Every solve: the low word of [11] = needsSplit | allInert << 1 | allSteady << 2.  needsSplit (a general multi-level solve: prestep,
+// velocity update and warm start are done, the sweeps and the verdicts are not) also fills in the arguments of
+// drv_solve_general_split, which the KERNEL calls - the outermost frame never saves a return address, and the solve function stays a leaf:
+// [0..9] = nMass, bias, bounce, jn, jt of the two contacts, [10] = pk | pair << 32,
+// [11] = bits | (restIn | bias0 == 0 << 1 | bias1 == 0 << 2) << 8 | myLevel << 16 | (bodyA | bodyB << 8 | level word << 16) << 32.
+typedef double DrvSolveRet __attribute__((ext_vector_type(12)));
+DE_DEV double drv_pack2(int lo, int hi) { return __hiloint2double(hi, lo); }
+// MULTI: some active arbiters share a dynamic body (maxLevel > 0).  The two kinds of solve are two out-of-line functions
+// (drv_prestep_solve, drv_prestep_solve_multi), each with a register allocation of its own: together, and without a call in
+// between that splits every live range, they need more than 128 VGPRs (8 - 17 spills around the single-level loops, seen in the ISA).
+template <bool MULTI>
+DE_DEV DrvSolveRet drv_prestep_solve_body(int lane, int nCarPed, int pk, int a_pair, int bodyA, int bodyB, int myLevel,
+                                          int maxLevel_, int anyActive_, double jn0, double jn1, double jt0, double jt1) {
   DrvLds& L = g_L;
   DrvMailbox& M = L.u.mb;
-  int a_state = pk & 0xFF;
-  int a_count = (pk >> 8) & 0xFF, a_age = (pk >> 16) & 0xFF;
-  bool touched = (pk >> 24) & 1, freeMe = (pk >> 25) & 1, hashSame = (pk >> 26) & 1, prevInert = (pk >> 27) & 1;
-  bool skipped = (pk >> 28) & 1, slotOcc = (pk >> 29) & 1, active = (pk >> 30) & 1;
+  const int a_state = pk & 0xFF;
+  const int a_count = (pk >> 8) & 0xFF;
+  const bool active = (pk >> 30) & 1;
   const bool isCar = lane < (uniform_i(nCarPed) & 0xFF), isPed = lane >= DRV_SLOT_PED && lane < DRV_SLOT_PED + (uniform_i(nCarPed) >> 8);
   const int maxLevel = (int)(signed char)(uniform_i(maxLevel_) & 0xFF), period = uniform_i(maxLevel_) >> 8;
   const uint64_t activeMask = uniform_i(anyActive_) ? 1ull : 0ull;
@@ -941,8 +1001,7 @@ DRV_PROF(const unsigned long long P1 = __builtin_amdgcn_s_memtime();)
   // ---- velocity update (velocity_func: friction_* or default) -------------------------------------------
   velocity_update(L, lane, isCar, isPed);
 DRV_PROF(int profMode = 0; const unsigned long long P2 = __builtin_amdgcn_s_memtime();)
-  bool tookSplit = false;  // (wave-uniform) the sweeps ran in drv_solve_general_split: counted in EI_N_SPLIT
-  if (activeMask && maxLevel == 0) {
+  if (!MULTI && activeMask) {
     // No two active arbiters share a dynamic body: each lane keeps its two bodies in registers through the warm start
     // and all 10 iterations, with one LDS load and one store (same arithmetic, no LDS round trip per iteration).
     __syncthreads();
@@ -967,7 +1026,7 @@ DRV_PROF(profMode = 2;)
       body_store_vel(L, bodyB, b);
     }
     __syncthreads();
-  } else if (activeMask) {
+  } else if (MULTI) {
     __syncthreads();
     // ---- warm start (cpArbiterApplyCachedImpulse; skipped on first contact), level by level ------------
     for (int lv = 0; lv <= maxLevel; ++lv) {
@@ -1013,62 +1072,40 @@ DRV_PROF(profMode = wave_ballot(!biasOnly) == 0ull ? 3 : 4;)
         __syncthreads();
       }
     } else [[unlikely]] {
-      // the general sweeps are a function of their own (drv_solve_general_split).  NOTHING of this frame lives across the call:
-      // what the verdicts below need - the packed slot state, the pair, the tangent impulses, three predicates - travels through
-      // the callee's registers and comes back in its return value (a value kept across the call would be spilled, and the
-      // allocator then spills it across the whole function, the bias-only loops that every pile-up runs included: measured)
+      // the general sweeps are a function of their own (drv_solve_general_split), and the kernel calls it: this function returns here
+      // with what the sweeps and the verdicts need (a function that calls saves its return address through a VGPR that it stores to
+      // and reloads from scratch right in front of EVERY return, and keeps 16 values in scratch across the call)
+DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + blockIdx.x * 8; const unsigned long long P3 = __builtin_amdgcn_s_memtime(); d[2] += P1 - P0; d[3] += (P2 - P1) + ((P3 - P2) << 32); })
       const int bits3 = (restIn ? 1 : 0) | (bias[0] == 0.0 ? 2 : 0) | (bias[1] == 0.0 ? 4 : 0);
-      const DrvSplitRet sr = drv_solve_general_split(lane, myLevel, bodyA | (bodyB << 8), maxLevel_, nMass[0], nMass[1], bias[0], bias[1], bounce[0],
-                                                     bounce[1], jn[0], jn[1], jt[0], jt[1], pk, a_pair, bits3);
-      lane = fresh_lane();
-      pk = sr.pk; a_pair = sr.pair;
-      a_state = pk & 0xFF; a_count = (pk >> 8) & 0xFF; a_age = (pk >> 16) & 0xFF;
-      touched = (pk >> 24) & 1; freeMe = (pk >> 25) & 1; hashSame = (pk >> 26) & 1; prevInert = (pk >> 27) & 1;
-      skipped = (pk >> 28) & 1; slotOcc = (pk >> 29) & 1; active = (pk >> 30) & 1;
-      restIn = (sr.bits & 1) != 0;
-      bias[0] = (sr.bits & 2) ? 0.0 : 1.0; bias[1] = (sr.bits & 4) ? 0.0 : 1.0;  // (only compared with zero from here on)
-      jn[0] = sr.jn0; jn[1] = sr.jn1; jBias[0] = sr.jb0; jBias[1] = sr.jb1; jt[0] = sr.jt0; jt[1] = sr.jt1;
-      tookSplit = true;
+      DrvSolveRet r;
+      r[0] = nMass[0]; r[1] = nMass[1]; r[2] = bias[0]; r[3] = bias[1]; r[4] = bounce[0]; r[5] = bounce[1];
+      r[6] = jn[0]; r[7] = jn[1]; r[8] = jt[0]; r[9] = jt[1];
+      r[10] = drv_pack2(pk, a_pair);
+      r[11] = drv_pack2(1 | (bits3 << 8) | (myLevel << 16), bodyA | (bodyB << 8) | (maxLevel_ << 16));
+      return r;
     }
   }
 DRV_PROF(const unsigned long long P3 = __builtin_amdgcn_s_memtime();)
-  // arbiters that were active this step are NORMAL from the next step on (cpSpaceStep resets the state)
-  const bool wasNormal = a_state == ARB_NORMAL;  // i.e. not a first contact in this substep
-  if (active && a_state == ARB_FIRST) a_state = ARB_NORMAL;
-  // steady: re-running this slot on identical inputs (same frozen positions, bodies at rest) reproduces this substep
-  // bit for bit: the slot record is unchanged (same contact ids, same accumulated impulses, NORMAL before and after, or
-  // ignored) and both bodies were at rest before the prestep and after the solve.  See DESIGN.md "steady replay".
-  bool steady = true;
-  if (slotOcc && !skipped) {
-    steady = touched && !freeMe && hashSame;
-    if (steady && a_state != ARB_IGNORE) {
-      steady = a_state == ARB_NORMAL && wasNormal && restIn && L.s_jn0[lane] == jn[0] && L.s_jt0[lane] == jt[0] &&
-               L.s_jn1[lane] == jn[1] && L.s_jt1[lane] == jt[1];
-      if (steady) {
-        const int i = a_pair >> 8, j = a_pair & 0xFF;
-        steady = L.vx[i] == 0.0 && L.vy[i] == 0.0 && L.w[i] == 0.0;
-        if (j < DRV_SLOT_OBST) steady = steady && L.vx[j] == 0.0 && L.vy[j] == 0.0 && L.w[j] == 0.0;
-      }
-    }
-  }
-  const bool allSteady = wave_ballot(!steady) == 0ull;
-  // inert: touched, not first contact, and (ignored | zero bias and zero accumulated impulses on every contact)
-  bool inert = true;
-  if (slotOcc && skipped) inert = prevInert;
-  else if (slotOcc) {
-    inert = touched && !freeMe &&
-            (a_state == ARB_IGNORE ||
-             (a_state == ARB_NORMAL && wasNormal && bias[0] == 0.0 && bias[1] == 0.0 && jn[0] == 0.0 && jt[0] == 0.0 &&
-              jn[1] == 0.0 && jt[1] == 0.0 && jBias[0] == 0.0 && jBias[1] == 0.0));
-  }
-  if (slotOcc) {
-    if (freeMe) L.s_pair[lane] = 0xFFFF;
-    L.s_meta[lane] = a_state | (a_count << 8) | (a_age << 16) | (steady ? (1 << 24) : 0) | (inert ? (1 << 25) : 0);
-    if (touched) { L.s_jn0[lane] = jn[0]; L.s_jt0[lane] = jt[0]; L.s_jn1[lane] = jn[1]; L.s_jt1[lane] = jt[1]; }
-  }
-  const bool allInert = wave_ballot(!inert) == 0ull;
+  const int bits = drv_slot_verdicts(lane, pk, a_pair, restIn, bias[0] == 0.0, bias[1] == 0.0, jn[0], jn[1], jt[0], jt[1], jBias[0], jBias[1], false);
 DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + blockIdx.x * 8; const unsigned long long P4 = __builtin_amdgcn_s_memtime(); d[2] += (P1 - P0) + ((P4 - P3) << 32); d[3] += (P2 - P1) + ((P3 - P2) << 32); })
-  return (allInert ? 2 : 0) | (allSteady ? 4 : 0) | (tookSplit ? 8 : 0) DRV_PROF(| (prof_any(profMode) << 4));
+  DrvSolveRet r;  // (only the low word of [11] means anything)
+  r[11] = drv_pack2(bits DRV_PROF(| (prof_any(profMode) << 4)), 0);
+  return r;
+}
+// nothing active, or no two active arbiters share a dynamic body (maxLevel = 0): returns allInert << 1 | allSteady << 2
+DE_OOL int drv_prestep_solve(int lane, int nCarPed, int pk, int a_pair, int bodyA, int bodyB, int anyActive_, double jn0, double jn1, double jt0,
+                             double jt1) {
+  return __double2loint(drv_prestep_solve_body<false>(lane, nCarPed, pk, a_pair, bodyA, bodyB, 0, 1 << 8 /* maxLevel 0, period 1 */, anyActive_, jn0, jn1, jt0, jt1)[11]);
+}
+// active arbiters that share dynamic bodies (maxLevel > 0)
+DE_OOL DrvSolveRet drv_prestep_solve_multi(int lane, int nCarPed, int pk, int a_pair, int bodyA, int bodyB, int myLevel, int maxLevel_, double jn0,
+                                           double jn1, double jt0, double jt1) {
+  return drv_prestep_solve_body<true>(lane, nCarPed, pk, a_pair, bodyA, bodyB, myLevel, maxLevel_, 1, jn0, jn1, jt0, jt1);
+}
+// The verdicts and the slot record after drv_solve_general_split: a leaf like the sweeps before it, called by the kernel with the
+// values those hand back.
+DE_OOL int drv_split_verdicts(int lane, int pk, int a_pair, int bits3, double jn0, double jn1, double jBias0, double jBias1, double jt0, double jt1) {
+  return drv_slot_verdicts(lane, pk, a_pair, (bits3 & 1) != 0, (bits3 & 2) != 0, (bits3 & 4) != 0, jn0, jn1, jt0, jt1, jBias0, jBias1, true);
 }
 struct ContactRet {
   uint64_t occ;
@@ -1398,10 +1435,27 @@ DRV_PROF(const unsigned long long T2 = __builtin_amdgcn_s_memtime();)
 DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgs + blockIdx.x * 8; d[0] += U1 - T1; d[1] += U2 - U1; d[2] += U3 - U2; d[3] += U4 - U3; d[4] += T2 - U4; })
   // everything per-slot from here on - prestep, solve, the steady / inert verdicts and the slot record - happens inside the
   // function: nothing of the contact cache stays live in this frame across the call
-  const int solveBits = drv_prestep_solve(lane, nCarPed,
-                                          (a_state & 0xFF) | ((a_count & 0xFF) << 8) | ((a_age & 0xFF) << 16) | (touched ? 1 << 24 : 0) | (freeMe ? 1 << 25 : 0) |
-                                              (hashSame ? 1 << 26 : 0) | (prevInert ? 1 << 27 : 0) | (skipped ? 1 << 28 : 0) | (slotOcc ? 1 << 29 : 0) | (active ? 1 << 30 : 0),
-                                          a_pair, bodyA, bodyB, myLevel, (maxLevel & 0xFF) | (period << 8), activeMask != 0ull ? 1 : 0, jn[0], jn[1], jt[0], jt[1]);
+  const int pkArg = (a_state & 0xFF) | ((a_count & 0xFF) << 8) | ((a_age & 0xFF) << 16) | (touched ? 1 << 24 : 0) | (freeMe ? 1 << 25 : 0) |
+                    (hashSame ? 1 << 26 : 0) | (prevInert ? 1 << 27 : 0) | (skipped ? 1 << 28 : 0) | (slotOcc ? 1 << 29 : 0) | (active ? 1 << 30 : 0);
+  int solveBits;
+  if (activeMask == 0ull || maxLevel == 0) {
+    solveBits = drv_prestep_solve(lane, nCarPed, pkArg, a_pair, bodyA, bodyB, activeMask != 0ull ? 1 : 0, jn[0], jn[1], jt[0], jt[1]);
+  } else {
+    const DrvSolveRet sv = drv_prestep_solve_multi(lane, nCarPed, pkArg, a_pair, bodyA, bodyB, myLevel, (maxLevel & 0xFF) | (period << 8), jn[0], jn[1], jt[0], jt[1]);
+    solveBits = __double2loint(sv[11]);
+    if (uniform_i(solveBits) & 1) [[unlikely]] {
+      // A general multi-level solve: the sweeps and then the verdicts, both leaves, called from here.  NOTHING of this frame lives across
+      // the three calls: what one callee hands back goes straight into the next one's argument registers (the packed slot state, the
+      // pair, the tangent impulses and three predicates travel through the sweeps and come back in their return value).
+      const int w1 = __double2hiint(sv[11]);
+DRV_PROF(const unsigned long long S0 = __builtin_amdgcn_s_memtime();)
+      const DrvSplitRet sr = drv_solve_general_split(fresh_lane(), (solveBits >> 16) & 0xFF, w1 & 0xFFFF, w1 >> 16, sv[0], sv[1], sv[2], sv[3], sv[4], sv[5],
+                                                     sv[6], sv[7], sv[8], sv[9], __double2loint(sv[10]), __double2hiint(sv[10]), (solveBits >> 8) & 7);
+DRV_PROF(const unsigned long long S1 = __builtin_amdgcn_s_memtime();)
+      solveBits = drv_split_verdicts(fresh_lane(), sr.pk, sr.pair, sr.bits, sr.jn0, sr.jn1, sr.jb0, sr.jb1, sr.jt0, sr.jt1) DRV_PROF(| (4 << 4));
+DRV_PROF(if (fresh_lane() == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + blockIdx.x * 8; d[3] += (S1 - S0) << 32; d[2] += (__builtin_amdgcn_s_memtime() - S1) << 32; })
+    }
+  }
   occ &= ~freeMask;
 DRV_PROF(const unsigned long long T3 = T2, T4 = T2, T5 = __builtin_amdgcn_s_memtime(); const int profModeW = (uniform_i(solveBits) >> 4) & 7;)
 DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + blockIdx.x * 8; d[0] += T1 - T0; d[1] += T2 - T1; d[2] += T3 - T2; d[3] += T4 - T3; d[4] += T5 - T4; d[5] += 1ull + (light ? (1ull << 16) : 0ull); d[6] += (unsigned long long)(maxLevel + 1) + ((unsigned long long)(maxLevel + 1) << (12 * profModeW)); d[7] += (unsigned long long)nTouched + ((unsigned long long)profCand << 16); })
@@ -1850,7 +1904,15 @@ DRV_PROF(if (lane < 8 && e < 4096) { g_dbgp[e * 8 + lane] = 0ull; g_dbgs[e * 8 +
   // steady-replay state: the contact path ran (or was replayed) in the previous substep and reported every slot steady
   bool steadyAll = (uniform_i(envi[EI_PAD]) & 2) != 0;
   bool vbValid = (uniform_i(envi[EI_PAD]) & 4) != 0;
-  int nFast = 0, nQuiet = 0, nContact = 0, nSlots = 0, nWhyCand = 0, nWhyMoving = 0, nWhyInert = 0, nSteady = 0, nLight = 0, nSplit = 0;  // diagnostics
+  // The step's ten diagnostic counters (EI_N_FAST .. EI_N_SPLIT), packed into two wave-uniform words: they live in scalar registers
+  // across the calls of the substep loop (ten words, two of them counted after the contact path, took vector registers that were
+  // stored to scratch before every call of the solver and reloaded after it).  cntA: four bits per counter in the order of the
+  // EI_N_* words (each counts at most the step's 10 substeps; the field of EI_N_SLOTS stays empty), cntB: the sum of live slots
+  // (at most 10 x DRV_NS = 240) | nLight << 8 | nSplit << 12.
+  unsigned cntA = 0u, cntB = 0u;
+#define DRV_CNT(ei) (1u << (4 * ((ei) - EI_N_FAST)))
+#define DRV_CNT_GET(ei) ((int)((cntA >> (4 * ((ei) - EI_N_FAST))) & 15u))
+  static_assert(EI_N_STEADY - EI_N_FAST == 7 && EI_N_SLOTS - EI_N_FAST == 3 && DRV_NS * 10 < 256, "seven counters of four bits in cntA, the slot sum in eight bits of cntB");
   __syncthreads();
 
 DRV_PROF(const unsigned long long K0 = __builtin_amdgcn_s_memtime(); unsigned long long tPh1 = 0, tBroad = 0, tFast = 0, tCont = 0, tBook = 0;)
@@ -1885,11 +1947,11 @@ DRV_PROF(const unsigned long long A1 = A0;)
     // (a light-mode attempt that fails is paid on top of the full path, and what made it fail - a moving car leaning on a
     // resting pile - persists: after a failure the rest of the step goes straight to the full path.  Both give the same result.)
     const bool light = steadyOk && anyDirty && !lightOff;
-    if (!(anyCand == 0ull && occ == 0ull) && !quiescent && !replay) { if (candChanged) nWhyCand++; else if (anyMoving) nWhyMoving++; else nWhyInert++; }
+    if (!(anyCand == 0ull && occ == 0ull) && !quiescent && !replay) cntA += candChanged ? DRV_CNT(EI_N_WHY_CAND) : anyMoving ? DRV_CNT(EI_N_WHY_MOVING) : DRV_CNT(EI_N_WHY_INERT);
 
 DRV_PROF(const unsigned long long A2 = __builtin_amdgcn_s_memtime(); bool tookContact = false;)
-    if (anyCand == 0ull && occ == 0ull) nFast++; else if (quiescent) nQuiet++; else if (replay) nSteady++; else nContact++;
-    nSlots += __popcll(occ);
+    cntA += (anyCand == 0ull && occ == 0ull) ? DRV_CNT(EI_N_FAST) : quiescent ? DRV_CNT(EI_N_QUIET) : replay ? DRV_CNT(EI_N_STEADY) : DRV_CNT(EI_N_CONTACT);
+    cntB += (unsigned)__popcll(occ);
     if ((anyCand == 0ull && occ == 0ull) || quiescent) {
       // ---------- fast path: nothing touches and the contact cache is empty (or quiescent): velocity update only
       velocity_update_ool(A | (nPed << 8));
@@ -1904,9 +1966,9 @@ DRV_PROF(tookContact = true;)
       if (wave_ballot((cr.err & 1) != 0) != 0ull && lane == 0) L.stepErr |= 1;
       if (light && !(uniform_i(cr.err >> 3) & 1)) lightOff = true;
       if (uniform_i(cr.err >> 3) & 1) {  // light mode: no dirty pair touches => replay
-        replay = true; nLight++;
+        replay = true; cntB = (unsigned)uniform_i((int)(cntB + (1u << 8)));
       } else {
-        nSplit += uniform_i(cr.err >> 4) & 1;
+        cntB = (unsigned)uniform_i((int)(cntB + ((unsigned)(uniform_i(cr.err >> 4) & 1) << 12)));
         occ = uniform_u64(cr.occ);
         inertAll = (uniform_i(cr.err >> 1) & 1) != 0;
         steadyAll = (uniform_i(cr.err >> 2) & 1) != 0;
@@ -1918,6 +1980,8 @@ DRV_PROF(tookContact = true;)
       vbValid = true;
     }
     __syncthreads();
+    if (!PARTIAL) lane = fresh_lane();  // (on every path: the copy of the loop's top is not kept across the calls above; seen in the ISA -
+                                        //  the Partial kernel then stores the register that carries its scalar values instead)
 
 DRV_PROF(const unsigned long long A3 = __builtin_amdgcn_s_memtime(); tPh1 += A1 - A0; tBroad += A2 - A1; if (tookContact) tCont += A3 - A2; else tFast += A3 - A2;)
     // ======== bookkeeping :280-287 =========================================================================
@@ -1964,15 +2028,14 @@ DRV_PROF(const unsigned long long K1 = __builtin_amdgcn_s_memtime();)
     static_assert(EI_N_QUIET == EI_N_FAST + 1 && EI_N_CONTACT == EI_N_FAST + 2 && EI_N_SLOTS == EI_N_FAST + 3 && EI_N_WHY_CAND == EI_N_FAST + 4 &&
                   EI_N_WHY_MOVING == EI_N_FAST + 5 && EI_N_WHY_INERT == EI_N_FAST + 6 && EI_N_STEADY == EI_N_FAST + 7 && EI_N_LIGHT == EI_N_FAST + 8 && EI_N_SPLIT == EI_N_FAST + 9,
                   "the diagnostic counters are consecutive");
-    const int add = lane == 0 ? nFast : lane == 1 ? nQuiet : lane == 2 ? nContact : lane == 3 ? nSlots : lane == 4 ? nWhyCand : lane == 5 ? nWhyMoving :
-                    lane == 6 ? nWhyInert : lane == 7 ? nSteady : lane == 8 ? nLight : nSplit;
+    const int add = (int)(cl == 3 ? (cntB & 0xFFu) : cl < 8 ? (cntA >> (4 * cl)) & 15u : (cntB >> (4 * cl - 24)) & 15u);  // (lanes 8, 9: nLight, nSplit)
     if (lane < 10) envi[EI_N_FAST + lane] = g_cnt + add;
   }
   if (errBits && lane == 0) envi[EI_ERR] = g_err | errBits;
   // Partial observation of this environment, fused (see drv_partial_obs_fused): the first `fusedAgents` agent passes run
   // here, the rest is left to the deferred launch.  Without a forecast (DYNENV_NO_ISOLATION, or no environment was slow in the
   // previous step): an environment that spent the step on the contact path defers everything, a light one nothing.
-  int fusedAgents = !(PARTIAL && pobs) ? 0 : nContact >= DRV_DEFER_MIN_CONTACT ? 0 : (A < DRV_FUSED_AGENTS ? A : DRV_FUSED_AGENTS);
+  int fusedAgents = !(PARTIAL && pobs) ? 0 : DRV_CNT_GET(EI_N_CONTACT) >= DRV_DEFER_MIN_CONTACT ? 0 : (A < DRV_FUSED_AGENTS ? A : DRV_FUSED_AGENTS);
   // With a forecast of when the launch will end (the previous step's slowest environment, drv_iso_report keeps it) every
   // environment, light or not, simply runs its passes until then and leaves the rest: the SIMDs whose four waves are all light are
   // the ones with the most vision to do (an environment on the contact path is done with its physics later and gets to fewer of
@@ -2007,8 +2070,11 @@ DRV_PROF(const unsigned long long K1 = __builtin_amdgcn_s_memtime();)
       else envi[EI_ERR] = envi[EI_ERR] | 4;  // only a host that replays a captured launch (frozen pv_par: the length is never cleared) gets here
     }
   }
-DRV_PROF(if (lane == 0 && e < 4096) { unsigned long long* d = g_dbgw + e * 12; const unsigned long long KE = __builtin_amdgcn_s_memtime(); d[0] = KE - KS; d[1] = nContact; d[2] = __popcll(occ); d[3] = nSteady + nQuiet; d[4] = K0 - KS; d[5] = tPh1; d[6] = tBroad; d[7] = tFast; d[8] = tCont; d[9] = (K1 - K0) - tPh1 - tBroad - tFast - tCont; d[10] = KE - K1; d[11] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned long long)__builtin_amdgcn_s_getreg(63492); })
+DRV_PROF(if (lane == 0 && e < 4096) { unsigned long long* d = g_dbgw + e * 12; const unsigned long long KE = __builtin_amdgcn_s_memtime(); d[0] = KE - KS; d[1] = DRV_CNT_GET(EI_N_CONTACT); d[2] = __popcll(occ); d[3] = DRV_CNT_GET(EI_N_STEADY) + DRV_CNT_GET(EI_N_QUIET); d[4] = K0 - KS; d[5] = tPh1; d[6] = tBroad; d[7] = tFast; d[8] = tCont; d[9] = (K1 - K0) - tPh1 - tBroad - tFast - tCont; d[10] = KE - K1; d[11] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned long long)__builtin_amdgcn_s_getreg(63492); })
 }
+
+#undef DRV_CNT
+#undef DRV_CNT_GET
 
 // tick_src = 1 (a step of this handle was captured into a hipGraph): what the host does between two eager launches, on the device
 // (flipPv: the deferred-vision parity alternates only over steps that run the Partial + deferred pair - a list's length word is cleared by
