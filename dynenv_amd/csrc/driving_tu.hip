@@ -5,6 +5,7 @@
 
 #include "driving_kernels.hip"
 #include "driving_partial.hip"
+#include "driving_reset_masked.hip"
 #include "dynenv_host.h"
 
 #define ISO_PROBE_EVERY 64     /* steps between two looks at the device's validation counter (an asynchronous 4-byte copy) */
@@ -201,6 +202,15 @@ struct HOST_LOCAL DrvHandle final : dynenv {
       hipLaunchKernelGGL(drv_partial_obs_kernel, dim3(S.E), dim3(64), 0, st, S, (int)cfg.noise_type, cfg.noise_magnitude, obs);
     else if (obs)
       hipLaunchKernelGGL(drv_obs_kernel, dim3(S.E), dim3(64), 0, st, S, obs);
+    return launched();
+  }
+
+  int reset_masked(const uint8_t* mask, float* obs, hipStream_t st) override {
+    hipLaunchKernelGGL(drv_reset_masked_kernel, dim3(S.E), dim3(64), 0, st, S, mask);
+    if (obs && partial)
+      hipLaunchKernelGGL(drv_partial_obs_masked_kernel, dim3(S.E), dim3(64), 0, st, S, mask, (int)cfg.noise_type, cfg.noise_magnitude, obs);
+    else if (obs)
+      hipLaunchKernelGGL(drv_obs_masked_kernel, dim3(S.E), dim3(64), 0, st, S, mask, obs);
     return launched();
   }
 

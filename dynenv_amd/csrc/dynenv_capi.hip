@@ -82,6 +82,12 @@ int dynenv_reset(dynenv_t* h, float* obs_dev, void* stream) {
   return h->reset(obs_dev, (hipStream_t)stream);
 }
 
+int dynenv_reset_masked(dynenv_t* h, const uint8_t* mask_dev, float* obs_dev, void* stream) {
+  if (!h || !mask_dev) return fail(DYNENV_ERR_ARG, "null argument");
+  ON_DEVICE(h);
+  return h->reset_masked(mask_dev, obs_dev, (hipStream_t)stream);
+}
+
 int dynenv_full_obs_dim(const dynenv_t* h) { return h ? h->full_dim : fail(DYNENV_ERR_ARG, "null handle"); }
 int dynenv_full_obs(dynenv_t* h, float* full_dev, void* stream) {
   if (!h || !full_dev) return fail(DYNENV_ERR_ARG, "null argument");
@@ -444,3 +450,6 @@ int dynenv_checkpoint_load(dynenv_t* h, const void* buf_host, size_t nbytes) {
 }
 
 }  // extern "C"
+
+// device code only, behind everything above: no kernel a step launches moves (rc_layout_pad, robocup_kernels.hip)
+#include "robocup_reset_masked.hip"

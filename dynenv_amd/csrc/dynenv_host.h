@@ -59,6 +59,9 @@ struct HOST_LOCAL dynenv {
   virtual void layout(dynenv_layout_t& L) const = 0;  // the block table and steps_per_episode
   virtual void set_seed(uint64_t seed) = 0;
   virtual int reset(float* obs, hipStream_t st) = 0;
+  // exactly the environments e with mask[e] != 0 (device uint8 [E]), each as reset() leaves it; one wave per environment, no more
+  // launches than reset(), nothing but launches on `st` (capturable behind a captured step); the scheduler's scratch is not touched
+  virtual int reset_masked(const uint8_t* mask, float* obs, hipStream_t st) = 0;
   // records ev_begin in front of the step's dominant kernel and ev_main right behind it (step_begin / step_main_done)
   virtual int step(const int* actions, const double* head, float* obs, double* rewards, uint8_t* dones, hipStream_t st) = 0;
   virtual int full_obs(float* full, hipStream_t st) = 0;

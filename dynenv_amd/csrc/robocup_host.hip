@@ -14,6 +14,11 @@ static int rc_full_row(int R, dynenv_layout_t* L = nullptr) {
   return row_blocks(L, 3, rows, feat);
 }
 
+// the kernels of robocup_reset_masked.hip, which dynenv_capi.hip includes last (behind everything the step launches run)
+extern "C" __global__ void rc_reset_masked_kernel(RcState S, const uint8_t* __restrict__ mask);
+extern "C" __global__ void rc_obs_masked_kernel(RcState S, const uint8_t* __restrict__ mask, float* __restrict__ obs);
+extern "C" __global__ void rc_partial_obs_masked_kernel(RcState S, const uint8_t* __restrict__ mask, float* __restrict__ obs);
+
 struct HOST_LOCAL RcHandle final : dynenv {
   RcState R;
 
@@ -137,6 +142,16 @@ struct HOST_LOCAL RcHandle final : dynenv {
       hipLaunchKernelGGL(rc_obs_kernel, dim3(R.E), dim3(64), 0, st, R, obs, 0);
       if (R.obs_type == DYNENV_OBS_PARTIAL)
         hipLaunchKernelGGL(rc_partial_obs_kernel, dim3(R.E), dim3(64), 0, st, R, obs, (double*)nullptr);
+    }
+    return launched();
+  }
+
+  int reset_masked(const uint8_t* mask, float* obs, hipStream_t st) override {
+    hipLaunchKernelGGL(rc_reset_masked_kernel, dim3(R.E), dim3(64), 0, st, R, mask);
+    if (obs) {
+      hipLaunchKernelGGL(rc_obs_masked_kernel, dim3(R.E), dim3(64), 0, st, R, mask, obs);
+      if (R.obs_type == DYNENV_OBS_PARTIAL)
+        hipLaunchKernelGGL(rc_partial_obs_masked_kernel, dim3(R.E), dim3(64), 0, st, R, mask, obs);
     }
     return launched();
   }

@@ -1822,7 +1822,9 @@ DE_OOL void rc_write_obs_ool(int lane, int R, int obs_dim, float* __restrict__ o
     float x;
     if (ff == 0) x = O.bx * team;
     else if (ff == 1) x = O.by * team;
-    else if (ff == 2) x = owned * team;
+    // ballOwned * team is an INT product in the reference (RoboCupEnvironment.py:1149-1189): a free ball reads +0.0f for either team,
+    // where the float product 0.0f * -1.0f is -0.0f; adding +0.0f turns that -0.0f into +0.0f and changes no other value
+    else if (ff == 2) x = owned * team + 0.0f;
     else if (ff == 3) x = (a == c0 || a == c1) ? 1.0f : 0.0f;
     else if (ff == 4) x = O.rx[a] * team;
     else if (ff == 5) x = O.ry[a] * team;

@@ -132,19 +132,80 @@ def _robocup_spaces(obs_type, allow_head_turn):
     return observation_space, action_space, reco
 
 
+def reset_mask(envs, num_envs, device=None):
+    """The argument of BatchedDynEnv.reset_envs -> a contiguous uint8 [num_envs] mask tensor (on `device`, if given).
+      * a bool tensor or numpy array, wherever it lives, and a uint8 tensor ON THE DEVICE - `dones` - are the mask itself: [num_envs],
+        taken as it is (bool is viewed as uint8: no copy, nothing is read);
+      * a list / numpy array / host tensor of integer ids - uint8 included: on the host small integers are ids, never a mask - is
+        built into a mask here and uploaded with one copy; an id may be listed more than once, an id outside [0, num_envs) raises.
+    Anything else (a float, ids on the device - checking them would mean reading them back -, more than one dimension, another
+    length) raises DynEnvError: before anything is launched."""
+    import torch
+    if isinstance(envs, torch.Tensor) and (envs.dtype == torch.bool or (envs.dtype == torch.uint8 and envs.device.type != "cpu")):
+        m = envs
+    elif isinstance(envs, torch.Tensor):
+        if envs.device.type != "cpu":
+            raise _capi.DynEnvError("reset_envs: a device tensor must be a bool / uint8 mask [%d], not %s ids (they would have to be read back "
+                                    "to be checked; `mask[ids] = 1` is one line)" % (num_envs, envs.dtype))
+        m = envs.numpy()
+    else:
+        m = np.asarray(envs)
+    if not isinstance(m, torch.Tensor):
+        if m.dtype == np.bool_:
+            m = torch.as_tensor(np.ascontiguousarray(m))
+        else:
+            if m.size and m.dtype.kind not in "iu":
+                raise _capi.DynEnvError("reset_envs: environment ids must be integers, got %s" % m.dtype)
+            if m.ndim > 1:
+                raise _capi.DynEnvError("reset_envs: expected a list of environment ids, got shape %s" % (m.shape,))
+            ids = m.reshape(-1).astype(np.int64)
+            if ids.size and (ids.min() < 0 or ids.max() >= num_envs):
+                raise _capi.DynEnvError("reset_envs: environment id %d outside [0, %d)" % (int(ids.min() if ids.min() < 0 else ids.max()), num_envs))
+            host = np.zeros((num_envs,), np.uint8)
+            host[ids] = 1
+            m = torch.as_tensor(host)
+    if m.dim() != 1 or m.shape[0] != num_envs:
+        raise _capi.DynEnvError("reset_envs: the mask must be [%d], got shape %s" % (num_envs, tuple(m.shape)))
+    if m.dtype == torch.bool:
+        m = m.view(torch.uint8)
+    if device is not None and m.device != torch.device(device):
+        m = m.to(device)
+    return m if m.is_contiguous() else m.contiguous()
+
+
 class BatchedDynEnv(object):
-    """All `num_envs` environments of one GPU shard behind the reference's VecEnv surface."""
+    """All `num_envs` environments of one GPU shard behind the reference's VecEnv surface.
+
+    `episodes` says who decides that an episode is over:
+      * "lockstep" (the default): the whole batch is at one position of its fixed-length episode, the host counts the steps, and
+        step_flat(auto_reset=True) resets all environments together at the episode's end (SubprocVecEnv semantics, SURVEY F6);
+      * "per_env": every environment keeps its own time on the device.  step_flat(auto_reset=True) is the step followed by
+        reset_envs(dones) on the same stream: `dones` is the step's, and the rows of `obs` of the environments that finished already
+        hold their next episode's first observation.  Nothing is decided on the host, so the call may be captured into a graph, and
+        set_state / set_states / restore / fork / reset_envs may put environments at different times.  `keep_terminal_obs=True` copies
+        `obs` into the persistent tensor `terminal_obs` before that reset (a 38 MB copy per step at 4096 x 10 Driving Full); `track_episode_stats=True`
+        refreshes `last_episode_stats` (r, p, o, g) for the environments that just finished (one episode_stats() call per step, into persistent tensors:
+        both options work inside a captured step).
+        The compat step() / step_wait() raise: the reference's object-array protocol is lock-step by construction."""
 
     metadata = {"render.modes": []}
 
     def __init__(self, env_type, num_envs, num_players, observationType=ObservationType.FULL,
                  noiseType=NoiseType.REALISTIC, noiseMagnitude=0, use_continuous_actions=False, seed=42,
-                 device=None, env_id_offset=0, flags=None, out_buffers=None, eager_compat=False):
+                 device=None, env_id_offset=0, flags=None, out_buffers=None, eager_compat=False, episodes="lockstep",
+                 keep_terminal_obs=False, track_episode_stats=False):
         import torch  # device memory + streams only
         if not torch.cuda.is_available():
             raise _capi.DynEnvError("dynenv_amd needs an MI355X (HIP device); there is no CPU fallback")
+        if episodes not in ("lockstep", "per_env"):
+            raise _capi.DynEnvError("episodes must be 'lockstep' or 'per_env', got %r" % (episodes,))
         self._torch = torch
         self._lib = _capi.load()
+        self.episodes = episodes
+        self.per_env = episodes == "per_env"
+        self.keep_terminal_obs, self.track_episode_stats = bool(keep_terminal_obs), bool(track_episode_stats)
+        self.last_episode_stats = None
+        self._stats_now = None
         env_type = DynEnvType(env_type)
         if env_type == DynEnvType.DRIVE and use_continuous_actions:
             # reference quirk C4: the continuous-action branch of DrivingEnvironment.processAction is broken
@@ -194,6 +255,14 @@ class BatchedDynEnv(object):
         self._builder = CompatBuilder(row_groups(self.layout, env_type, observationType))
         self._counts_np = None
         self.terminal_obs = None
+        if self.per_env:
+            # persistent buffers, written in place by every step: a captured step refreshes THESE tensors at every replay
+            if self.keep_terminal_obs:
+                self.terminal_obs = torch.zeros_like(self.obs)
+            if self.track_episode_stats:
+                mk = lambda n, dt: torch.zeros((E, n), dtype=dt, device=self.device)
+                self.last_episode_stats = (mk(A, torch.float64), mk(A, torch.float64), mk(A, torch.float64), mk(2, torch.int32))
+                self._stats_now = tuple(torch.zeros_like(x) for x in self.last_episode_stats)
         self._episode_step = 0
         self._needs_reset = True
         self._pending = None
@@ -213,6 +282,19 @@ class BatchedDynEnv(object):
         self._episode_step = 0
         self._needs_reset = False
         self._counts_np = None  # the scene (obstacle / pedestrian counts) changed
+        return self.obs
+
+    def reset_envs(self, envs):
+        """Reset exactly the listed environments on the device (dynenv_reset_masked: one wave per environment, on torch's current stream,
+        nothing waited for) and write their first observation into their rows of `self.obs`; every other environment and its rows stay
+        as they are.  `envs`: a bool / uint8 [num_envs] device tensor - `self.dones`, say -, used as it is, or a list / numpy array / host
+        tensor of environment ids (reset_mask).  A listed environment ends up exactly as reset_flat() would leave it: next episode,
+        time 0, a fresh scene, contact cache, shortcut state and error word cleared.  With episodes="lockstep" the host's position in
+        the episode stays where it is: `dones` of an environment reset on its own then comes from its own time on the device."""
+        mask = reset_mask(envs, self.num_envs, self.device)
+        _capi.check(self._lib.dynenv_reset_masked(self._h, C.c_void_p(mask.data_ptr()), C.c_void_p(self.obs.data_ptr()), self._stream()),
+                    "dynenv_reset_masked")
+        self._counts_np = None  # the scenes (obstacle / pedestrian counts) changed
         return self.obs
 
     def _stage_actions(self, actions):
@@ -253,7 +335,7 @@ class BatchedDynEnv(object):
         if self._needs_reset:
             raise _capi.DynEnvError("call reset() before step()")
         torch = self._torch
-        if auto_reset and torch.cuda.is_current_stream_capturing():
+        if auto_reset and not self.per_env and torch.cuda.is_current_stream_capturing():
             # the host's position in the episode does not advance at replay: a reset decided now would be frozen into the graph (or never come)
             raise _capi.DynEnvError("step_flat(auto_reset=True) inside a stream capture: capture with auto_reset=False and reset between replays")
         a, head = self._stage_actions(actions)
@@ -275,6 +357,18 @@ class BatchedDynEnv(object):
             _capi.check(self._lib.dynenv_step(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(self.obs.data_ptr()),
                                               C.c_void_p(self.rewards.data_ptr()), C.c_void_p(self.dones.data_ptr()),
                                               self._stream()), "dynenv_step")
+        if self.per_env:
+            # every environment ends on its own: the device's `dones` is the mask, no host counter is read or kept
+            if auto_reset:
+                if self.keep_terminal_obs:
+                    self.terminal_obs.copy_(self.obs)
+                if self.track_episode_stats:
+                    self.episode_stats(out=self._stats_now)
+                    done = self.dones.bool().unsqueeze(1)
+                    for last, now in zip(self.last_episode_stats, self._stats_now):
+                        torch.where(done, now, last, out=last)
+                self.reset_envs(self.dones)
+            return self.obs, self.rewards, self.dones
         self._episode_step += 1
         self.last_done = self._episode_step >= self.steps_per_episode  # fixed-length episodes
         if self.last_done and auto_reset:
@@ -284,13 +378,17 @@ class BatchedDynEnv(object):
             self.reset_flat()
         return self.obs, self.rewards, self.dones
 
-    def episode_stats(self):
+    def episode_stats(self, out=None):
+        """(r, p, o [E, A] float64, g [E, 2] int32) of the running episodes; `out`: four such tensors to write into instead of new ones"""
         torch = self._torch
         E, A = self.num_envs, self.n_agents
-        r = torch.empty((E, A), dtype=torch.float64, device=self.device)
-        p = torch.empty_like(r)
-        o = torch.empty_like(r)
-        g = torch.empty((E, 2), dtype=torch.int32, device=self.device)
+        if out is not None:
+            r, p, o, g = out
+        else:
+            r = torch.empty((E, A), dtype=torch.float64, device=self.device)
+            p = torch.empty_like(r)
+            o = torch.empty_like(r)
+            g = torch.empty((E, 2), dtype=torch.int32, device=self.device)
         _capi.check(self._lib.dynenv_episode_stats(self._h, C.c_void_p(r.data_ptr()), C.c_void_p(p.data_ptr()),
                                                    C.c_void_p(o.data_ptr()), C.c_void_p(g.data_ptr()), self._stream()),
                     "dynenv_episode_stats")
@@ -336,6 +434,9 @@ class BatchedDynEnv(object):
         (Blobs that put different environments at different times make `dones` meaningless; the device keeps stepping them.)"""
         _capi.check(self._lib.dynenv_set_state(self._h, env, C.byref(st), C.sizeof(st)), "dynenv_set_state")
         self._counts_np = None  # the scene (obstacle / pedestrian counts) may have changed
+        if self.per_env:  # no host-side position: the environment's own `elapsed` is all there is
+            self._needs_reset = False
+            return
         step = int(st.elapsed) // self._substeps()
         if not self._needs_reset and step != self._episode_step and self.num_envs > 1 and not getattr(self, "_set_state_moved", False):
             # ONE blob with another `elapsed` than the batch's moves the host's episode position - and with it `dones` and the auto-reset of
@@ -396,7 +497,7 @@ class BatchedDynEnv(object):
         meaningful for them.  On a handle that was never reset there is no position to keep: pass `episode_step` then.
         Duplicate ids in one call are an error (raised when the ids live on the host, unspecified state otherwise)."""
         torch = self._torch
-        if self._needs_reset and episode_step is None:
+        if self._needs_reset and episode_step is None and not self.per_env:
             raise _capi.DynEnvError("set_states before the first reset(): pass episode_step (the batch's position in its lock-step episode)")
         ids, n = self._env_ids(env_ids, unique=True)
         size = self.state_size
@@ -424,6 +525,8 @@ class BatchedDynEnv(object):
         self._counts_np = None  # the scenes (obstacle / pedestrian counts) may have changed
         if episode_step is not None:
             self._episode_step = int(episode_step)
+            self._needs_reset = False
+        elif self.per_env:
             self._needs_reset = False
         return status
 
@@ -464,6 +567,8 @@ class BatchedDynEnv(object):
         _capi.check(self._lib.dynenv_checkpoint_load(self._h, C.c_void_p(buf.ctypes.data), buf.size), "dynenv_checkpoint_load")
         self._needs_reset = False
         self._counts_np = None
+        if self.per_env:
+            return
         # the host's position in the (lock-step, fixed-length) episode follows the restored device state: auto-reset and
         # `dones` are driven by it
         self._episode_step = int(self.get_state(0).elapsed) // self._substeps()
@@ -550,6 +655,9 @@ class BatchedDynEnv(object):
         self._pending = actions
 
     def step_wait(self):
+        if self.per_env:
+            raise _capi.DynEnvError("step() / step_wait() return the reference's lock-step object arrays (SURVEY F6): with episodes='per_env' "
+                                    "use step_flat()")
         actions, self._pending = self._pending, None
         counts = self._host_counts()
         self.step_flat(actions if self.allow_head_turn else np.asarray(actions), auto_reset=False, validate=True)

@@ -7,6 +7,8 @@
  *                           RoboCupEnvironment objects (DrivingEnvironment.py:20-56, RoboCupEnvironment.py:23-71)
  *   dynenv_reset         <- DynEnv/utils/subproc_vec_env.py:118-122 SubprocVecEnv.reset ->
  *                           DynEnv/environment_base.py:205-224 EnvironmentBase.reset
+ *   dynenv_reset_masked  <- the same EnvironmentBase.reset (environment_base.py:205-224), for chosen environments: what a
+ *                           SubprocVecEnv worker does when ITS environment is done (subproc_vec_env.py:19-22)
  *   dynenv_step          <- DynEnv/utils/subproc_vec_env.py:102-111 step_async/step_wait ->
  *                           DynEnv/DrivingEnvironment.py:248-322 / DynEnv/RoboCupEnvironment.py:446-524 step
  *   dynenv_episode_stats <- info['episode_r'|'episode_p_r'|'episode_o_r'|'episode_g'] (DrivingEnvironment.py:310-316,
@@ -150,6 +152,19 @@ int dynenv_seed(dynenv_t* h, uint64_t seed);
 
 /* (Re)build every environment's scene and write the first observation(s): obs_dev float32 [E, T, A, obs_dim]. */
 int dynenv_reset(dynenv_t* h, float* obs_dev, void* stream);
+
+/* Reset exactly the environments e with mask_dev[e] != 0 (uint8 [E]; the dones_dev of the step before it is a valid mask).
+ * obs_dev as for dynenv_reset: float32 [E, T, A, obs_dim], or NULL.
+ *   A LISTED environment ends up as dynenv_reset would leave it, starting from the same per-environment episode counter - byte for
+ *   byte, in every device array of the handle: its episode counter goes up by one, its elapsed time becomes 0 and its scene is redrawn
+ *   from (seed, global id, episode); its accumulators are zeroed, its contact-cache slots freed, its shortcut state and its error word
+ *   cleared; RoboCup: the joints' order, the per-environment constants and the shape cache are rewritten.  obs_dev[e] gets the first
+ *   observation: T copies for Full, T separate noisy draws (time word t) for Partial.
+ *   An UNLISTED environment: no byte of its state and no byte of obs_dev[e] changes.
+ * Ordered on `stream`; no host synchronisation, no allocation, no host copy: capturable into a hipGraph behind a captured dynenv_step.
+ * One wave per environment, no more launches than dynenv_reset; the scheduler's scratch (timing only) is not touched.
+ * Errors: NULL handle or mask -> DYNENV_ERR_ARG. */
+int dynenv_reset_masked(dynenv_t* h, const uint8_t* mask_dev, float* obs_dev, void* stream);
 
 /* One environment step for all E environments (10 / 50 physics substeps fused in one launch).
  *   actions_dev  int32 [E, A, action_dim]      obs_dev float32 [E, T, A, obs_dim]
