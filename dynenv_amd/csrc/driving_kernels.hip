@@ -2095,119 +2095,6 @@ drv_step_partial_kernel(DrvState S, const int* __restrict__ actions, double* __r
   drv_step_body<true>(S, actions, nullptr, rewards, dones, pobs, pvNoise, pvMagn);
 }
 
-// ------------------------------------------------------------------------------------------------
-// observation-only kernel (used after reset / set_state)
-// ------------------------------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(64) drv_obs_kernel(DrvState S, float* __restrict__ obs) {
-  DrvLds& L = g_L;
-  const int e = blockIdx.x, lane = threadIdx.x, A = S.A;
-  const int* envi = S.envi + (size_t)e * EI_COUNT;
-  const int nPed = uniform_i(envi[EI_NPED]), nObst = uniform_i(envi[EI_NOBST]);
-  load_env(S, L, e, lane, A, nPed, nObst, 0ull);
-  write_full_obs_ool(lane, A, nPed, nObst, S.obs_dim, obs + (size_t)e * A * S.obs_dim);
-}
-
-// ------------------------------------------------------------------------------------------------
-// reset kernel: scene re-randomisation, one thread per environment
-// (environment_base.py:205-211 -> DrivingEnvironment._setup_scene :58-115, :527-584).  Not on the per-step path.
-// ------------------------------------------------------------------------------------------------
-DE_DEV void road_get_spot(const DrvRoad& r, int lane, int spot, V2& pos, double& angle) {  // Road.py:100-114
-  int end = lane >= r.nLanes ? 1 : 0;
-  V2 p = end ? r.p1 : r.p0;
-  V2 spotDir = vmul(end ? vneg(r.dir) : r.dir, r.followDist);
-  V2 laneDir = vmul(end ? r.normal : vneg(r.normal), r.width);
-  double l = (double)(end ? lane - r.nLanes : lane) + 0.5;
-  pos = vadd(vadd(p, vmul(laneDir, l)), vmul(spotDir, (double)spot));
-  angle = dm_atan2(spotDir.y, spotDir.x);
-}
-DE_DEV V2 road_get_walk_spot(const DrvRoad& r, int side, double length, double width) {  // Road.py:117-123
-  V2 w0 = r.walk[side][0], w1 = r.walk[side][1];
-  V2 center = vadd(w0, vmul(vsub(w1, w0), length));
-  double f = width * r.width;
-  V2 off = vmul(vmul(r.normal, f), side ? 1.0 : -1.0);
-  return vadd(center, off);
-}
-
-extern "C" __global__ void __launch_bounds__(64) drv_reset_kernel(DrvState S) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= S.E) return;
-  const size_t E = (size_t)S.E;
-  const int A = S.A;
-  int* envi = S.envi + (size_t)e * EI_COUNT;
-  const uint32_t ep = (uint32_t)envi[EI_EPISODE];
-  const uint32_t genv = (uint32_t)(S.env_id_offset + e);
-  // zero this env's rows
-  for (int k = 0; k < DRV_NB; ++k) {
-    for (int f = 0; f < BF_COUNT; ++f) S.body[(size_t)f * E * DRV_NB + (size_t)e * DRV_NB + k] = 0.0;
-    S.flags[(size_t)e * DRV_NB + k] = 0;
-    S.aux[(size_t)e * DRV_NB + k] = 0;
-  }
-  for (int k = 0; k < 16; ++k) {
-    for (int f = 0; f < CF_COUNT; ++f) S.carx[(size_t)f * E * 16 + (size_t)e * 16 + k] = 0.0;
-    S.epr[(size_t)e * 16 + k] = 0.0;
-    S.epr[E * 16 + (size_t)e * 16 + k] = 0.0;
-  }
-  for (int k = 0; k < DRV_NS; ++k) { S.s_pair[(size_t)e * DRV_NS + k] = 0xFFFF; S.s_meta[(size_t)e * DRV_NS + k] = 0; }
-  // cars: spots = permutation(30)[:A] (partial Fisher-Yates), road/end/team/type draws
-  int spots[30];
-  for (int i = 0; i < 30; ++i) spots[i] = i;
-  for (int i = 0; i < A; ++i) {
-    dm_u32x4 u = dm_env_rng(S.seed, genv, ep, DM_RNG_RESET_PERM, (uint32_t)i, 0);
-    int j = i + dm_randint(u.v[0], 0, 29 - i);
-    int t = spots[i]; spots[i] = spots[j]; spots[j] = t;
-  }
-  for (int i = 0; i < A; ++i) {
-    dm_u32x4 u = dm_env_rng(S.seed, genv, ep, DM_RNG_RESET_AGENT, (uint32_t)i, 0);
-    int roadSel = dm_randint(u.v[0], 0, 1), endSel = dm_randint(u.v[1], 0, 1);
-    int team = dm_randint(u.v[2], 0, 2), type = dm_randint(u.v[3], 0, 3);
-    V2 goal = endSel ? C.roads[roadSel].p1 : C.roads[roadSel].p0;
-    int spotID = spots[i];
-    int roadID = spotID < 20 ? 0 : 1;
-    spotID -= roadID ? 20 : 0;
-    int laneID = spotID / 5, spot = spotID % 5;
-    V2 pos; double angle;
-    road_get_spot(C.roads[roadID], laneID, spot, pos, angle);
-    V2 dir = vrot_angle(v2(1.0, 0.0), angle);
-    size_t b = (size_t)e * DRV_NB + i;
-    S.body[BF_PX * E * DRV_NB + b] = pos.x; S.body[BF_PY * E * DRV_NB + b] = pos.y; S.body[BF_ANG * E * DRV_NB + b] = angle;
-    size_t c = (size_t)e * 16 + i;
-    S.carx[CF_DIRX * E * 16 + c] = dir.x; S.carx[CF_DIRY * E * 16 + c] = dir.y;
-    S.carx[CF_PREVX * E * 16 + c] = pos.x; S.carx[CF_PREVY * E * 16 + c] = pos.y;
-    S.carx[CF_GOALX * E * 16 + c] = goal.x; S.carx[CF_GOALY * E * 16 + c] = goal.y;
-    S.flags[b] = CARF_PACK(type, team, 0, 0, 0, LP_OffRoad);
-  }
-  dm_u32x4 uc = dm_env_rng(S.seed, genv, ep, DM_RNG_RESET_COUNTS, 0, 0);
-  int nPed = dm_randint(uc.v[0], 10, 20), nObstRaw = dm_randint(uc.v[1], 10, 20);
-  for (int i = 0; i < nPed; ++i) {
-    dm_u32x4 a = dm_env_rng(S.seed, genv, ep, DM_RNG_RESET_PED, (uint32_t)i, 0);
-    dm_u32x4 bq = dm_env_rng(S.seed, genv, ep, DM_RNG_RESET_PED, (uint32_t)i, 1);
-    int road = dm_randint(a.v[0], 0, 1), side = dm_randint(a.v[1], 0, 1);
-    double len = dm_unit(a.v[2]), wid = dm_unit(a.v[3]) / 2.0 + 0.25;
-    V2 p = road_get_walk_spot(C.roads[road], side, len, wid);
-    size_t b = (size_t)e * DRV_NB + DRV_SLOT_PED + i;
-    S.body[BF_PX * E * DRV_NB + b] = p.x; S.body[BF_PY * E * DRV_NB + b] = p.y;
-    S.flags[b] = PEDF_PACK(road, side, 0, 0, 0, dm_randint(bq.v[0], 3, 6));
-  }
-  int nObst = 0;
-  for (int i = 0; i < nObstRaw; ++i) {
-    dm_u32x4 a = dm_env_rng(S.seed, genv, ep, DM_RNG_RESET_OBST, (uint32_t)i, 0);
-    int road = dm_randint(a.v[0], 0, 1), side = dm_randint(a.v[1], 0, 1);
-    double len = dm_unit(a.v[2]), wid = dm_unit(a.v[3]) / 2.0 + 0.25;
-    V2 c = road_get_walk_spot(C.roads[road], side, len, wid);
-    if (drv_is_off_road(c)) {
-      S.obst[(size_t)e * DRV_MAXO + nObst] = c.x;
-      S.obst[E * DRV_MAXO + (size_t)e * DRV_MAXO + nObst] = c.y;
-      nObst++;
-    }
-  }
-  envi[EI_ELAPSED] = 0; envi[EI_ALLFIN] = 0; envi[EI_NPED] = nPed; envi[EI_NOBST] = nObst;
-  envi[EI_EPISODE] = (int)(ep + 1); envi[EI_OCC] = 0; envi[EI_ERR] = 0;
-  envi[EI_N_FAST] = 0; envi[EI_N_QUIET] = 0; envi[EI_N_CONTACT] = 0; envi[EI_N_SLOTS] = 0; envi[EI_PAD] = 0;
-  envi[EI_N_STEADY] = 0; envi[EI_N_LIGHT] = 0; envi[EI_N_SPLIT] = 0;
-  envi[EI_N_WHY_CAND] = 0; envi[EI_N_WHY_MOVING] = 0; envi[EI_N_WHY_INERT] = 0;
-  for (int k = 0; k < 64; ++k) S.lastcand[(size_t)e * 64 + k] = -1;
-}
-
 // episode_g = [#finished & !crashed, #crashed] (:315-316) + episode accumulators, gathered for the host mirror
 extern "C" __global__ void drv_stats_kernel(DrvState S, double* ep_r, double* ep_pos_r, double* ep_obs_r, int* goals) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2248,7 +2135,8 @@ extern "C" __global__ void math_selftest_kernel(const double* x, const double* y
 // step kernels.  The blob travels between HBM and an LDS tile as contiguous 8-byte words across the wave (a blob is 8-byte aligned, no
 // more: dynenv.h); the lanes then read / write their own car or pedestrian struct in LDS, and every access to the field-major arrays is
 // one whole row of the environment per instruction ([e][32] doubles = one 256-byte segment).  No lane strides over the 128- / 64-byte
-// structs in global memory.  Same bytes as the per-environment host path of driving_tu.hip (get_state / set_state), which stays.
+// structs in global memory.  dynenv_get_state / dynenv_set_state are these kernels for one blob (idx == nullptr, first = the
+// environment) through a staging area in device memory.
 // ------------------------------------------------------------------------------------------------
 #define DRV_BLOB_WORDS ((int)(sizeof(dynenv_driving_state_t) / 8))
 static_assert(sizeof(dynenv_driving_state_t) % 8 == 0, "the blob moves as 8-byte words");
@@ -2257,12 +2145,12 @@ union DrvBlobTile {
   unsigned long long q[DRV_BLOB_WORDS];
 };
 
-// idx == nullptr: environments 0..n-1.  An index outside [0, E) leaves its blob untouched.
+// idx == nullptr: environments first..first + n - 1.  An index outside [0, E) leaves its blob untouched.
 extern "C" __global__ void __launch_bounds__(64)
-drv_get_states_kernel(DrvState S, const int* __restrict__ idx, unsigned long long* __restrict__ blobs) {
+drv_get_states_kernel(DrvState S, const int* __restrict__ idx, int first, unsigned long long* __restrict__ blobs) {
   __shared__ DrvBlobTile T;
   const int lane = threadIdx.x, k = blockIdx.x, A = S.A;
-  const int e = idx ? uniform_i(idx[k]) : k;
+  const int e = idx ? uniform_i(idx[k]) : first + k;
   if (e < 0 || e >= S.E) return;
   const size_t E = (size_t)S.E, row = (size_t)e * DRV_NB;
   for (int q = lane; q < DRV_BLOB_WORDS; q += 64) T.q[q] = 0ull;  // pads and unused car / pedestrian / obstacle slots read 0
@@ -2307,12 +2195,14 @@ drv_get_states_kernel(DrvState S, const int* __restrict__ idx, unsigned long lon
   for (int q = lane; q < DRV_BLOB_WORDS; q += 64) out[q] = T.q[q];
 }
 
-// status (may be nullptr): 0 written, 1 blob rejected (error bit 6 raised on the environment, nothing else touched), 2 index outside [0, E)
+// status (may be nullptr): 0 written, 1 blob rejected (nothing of the environment touched but, if `raise`, error bit 6 raised on it: the
+// batched call has nobody to return an error to, the synchronous one has), 2 index outside [0, E).  This is THE test of a blob's fit.
 extern "C" __global__ void __launch_bounds__(64)
-drv_set_states_kernel(DrvState S, const int* __restrict__ idx, const unsigned long long* __restrict__ blobs, int* __restrict__ status) {
+drv_set_states_kernel(DrvState S, const int* __restrict__ idx, int first, const unsigned long long* __restrict__ blobs, int* __restrict__ status,
+                      int raise) {
   __shared__ DrvBlobTile T;
   const int lane = threadIdx.x, k = blockIdx.x, A = S.A;
-  const int e = idx ? uniform_i(idx[k]) : k;
+  const int e = idx ? uniform_i(idx[k]) : first + k;
   if (e < 0 || e >= S.E) { if (status && lane == 0) status[k] = 2; return; }
   const size_t E = (size_t)S.E, row = (size_t)e * DRV_NB;
   const unsigned long long* in = blobs + (size_t)k * DRV_BLOB_WORDS;
@@ -2320,7 +2210,7 @@ drv_set_states_kernel(DrvState S, const int* __restrict__ idx, const unsigned lo
   __syncthreads();
   const int nPed = uniform_i(T.st.n_peds), nObst = uniform_i(T.st.n_obst);
   if (uniform_i(T.st.n_cars) != A || nPed < 0 || nPed > DRV_MAXP || nObst < 0 || nObst > DRV_MAXO) {
-    if (lane == 0) { atomicOr(&S.envi[(size_t)e * EI_COUNT + EI_ERR], 64); if (status) status[k] = 1; }
+    if (lane == 0) { if (raise) atomicOr(&S.envi[(size_t)e * EI_COUNT + EI_ERR], 64); if (status) status[k] = 1; }
     return;
   }
   if (lane < DRV_NB) {

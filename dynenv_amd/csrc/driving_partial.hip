@@ -564,16 +564,7 @@ DE_DEV PvIn pv_load_inputs(const DrvState& S, int e, int lane, int nPed, int nOb
   return in;
 }
 
-// stand-alone launch (after reset / set_state, where no step kernel ran)
-extern "C" __global__ void __launch_bounds__(64, 4)  // 128 VGPRs: all 4096 environments resident in one pass
-drv_partial_obs_kernel(DrvState S, int noiseType, double magn, float* __restrict__ obs) {
-  const int e = blockIdx.x, lane = threadIdx.x;
-  const int* envi = S.envi + (size_t)e * EI_COUNT;
-  const int nPed = uniform_i(envi[EI_NPED]), nObst = uniform_i(envi[EI_NOBST]), elapsed = uniform_i(envi[EI_ELAPSED]);
-  const uint32_t episode = (uint32_t)uniform_i(envi[EI_EPISODE]);
-  const PvIn in = pv_load_inputs(S, e, lane, nPed, nObst);
-  pv_env(S, g_P, e, lane, nPed, nObst, elapsed, episode, in, noiseType, magn, obs, 0, S.A);
-}
+// (the stand-alone launch behind a reset: drv_partial_obs_kernel, driving_reset.hip)
 
 // Fused call at the end of drv_step_kernel: the wave that has just finished environment e's step produces its Partial
 // observation right away, from the state still in its LDS tile, while the waves of heavier environments are still

@@ -1,18 +1,38 @@
-// driving_reset_masked.hip - dynenv_reset_masked for Driving: reset exactly the environments whose mask byte is set, one wave per
-// environment (grid E; a wave whose byte is 0 ends at once), and write their first observation.  Included at the END of the device
-// code of driving_tu.hip: no instruction of what the step launches run changes (the unit's addresses are not pinned: DESIGN.md 4).
+// driving_reset.hip - the Driving reset (dynenv_reset, dynenv_reset_masked) and the stand-alone observation kernels: what runs when no
+// step does.  Included at the END of the device code of driving_tu.hip, so everything a step launches stays in front of it (the unit's
+// addresses are not pinned: DESIGN.md 4).
 //
-// drv_reset_masked_kernel leaves a listed environment byte for byte as drv_reset_kernel (one thread per environment, which stays)
-// would: the same dm_env_rng draws (purpose, entity, counter), the same road_get_spot / road_get_walk_spot / vrot_angle arithmetic,
-// the same words written and the same words left alone (obstacle slots behind the new count, envi[EI_DEFER_OBS], the cache's hashes
-// and impulses).  Lane = object, as in the step kernel: cars 0..9, pedestrians 10..29, obstacle candidates 30..49.  Every access to
-// the field-major arrays is one whole row of the environment per instruction, as in drv_set_states_kernel.
+// drv_reset_masked_kernel: one wave per environment (grid E).  mask == nullptr resets every environment, otherwise exactly those whose
+// byte is set (a wave whose byte is 0 ends at once).  Lane = object, as in the step kernel: cars 0..9, pedestrians 10..29, obstacle
+// candidates 30..49; every lane makes its own dm_env_rng draws (purpose, entity, counter), and every access to the field-major arrays
+// is one whole row of the environment per instruction, as in drv_set_states_kernel.
+// A reset WRITES: the body, flag, aux, car and episode-reward rows whole (scene re-randomisation, environment_base.py:205-211 ->
+// DrivingEnvironment._setup_scene :58-115, :527-584), the obstacles it keeps, the contact cache's pair and meta words (every slot
+// free), lastcand (-1) and the int row - time 0, the next episode, the new counts, everything else 0.
+// It LEAVES ALONE: the obstacle slots behind the new count, envi[EI_DEFER_OBS] (scheduling scratch of the Partial step) and the contact
+// cache's hashes and impulses.
+DE_DEV void road_get_spot(const DrvRoad& r, int lane, int spot, V2& pos, double& angle) {  // Road.py:100-114
+  int end = lane >= r.nLanes ? 1 : 0;
+  V2 p = end ? r.p1 : r.p0;
+  V2 spotDir = vmul(end ? vneg(r.dir) : r.dir, r.followDist);
+  V2 laneDir = vmul(end ? r.normal : vneg(r.normal), r.width);
+  double l = (double)(end ? lane - r.nLanes : lane) + 0.5;
+  pos = vadd(vadd(p, vmul(laneDir, l)), vmul(spotDir, (double)spot));
+  angle = dm_atan2(spotDir.y, spotDir.x);
+}
+DE_DEV V2 road_get_walk_spot(const DrvRoad& r, int side, double length, double width) {  // Road.py:117-123
+  V2 w0 = r.walk[side][0], w1 = r.walk[side][1];
+  V2 center = vadd(w0, vmul(vsub(w1, w0), length));
+  double f = width * r.width;
+  V2 off = vmul(vmul(r.normal, f), side ? 1.0 : -1.0);
+  return vadd(center, off);
+}
 
 extern "C" __global__ void __launch_bounds__(64)
 drv_reset_masked_kernel(DrvState S, const uint8_t* __restrict__ mask) {
   __shared__ int spots[32];
   const int e = blockIdx.x, lane = threadIdx.x, A = S.A;
-  if (uniform_i(mask[e]) == 0) return;
+  if (mask && uniform_i(mask[e]) == 0) return;
   const size_t E = (size_t)S.E, row = (size_t)e * DRV_NB;
   const uint32_t ep = (uint32_t)uniform_i(S.envi[(size_t)e * EI_COUNT + EI_EPISODE]);
   const uint32_t genv = (uint32_t)(S.env_id_offset + e);
@@ -68,8 +88,7 @@ drv_reset_masked_kernel(DrvState S, const uint8_t* __restrict__ mask) {
       keep = drv_is_off_road(w);
     }
   }
-  // the obstacles drv_is_off_road keeps, compacted in ascending candidate order (what the serial loop gives); the slots behind the
-  // new count keep what they held, as after drv_reset_kernel
+  // the obstacles drv_is_off_road keeps, compacted in ascending candidate order; the slots behind the new count keep what they held
   const uint64_t kept = wave_ballot(keep);
   const int nObst = __popcll(kept);
   if (keep) {
@@ -90,28 +109,29 @@ drv_reset_masked_kernel(DrvState S, const uint8_t* __restrict__ mask) {
   }
   if (lane < DRV_NS) { S.s_pair[(size_t)e * DRV_NS + lane] = 0xFFFF; S.s_meta[(size_t)e * DRV_NS + lane] = 0; }
   // the int row: time 0, the next episode, the new counts; cache occupancy, error word, shortcut bits and the diagnostics at 0
-  // (EI_DEFER_OBS is scheduling scratch of the Partial step and keeps its value, as after drv_reset_kernel)
-  static_assert(EI_DEFER_OBS == EI_COUNT - 1, "the words drv_reset_kernel writes are the row without its last one");
+  // (EI_DEFER_OBS is scheduling scratch of the Partial step and keeps its value)
+  static_assert(EI_DEFER_OBS == EI_COUNT - 1, "the words a reset writes are the row without its last one");
   if (lane < EI_DEFER_OBS)
     S.envi[(size_t)e * EI_COUNT + lane] = lane == EI_NPED ? nPed : lane == EI_NOBST ? nObst : lane == EI_EPISODE ? (int)(ep + 1) : 0;
   S.lastcand[(size_t)e * 64 + lane] = -1;  // quiescent shortcut state unknown
 }
 
-// the first observation of the listed environments: drv_obs_kernel / drv_partial_obs_kernel behind the mask test, the same device functions
-extern "C" __global__ void __launch_bounds__(64) drv_obs_masked_kernel(DrvState S, const uint8_t* __restrict__ mask, float* __restrict__ obs) {
+// The stand-alone observation kernels, one wave per environment (grid E), mask as above: the first observation behind a reset, and
+// dynenv_full_obs (drv_obs_kernel, every environment).  The step kernels write their own.
+extern "C" __global__ void __launch_bounds__(64) drv_obs_kernel(DrvState S, const uint8_t* __restrict__ mask, float* __restrict__ obs) {
   DrvLds& L = g_L;
   const int e = blockIdx.x, lane = threadIdx.x, A = S.A;
-  if (uniform_i(mask[e]) == 0) return;
+  if (mask && uniform_i(mask[e]) == 0) return;
   const int* envi = S.envi + (size_t)e * EI_COUNT;
   const int nPed = uniform_i(envi[EI_NPED]), nObst = uniform_i(envi[EI_NOBST]);
   load_env(S, L, e, lane, A, nPed, nObst, 0ull);
   write_full_obs_ool(lane, A, nPed, nObst, S.obs_dim, obs + (size_t)e * A * S.obs_dim);
 }
 
-extern "C" __global__ void __launch_bounds__(64, 4)
-drv_partial_obs_masked_kernel(DrvState S, const uint8_t* __restrict__ mask, int noiseType, double magn, float* __restrict__ obs) {
+extern "C" __global__ void __launch_bounds__(64, 4)  // 128 VGPRs: all 4096 environments resident in one pass
+drv_partial_obs_kernel(DrvState S, const uint8_t* __restrict__ mask, int noiseType, double magn, float* __restrict__ obs) {
   const int e = blockIdx.x, lane = threadIdx.x;
-  if (uniform_i(mask[e]) == 0) return;
+  if (mask && uniform_i(mask[e]) == 0) return;
   const int* envi = S.envi + (size_t)e * EI_COUNT;
   const int nPed = uniform_i(envi[EI_NPED]), nObst = uniform_i(envi[EI_NOBST]), elapsed = uniform_i(envi[EI_ELAPSED]);
   const uint32_t episode = (uint32_t)uniform_i(envi[EI_EPISODE]);

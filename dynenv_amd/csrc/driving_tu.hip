@@ -1,11 +1,11 @@
 // driving_tu.hip - the Driving translation unit: the kernels of driving_kernels.hip / driving_partial.hip and the Driving handle, i.e.
-// all of their host code (constants, allocation, the isolation scheduler, launches, state blobs, diagnostics).
+// all of their host code (constants, allocation, the isolation scheduler, launches, diagnostics).
 // Compiled with -Os (dynenv_amd/build.py; driving_host.h says why), linked with dynenv_capi.hip.
 #include <hip/hip_runtime.h>
 
 #include "driving_kernels.hip"
 #include "driving_partial.hip"
-#include "driving_reset_masked.hip"
+#include "driving_reset.hip"
 #include "dynenv_host.h"
 
 #define ISO_PROBE_EVERY 64     /* steps between two looks at the device's validation counter (an asynchronous 4-byte copy) */
@@ -196,26 +196,17 @@ struct HOST_LOCAL DrvHandle final : dynenv {
 
   void set_seed(uint64_t seed) override { cfg.seed = seed; S.seed = seed; }
 
-  int reset(float* obs, hipStream_t st) override {
-    hipLaunchKernelGGL(drv_reset_kernel, dim3((S.E + 63) / 64), dim3(64), 0, st, S);
-    if (obs && partial)
-      hipLaunchKernelGGL(drv_partial_obs_kernel, dim3(S.E), dim3(64), 0, st, S, (int)cfg.noise_type, cfg.noise_magnitude, obs);
-    else if (obs)
-      hipLaunchKernelGGL(drv_obs_kernel, dim3(S.E), dim3(64), 0, st, S, obs);
-    return launched();
-  }
-
   int reset_masked(const uint8_t* mask, float* obs, hipStream_t st) override {
     hipLaunchKernelGGL(drv_reset_masked_kernel, dim3(S.E), dim3(64), 0, st, S, mask);
     if (obs && partial)
-      hipLaunchKernelGGL(drv_partial_obs_masked_kernel, dim3(S.E), dim3(64), 0, st, S, mask, (int)cfg.noise_type, cfg.noise_magnitude, obs);
+      hipLaunchKernelGGL(drv_partial_obs_kernel, dim3(S.E), dim3(64), 0, st, S, mask, (int)cfg.noise_type, cfg.noise_magnitude, obs);
     else if (obs)
-      hipLaunchKernelGGL(drv_obs_masked_kernel, dim3(S.E), dim3(64), 0, st, S, mask, obs);
+      hipLaunchKernelGGL(drv_obs_kernel, dim3(S.E), dim3(64), 0, st, S, mask, obs);
     return launched();
   }
 
   int full_obs(float* full, hipStream_t st) override {
-    hipLaunchKernelGGL(drv_obs_kernel, dim3(S.E), dim3(64), 0, st, S, full);
+    hipLaunchKernelGGL(drv_obs_kernel, dim3(S.E), dim3(64), 0, st, S, (const uint8_t*)nullptr, full);
     return launched();
   }
   int global_state(float*, hipStream_t) override {
@@ -329,83 +320,14 @@ struct HOST_LOCAL DrvHandle final : dynenv {
     return m;
   }
 
-  int get_state(int32_t env, void* blob) override {
-    HIP_OK(hipDeviceSynchronize());
-    const size_t E = (size_t)S.E;
-    double body[BF_COUNT][DRV_NB], carx[CF_COUNT][16], obst[2][DRV_MAXO], epr[2][16];
-    int flags[DRV_NB], aux[DRV_NB], envi[EI_COUNT];
-    if (rows_d2h(&body[0][0], S.body, BF_COUNT, E, DRV_NB, env) || rows_d2h(&carx[0][0], S.carx, CF_COUNT, E, 16, env) ||
-        rows_d2h(&obst[0][0], S.obst, 2, E, DRV_MAXO, env) || rows_d2h(&epr[0][0], S.epr, 2, E, 16, env) ||
-        rows_d2h(flags, S.flags, 1, E, DRV_NB, env) || rows_d2h(aux, S.aux, 1, E, DRV_NB, env) || rows_d2h(envi, S.envi, 1, E, EI_COUNT, env))
-      return DYNENV_ERR_HIP;
-    dynenv_driving_state_t* st = (dynenv_driving_state_t*)blob;
-    memset(st, 0, sizeof(*st));
-    st->elapsed = envi[EI_ELAPSED]; st->all_finished = envi[EI_ALLFIN]; st->n_cars = S.A;
-    st->n_peds = envi[EI_NPED]; st->n_obst = envi[EI_NOBST]; st->episode = envi[EI_EPISODE];
-    for (int i = 0; i < DYNENV_MAX_CARS; ++i) { st->episode_r[i] = epr[0][i]; st->episode_pos_r[i] = epr[1][i]; }
-    for (int i = 0; i < S.A; ++i) {
-      dynenv_car_state_t& c = st->cars[i];
-      c.px = body[BF_PX][i]; c.py = body[BF_PY][i]; c.vx = body[BF_VX][i]; c.vy = body[BF_VY][i];
-      c.angle = body[BF_ANG][i]; c.w = body[BF_W][i];
-      c.dirx = carx[CF_DIRX][i]; c.diry = carx[CF_DIRY][i]; c.prevx = carx[CF_PREVX][i]; c.prevy = carx[CF_PREVY][i];
-      c.goalx = carx[CF_GOALX][i]; c.goaly = carx[CF_GOALY][i];
-      int f = flags[i];
-      c.type = f & 3; c.team = (f >> 2) & 3; c.finished = (f >> 4) & 1; c.crashed = (f >> 5) & 1;
-      c.fric = (f >> 6) & 1; c.lane_pos = (f >> 8) & 7;
-    }
-    for (int i = 0; i < st->n_peds; ++i) {
-      dynenv_ped_state_t& p = st->peds[i];
-      int l = DRV_SLOT_PED + i, f = flags[l];
-      p.px = body[BF_PX][l]; p.py = body[BF_PY][l]; p.vx = body[BF_VX][l]; p.vy = body[BF_VY][l];
-      p.road = f & 1; p.side = (f >> 1) & 1; p.dead = (f >> 2) & 1; p.crossing = (f >> 3) & 1;
-      p.begin_crossing = (f >> 4) & 1; p.speed = (f >> 8) & 15; p.moving = aux[l];
-    }
-    for (int i = 0; i < st->n_obst; ++i) { st->obst_x[i] = obst[0][i]; st->obst_y[i] = obst[1][i]; }
-    return DYNENV_OK;
-  }
-
-  int set_state(int32_t env, const void* blob) override {
-    const dynenv_driving_state_t* st = (const dynenv_driving_state_t*)blob;
-    if (st->n_cars != S.A || st->n_peds > DRV_MAXP || st->n_obst > DRV_MAXO || st->n_peds < 0 || st->n_obst < 0)
-      return fail(DYNENV_ERR_ARG, "state blob does not match this handle's layout");
-    HIP_OK(hipDeviceSynchronize());
-    const size_t E = (size_t)S.E;
-    double body[BF_COUNT][DRV_NB] = {}, carx[CF_COUNT][16] = {}, obst[2][DRV_MAXO] = {}, epr[2][16] = {};
-    int flags[DRV_NB] = {}, aux[DRV_NB] = {}, envi[EI_COUNT] = {};
-    for (int i = 0; i < S.A; ++i) {
-      const dynenv_car_state_t& c = st->cars[i];
-      body[BF_PX][i] = c.px; body[BF_PY][i] = c.py; body[BF_VX][i] = c.vx; body[BF_VY][i] = c.vy;
-      body[BF_ANG][i] = c.angle; body[BF_W][i] = c.w;
-      carx[CF_DIRX][i] = c.dirx; carx[CF_DIRY][i] = c.diry; carx[CF_PREVX][i] = c.prevx; carx[CF_PREVY][i] = c.prevy;
-      carx[CF_GOALX][i] = c.goalx; carx[CF_GOALY][i] = c.goaly;
-      flags[i] = CARF_PACK(c.type & 3, c.team & 3, c.finished & 1, c.crashed & 1, c.fric & 1, c.lane_pos & 7);
-    }
-    for (int i = 0; i < st->n_peds; ++i) {
-      const dynenv_ped_state_t& p = st->peds[i];
-      int l = DRV_SLOT_PED + i;
-      body[BF_PX][l] = p.px; body[BF_PY][l] = p.py; body[BF_VX][l] = p.vx; body[BF_VY][l] = p.vy;
-      flags[l] = PEDF_PACK(p.road & 1, p.side & 1, p.dead & 1, p.crossing & 1, p.begin_crossing & 1, p.speed & 15);
-      aux[l] = p.moving;
-    }
-    for (int i = 0; i < st->n_obst; ++i) { obst[0][i] = st->obst_x[i]; obst[1][i] = st->obst_y[i]; }
-    for (int i = 0; i < DYNENV_MAX_CARS; ++i) { epr[0][i] = st->episode_r[i]; epr[1][i] = st->episode_pos_r[i]; }
-    envi[EI_ELAPSED] = st->elapsed; envi[EI_ALLFIN] = st->all_finished; envi[EI_NPED] = st->n_peds;
-    envi[EI_NOBST] = st->n_obst; envi[EI_EPISODE] = st->episode; envi[EI_OCC] = 0; envi[EI_ERR] = 0;
-    if (rows_h2d(S.body, &body[0][0], BF_COUNT, E, DRV_NB, env) || rows_h2d(S.carx, &carx[0][0], CF_COUNT, E, 16, env) ||
-        rows_h2d(S.obst, &obst[0][0], 2, E, DRV_MAXO, env) || rows_h2d(S.epr, &epr[0][0], 2, E, 16, env) ||
-        rows_h2d(S.flags, flags, 1, E, DRV_NB, env) || rows_h2d(S.aux, aux, 1, E, DRV_NB, env) || rows_h2d(S.envi, envi, 1, E, EI_COUNT, env))
-      return DYNENV_ERR_HIP;
-    HIP_OK(hipMemset(S.lastcand + (size_t)env * 64, 0xFF, 64 * sizeof(int)));  // -1: quiescent shortcut state unknown
-    return DYNENV_OK;
-  }
-
-  // many environments in one launch, device memory on both sides (drv_get_states_kernel / drv_set_states_kernel: one wave per blob)
-  int get_states(const int32_t* idx, int32_t n, void* blobs, hipStream_t st) override {
-    hipLaunchKernelGGL(drv_get_states_kernel, dim3(n), dim3(64), 0, st, S, (const int*)idx, (unsigned long long*)blobs);
+  // one wave per blob (drv_get_states_kernel / drv_set_states_kernel)
+  int get_states(const int32_t* idx, int32_t first, int32_t n, void* blobs, hipStream_t st) override {
+    hipLaunchKernelGGL(drv_get_states_kernel, dim3(n), dim3(64), 0, st, S, (const int*)idx, (int)first, (unsigned long long*)blobs);
     return launched();
   }
-  int set_states(const int32_t* idx, int32_t n, const void* blobs, int32_t* status, hipStream_t st) override {
-    hipLaunchKernelGGL(drv_set_states_kernel, dim3(n), dim3(64), 0, st, S, (const int*)idx, (const unsigned long long*)blobs, (int*)status);
+  int set_states(const int32_t* idx, int32_t first, int32_t n, const void* blobs, int32_t* status, bool raise, hipStream_t st) override {
+    hipLaunchKernelGGL(drv_set_states_kernel, dim3(n), dim3(64), 0, st, S, (const int*)idx, (int)first, (const unsigned long long*)blobs, (int*)status,
+                       raise ? 1 : 0);
     return launched();
   }
   int error_flags_env(int32_t* flags, hipStream_t st) override {

@@ -50,7 +50,9 @@ int dynenv_create(const dynenv_cfg_t* cfg, dynenv_t** out) {
     return fail(DYNENV_ERR_UNSUPPORTED, "Image observations are out of scope");
   dynenv* h = cfg->env_type == DYNENV_ROBO_CUP ? new RcHandle() : drv_new_handle();
   h->cfg = *cfg;
-  if (int rc = h->init()) { dynenv_destroy(h); return rc; }
+  int rc = h->init();
+  if (!rc) rc = h->alloc(&h->stage, h->state_bytes / 8 + 1, SCRATCH);  // (scratch: the checkpoint is `allocs`, in init()'s order)
+  if (rc) { dynenv_destroy(h); return rc; }
   *out = h;
   return DYNENV_OK;
 }
@@ -79,7 +81,7 @@ int dynenv_seed(dynenv_t* h, uint64_t seed) {
 int dynenv_reset(dynenv_t* h, float* obs_dev, void* stream) {
   if (!h) return fail(DYNENV_ERR_ARG, "null handle");
   ON_DEVICE(h);
-  return h->reset(obs_dev, (hipStream_t)stream);
+  return h->reset_masked(nullptr, obs_dev, (hipStream_t)stream);
 }
 
 int dynenv_reset_masked(dynenv_t* h, const uint8_t* mask_dev, float* obs_dev, void* stream) {
@@ -175,17 +177,29 @@ int dynenv_debug_placement(dynenv_t* h, uint32_t* out, int32_t n) {
   return h->debug_placement(out, n);
 }
 
+// ONE environment through host memory, synchronously: the state kernels for one blob in the handle's staging area, on the null stream
 int dynenv_get_state(dynenv_t* h, int32_t env, void* blob, size_t nbytes) {
   if (!h || !blob) return fail(DYNENV_ERR_ARG, "null argument");
   if (env < 0 || env >= h->cfg.num_envs || nbytes < h->state_bytes) return fail(DYNENV_ERR_ARG, "bad env index / size");
   ON_DEVICE(h);
-  return h->get_state(env, blob);
+  HIP_OK(hipDeviceSynchronize());
+  if (int rc = h->get_states(nullptr, env, 1, h->stage, nullptr)) return rc;
+  HIP_OK(hipMemcpy(blob, h->stage, h->state_bytes, hipMemcpyDeviceToHost));
+  return DYNENV_OK;
 }
+// A blob that does not fit is an error of this call, whose caller is told: nothing is written and no error bit is raised.
 int dynenv_set_state(dynenv_t* h, int32_t env, const void* blob, size_t nbytes) {
   if (!h || !blob) return fail(DYNENV_ERR_ARG, "null argument");
   if (env < 0 || env >= h->cfg.num_envs || nbytes < h->state_bytes) return fail(DYNENV_ERR_ARG, "bad env index / size");
   ON_DEVICE(h);
-  return h->set_state(env, blob);
+  HIP_OK(hipDeviceSynchronize());
+  int32_t* status_dev = (int32_t*)(h->stage + h->state_bytes / 8);
+  int32_t status = -1;
+  HIP_OK(hipMemcpy(h->stage, blob, h->state_bytes, hipMemcpyHostToDevice));
+  if (int rc = h->set_states(nullptr, env, 1, h->stage, status_dev, false, nullptr)) return rc;
+  HIP_OK(hipMemcpy(&status, status_dev, sizeof(status), hipMemcpyDeviceToHost));
+  if (status != 0) return fail(DYNENV_ERR_ARG, "state blob does not match this handle's layout");
+  return DYNENV_OK;
 }
 
 // the batched, device-side forms: ordered on `stream`, no host synchronisation, no allocation, no host copy
@@ -200,13 +214,13 @@ int dynenv_get_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, void* 
   if (int rc = states_args(h, env_idx_dev, n, blobs_dev)) return rc;
   if (n == 0) return DYNENV_OK;
   ON_DEVICE(h);
-  return h->get_states(env_idx_dev, n, blobs_dev, (hipStream_t)stream);
+  return h->get_states(env_idx_dev, 0, n, blobs_dev, (hipStream_t)stream);
 }
 int dynenv_set_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const void* blobs_dev, int32_t* status_dev, void* stream) {
   if (int rc = states_args(h, env_idx_dev, n, blobs_dev)) return rc;
   if (n == 0) return DYNENV_OK;
   ON_DEVICE(h);
-  return h->set_states(env_idx_dev, n, blobs_dev, status_dev, (hipStream_t)stream);
+  return h->set_states(env_idx_dev, 0, n, blobs_dev, status_dev, true, (hipStream_t)stream);
 }
 int dynenv_error_flags_env(dynenv_t* h, int32_t* flags_dev, void* stream) {
   if (!h || !flags_dev) return fail(DYNENV_ERR_ARG, "null argument");
@@ -452,4 +466,4 @@ int dynenv_checkpoint_load(dynenv_t* h, const void* buf_host, size_t nbytes) {
 }  // extern "C"
 
 // device code only, behind everything above: no kernel a step launches moves (rc_layout_pad, robocup_kernels.hip)
-#include "robocup_reset_masked.hip"
+#include "robocup_reset.hip"

@@ -44,7 +44,10 @@ struct HOST_LOCAL dynenv {
   size_t state_bytes = 0;            // size of the canonical per-environment blob of dynenv_get_state / dynenv_set_state
   std::vector<void*> allocs;
   std::vector<size_t> alloc_bytes;  // checkpoint = these arrays, in allocation order
-  std::vector<void*> scratch;       // scheduling scratch (SIMD-isolation lists): NOT simulation state, never checkpointed
+  std::vector<void*> scratch;       // scheduling scratch (SIMD-isolation lists), `stage`: NOT simulation state, never checkpointed
+  // where dynenv_get_state / dynenv_set_state keep their one blob on the device: state_bytes, then the status word (dynenv_create;
+  // a handle is used by one thread at a time: dynenv.h)
+  unsigned long long* stage = nullptr;
   hipEvent_t ev_begin = nullptr, ev_main = nullptr, ev_end = nullptr;  // dynenv_set_step_events (caller-owned)
   // where the kernels keep the per-environment error word: err_array[env * err_stride + err_index] (err_array is one of `allocs`)
   const int* err_array = nullptr;
@@ -58,9 +61,8 @@ struct HOST_LOCAL dynenv {
   virtual int init() = 0;
   virtual void layout(dynenv_layout_t& L) const = 0;  // the block table and steps_per_episode
   virtual void set_seed(uint64_t seed) = 0;
-  virtual int reset(float* obs, hipStream_t st) = 0;
-  // exactly the environments e with mask[e] != 0 (device uint8 [E]), each as reset() leaves it; one wave per environment, no more
-  // launches than reset(), nothing but launches on `st` (capturable behind a captured step); the scheduler's scratch is not touched
+  // the reset: every environment (mask == nullptr: dynenv_reset) or exactly the environments e with mask[e] != 0 (device uint8 [E]); one
+  // wave per environment, nothing but launches on `st` (capturable behind a captured step); the scheduler's scratch is not touched
   virtual int reset_masked(const uint8_t* mask, float* obs, hipStream_t st) = 0;
   // records ev_begin in front of the step's dominant kernel and ev_main right behind it (step_begin / step_main_done)
   virtual int step(const int* actions, const double* head, float* obs, double* rewards, uint8_t* dones, hipStream_t st) = 0;
@@ -68,13 +70,12 @@ struct HOST_LOCAL dynenv {
   virtual int global_state(float* state, hipStream_t st) = 0;
   virtual int counts(int32_t* out, hipStream_t st) = 0;
   virtual int episode_stats(double* ep_r, double* ep_pos_r, double* ep_obs_r, int32_t* goals, hipStream_t st) = 0;
-  virtual int get_state(int32_t env, void* blob) = 0;        // (env and the blob's size are checked by the entry point)
-  virtual int set_state(int32_t env, const void* blob) = 0;
-  // the batched, device-side forms: n blobs state_bytes apart in device memory, one launch on `st`, no host synchronisation, allocation
-  // or copy.  idx (device, may be nullptr: environments 0..n-1) and n are checked by the entry point as far as the host can see them;
-  // the kernels skip an index outside [0, E).  status (may be nullptr): int32 [n] = 0 written, 1 blob rejected, 2 index out of range
-  virtual int get_states(const int32_t* idx, int32_t n, void* blobs, hipStream_t st) = 0;
-  virtual int set_states(const int32_t* idx, int32_t n, const void* blobs, int32_t* status, hipStream_t st) = 0;
+  // state transfer: n blobs state_bytes apart in device memory, one launch on `st`, no host synchronisation, allocation or copy.
+  // idx (device; nullptr: environments first..first + n - 1) and n are checked by the entry point as far as the host can see them; the
+  // kernels skip an index outside [0, E).  status (may be nullptr): int32 [n] = 0 written, 1 blob rejected, 2 index out of range;
+  // raise: a rejected blob also raises error bit 6 on its environment.  dynenv_get_state / dynenv_set_state are these for n = 1.
+  virtual int get_states(const int32_t* idx, int32_t first, int32_t n, void* blobs, hipStream_t st) = 0;
+  virtual int set_states(const int32_t* idx, int32_t first, int32_t n, const void* blobs, int32_t* status, bool raise, hipStream_t st) = 0;
   virtual int error_flags_env(int32_t* flags, hipStream_t st) = 0;  // int32 [E]: every environment's error word
   virtual int debug_counters(int64_t* out16) = 0;
   virtual int debug_placement(uint32_t*, int32_t) { return 0; }  // (Driving's SIMD isolation only: 0 words recorded)
@@ -105,20 +106,6 @@ static inline int row_blocks(dynenv_layout_t* L, int n, const int* rows, const i
     w += rows[i] * feat[i];
   }
   return w;
-}
-
-// one environment's rows of a field-major device array [nfields][E][width] <-> host [nfields][width]
-template <typename T>
-static int rows_d2h(T* dst, const T* src, size_t nfields, size_t E, size_t width, int env) {
-  for (size_t f = 0; f < nfields; ++f)
-    HIP_OK(hipMemcpy(dst + f * width, src + f * E * width + (size_t)env * width, sizeof(T) * width, hipMemcpyDeviceToHost));
-  return 0;
-}
-template <typename T>
-static int rows_h2d(T* dst, const T* src, size_t nfields, size_t E, size_t width, int env) {
-  for (size_t f = 0; f < nfields; ++f)
-    HIP_OK(hipMemcpy(dst + f * E * width + (size_t)env * width, src + f * width, sizeof(T) * width, hipMemcpyHostToDevice));
-  return 0;
 }
 
 // -DDRV_PROFILE builds: a profile symbol of N counters, `cols` per row -> <name>.txt in the directory DYNENV_PROFILE_DIR names (the profile

@@ -1,5 +1,5 @@
-// robocup_host.hip - the RoboCup handle: all host code of the RoboCup kernels (constant and scene tables, the pair table, launches, state
-// blobs, profile dumps).  Included by dynenv_capi.hip behind robocup_kernels.hip: it stays part of that translation unit, whose code
+// robocup_host.hip - the RoboCup handle: all host code of the RoboCup kernels (constant and scene tables, the pair table, launches,
+// profile dumps).  Included by dynenv_capi.hip behind robocup_kernels.hip: it stays part of that translation unit, whose code
 // layout the RoboCup launch time is sensitive to (RC_LAYOUT_PAD_WORDS, tools/rc_layout_sweep.py).
 static double moment_for_segment_host(double m, V2 a, V2 b, double r) {  // cpMomentForSegment
   V2 offset = vlerp(a, b, 0.5);
@@ -14,10 +14,10 @@ static int rc_full_row(int R, dynenv_layout_t* L = nullptr) {
   return row_blocks(L, 3, rows, feat);
 }
 
-// the kernels of robocup_reset_masked.hip, which dynenv_capi.hip includes last (behind everything the step launches run)
+// the kernels of robocup_reset.hip, which dynenv_capi.hip includes last (behind everything the step launches run)
 extern "C" __global__ void rc_reset_masked_kernel(RcState S, const uint8_t* __restrict__ mask);
-extern "C" __global__ void rc_obs_masked_kernel(RcState S, const uint8_t* __restrict__ mask, float* __restrict__ obs);
-extern "C" __global__ void rc_partial_obs_masked_kernel(RcState S, const uint8_t* __restrict__ mask, float* __restrict__ obs);
+extern "C" __global__ void rc_obs_kernel(RcState S, const uint8_t* __restrict__ mask, float* __restrict__ obs, int fullOnce);
+extern "C" __global__ void rc_partial_obs_kernel(RcState S, const uint8_t* __restrict__ mask, float* __restrict__ obs);
 
 struct HOST_LOCAL RcHandle final : dynenv {
   RcState R;
@@ -136,28 +136,18 @@ struct HOST_LOCAL RcHandle final : dynenv {
 
   void set_seed(uint64_t seed) override { cfg.seed = seed; R.seed = seed; }
 
-  int reset(float* obs, hipStream_t st) override {
-    hipLaunchKernelGGL(rc_reset_kernel, dim3((R.E + 63) / 64), dim3(64), 0, st, R);
-    if (obs) {
-      hipLaunchKernelGGL(rc_obs_kernel, dim3(R.E), dim3(64), 0, st, R, obs, 0);
-      if (R.obs_type == DYNENV_OBS_PARTIAL)
-        hipLaunchKernelGGL(rc_partial_obs_kernel, dim3(R.E), dim3(64), 0, st, R, obs, (double*)nullptr);
-    }
-    return launched();
-  }
-
   int reset_masked(const uint8_t* mask, float* obs, hipStream_t st) override {
     hipLaunchKernelGGL(rc_reset_masked_kernel, dim3(R.E), dim3(64), 0, st, R, mask);
     if (obs) {
-      hipLaunchKernelGGL(rc_obs_masked_kernel, dim3(R.E), dim3(64), 0, st, R, mask, obs);
+      hipLaunchKernelGGL(rc_obs_kernel, dim3(R.E), dim3(64), 0, st, R, mask, obs, 0);
       if (R.obs_type == DYNENV_OBS_PARTIAL)
-        hipLaunchKernelGGL(rc_partial_obs_masked_kernel, dim3(R.E), dim3(64), 0, st, R, mask, obs);
+        hipLaunchKernelGGL(rc_partial_obs_kernel, dim3(R.E), dim3(64), 0, st, R, mask, obs);
     }
     return launched();
   }
 
   int full_obs(float* full, hipStream_t st) override {
-    hipLaunchKernelGGL(rc_obs_kernel, dim3(R.E), dim3(64), 0, st, R, full, 1);
+    hipLaunchKernelGGL(rc_obs_kernel, dim3(R.E), dim3(64), 0, st, R, (const uint8_t*)nullptr, full, 1);
     return launched();
   }
   int global_state(float* state, hipStream_t st) override {
@@ -201,106 +191,14 @@ struct HOST_LOCAL RcHandle final : dynenv {
     return DYNENV_OK;
   }
 
-  int get_state(int32_t env, void* blob) override {
-    HIP_OK(hipDeviceSynchronize());
-    const size_t E = (size_t)R.E;
-    static thread_local double body[RB_COUNT + 4][RC_NB], rob[RR_COUNT][16], envd[RD_COUNT], epr[2][16];
-    static thread_local int robi[RI_COUNT][16], envi[RE_COUNT];
-    if (rows_d2h(&body[0][0], R.body, RB_COUNT + 4, E, RC_NB, env) || rows_d2h(&rob[0][0], R.rob, RR_COUNT, E, 16, env) ||
-        rows_d2h(&robi[0][0], R.robi, RI_COUNT, E, 16, env) || rows_d2h(&epr[0][0], R.epr, 2, E, 16, env))
-      return DYNENV_ERR_HIP;
-    HIP_OK(hipMemcpy(envi, R.envi + (size_t)env * RE_COUNT, sizeof(envi), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(envd, R.envd + (size_t)env * RD_COUNT, sizeof(envd), hipMemcpyDeviceToHost));
-    dynenv_robocup_state_t* st = (dynenv_robocup_state_t*)blob;
-    memset(st, 0, sizeof(*st));
-    st->elapsed = envi[RE_ELAPSED]; st->n_robots = R.R; st->ball_owned = envi[RE_OWNED]; st->n_last_kicked = envi[RE_NLK];
-    for (int i = 0; i < 4; ++i) st->last_kicked[i] = i < envi[RE_NLK] ? envi[RE_LK0 + i] : 0;
-    st->goals[0] = envi[RE_GOAL0]; st->goals[1] = envi[RE_GOAL1]; st->closest[0] = envi[RE_CLOSE0]; st->closest[1] = envi[RE_CLOSE1];
-    for (int t = 0; t < 2; ++t) {  // defenders are a set on the device: reported in ascending id order
-      int n = 0;
-      for (int i = 0; i < DYNENV_MAX_ROBOTS; ++i) if (envi[RE_DEF0 + t] & (1 << i)) st->defenders[t][n++] = i;
-      st->n_def[t] = n;
-      st->penal_times[t] = envd[RD_PT0 + t];
-    }
-    st->episode = envi[RE_EPISODE];
-    st->ball_free_cntr = envd[RD_FREECNT]; st->grace_period = envd[RD_GRACE];
-    st->bpx = body[RB_PX][RC_BALL]; st->bpy = body[RB_PY][RC_BALL]; st->bvx = body[RB_VX][RC_BALL]; st->bvy = body[RB_VY][RC_BALL];
-    st->bw = body[RB_W][RC_BALL]; st->bprevx = envd[RD_BPREVX]; st->bprevy = envd[RD_BPREVY];
-    for (int i = 0; i < DYNENV_MAX_ROBOTS; ++i) { st->episode_r[i] = epr[0][i]; st->episode_pos_r[i] = epr[1][i]; }
-    for (int i = 0; i < R.R; ++i) {
-      dynenv_robot_state_t& s = st->robots[i];
-      const int l = 2 * i, r = 2 * i + 1, f = robi[RI_FLAGS][i];
-      s.lpx = body[RB_PX][l]; s.lpy = body[RB_PY][l]; s.lvx = body[RB_VX][l]; s.lvy = body[RB_VY][l]; s.la = body[RB_ANG][l]; s.lw = body[RB_W][l];
-      s.rpx = body[RB_PX][r]; s.rpy = body[RB_PY][r]; s.rvx = body[RB_VX][r]; s.rvy = body[RB_VY][r]; s.ra = body[RB_ANG][r]; s.rw = body[RB_W][r];
-      s.head_angle = rob[RR_HEAD][i]; s.head_moving = rob[RR_HEADMOV][i]; s.prevx = rob[RR_PREVX][i]; s.prevy = rob[RR_PREVY][i];
-      s.initx = rob[RR_INITX][i]; s.inity = rob[RR_INITY][i]; s.penal_time = rob[RR_PENALT][i]; s.fall_time = rob[RR_FALLT][i];
-      s.move_time = rob[RR_MOVET][i];
-      s.team = (f & RF_TEAMPOS) ? 1 : -1; s.penalized = !!(f & RF_PENAL); s.touching = !!(f & RF_TOUCH); s.might_push = !!(f & RF_PUSH);
-      s.fallen = !!(f & RF_FALLEN); s.kicking = !!(f & RF_KICK); s.foot = !!(f & RF_FOOT); s.joint_removed = !!(f & RF_JREM);
-      s.touch_cntr = robi[RI_TOUCHC][i]; s.fall_cntr = robi[RI_FALLC][i];
-    }
-    return DYNENV_OK;
-  }
-
-  int set_state(int32_t env, const void* blob) override {
-    const dynenv_robocup_state_t* st = (const dynenv_robocup_state_t*)blob;
-    if (st->n_robots != R.R) return fail(DYNENV_ERR_ARG, "state blob does not match this handle's layout");
-    HIP_OK(hipDeviceSynchronize());
-    const size_t E = (size_t)R.E;
-    static thread_local double body[RB_COUNT + 4][RC_NB], rob[RR_COUNT][16], envd[RD_COUNT], epr[2][16];
-    static thread_local int robi[RI_COUNT][16], envi[RE_COUNT];
-    memset(body, 0, sizeof(body)); memset(rob, 0, sizeof(rob)); memset(envd, 0, sizeof(envd)); memset(epr, 0, sizeof(epr));
-    memset(robi, 0, sizeof(robi)); memset(envi, 0, sizeof(envi));
-    int ncon = 0;
-    for (int i = 0; i < R.R; ++i) {
-      const dynenv_robot_state_t& s = st->robots[i];
-      const int l = 2 * i, r = 2 * i + 1;
-      body[RB_PX][l] = s.lpx; body[RB_PY][l] = s.lpy; body[RB_VX][l] = s.lvx; body[RB_VY][l] = s.lvy; body[RB_ANG][l] = s.la; body[RB_W][l] = s.lw;
-      body[RB_PX][r] = s.rpx; body[RB_PY][r] = s.rpy; body[RB_VX][r] = s.rvx; body[RB_VY][r] = s.rvy; body[RB_ANG][r] = s.ra; body[RB_W][r] = s.rw;
-      for (int k = 0; k < 2; ++k) {  // shape cache = geometry at cpSpaceAddShape time
-        const int b = 2 * i + k;
-        double sn, cs;
-        dm_sincos(body[RB_ANG][b], &sn, &cs);
-        body[RB_COUNT + 0][b] = body[RB_PX][b]; body[RB_COUNT + 1][b] = body[RB_PY][b]; body[RB_COUNT + 2][b] = cs; body[RB_COUNT + 3][b] = sn;
-      }
-      rob[RR_HEAD][i] = s.head_angle; rob[RR_HEADMOV][i] = s.head_moving; rob[RR_PREVX][i] = s.prevx; rob[RR_PREVY][i] = s.prevy;
-      rob[RR_INITX][i] = s.initx; rob[RR_INITY][i] = s.inity; rob[RR_PENALT][i] = s.penal_time; rob[RR_FALLT][i] = s.fall_time;
-      rob[RR_MOVET][i] = s.move_time;
-      int f = (s.team > 0 ? RF_TEAMPOS : 0) | (s.penalized ? RF_PENAL : 0) | (s.touching ? RF_TOUCH : 0) | (s.might_push ? RF_PUSH : 0) |
-              (s.fallen ? RF_FALLEN : 0) | (s.kicking ? RF_KICK : 0) | (s.foot ? RF_FOOT : 0) | (s.joint_removed ? RF_JREM : 0);
-      robi[RI_FLAGS][i] = f; robi[RI_TOUCHC][i] = s.touch_cntr; robi[RI_FALLC][i] = s.fall_cntr;
-      if (!s.joint_removed) envi[RE_CORDER + ncon++] = 2 * i;
-      envi[RE_CORDER + ncon++] = 2 * i + 1;
-    }
-    body[RB_PX][RC_BALL] = st->bpx; body[RB_PY][RC_BALL] = st->bpy; body[RB_VX][RC_BALL] = st->bvx; body[RB_VY][RC_BALL] = st->bvy;
-    body[RB_W][RC_BALL] = st->bw; body[RB_COUNT + 0][RC_BALL] = st->bpx; body[RB_COUNT + 1][RC_BALL] = st->bpy; body[RB_COUNT + 2][RC_BALL] = 1.0;
-    envi[RE_ELAPSED] = st->elapsed; envi[RE_OWNED] = st->ball_owned; envi[RE_NLK] = st->n_last_kicked;
-    for (int i = 0; i < 4; ++i) envi[RE_LK0 + i] = st->last_kicked[i];
-    envi[RE_GOAL0] = st->goals[0]; envi[RE_GOAL1] = st->goals[1]; envi[RE_CLOSE0] = st->closest[0]; envi[RE_CLOSE1] = st->closest[1];
-    for (int t = 0; t < 2; ++t) {
-      int m = 0;
-      for (int i = 0; i < st->n_def[t]; ++i) m |= 1 << st->defenders[t][i];
-      envi[RE_DEF0 + t] = m;
-      envd[RD_PT0 + t] = st->penal_times[t];
-    }
-    envi[RE_NCON] = ncon; envi[RE_EPISODE] = st->episode; envi[RE_OCC] = 0; envi[RE_ERR] = 0;
-    envd[RD_FREECNT] = st->ball_free_cntr; envd[RD_GRACE] = st->grace_period; envd[RD_BPREVX] = st->bprevx; envd[RD_BPREVY] = st->bprevy;
-    for (int i = 0; i < DYNENV_MAX_ROBOTS; ++i) { epr[0][i] = st->episode_r[i]; epr[1][i] = st->episode_pos_r[i]; }
-    if (rows_h2d(R.body, &body[0][0], RB_COUNT + 4, E, RC_NB, env) || rows_h2d(R.rob, &rob[0][0], RR_COUNT, E, 16, env) ||
-        rows_h2d(R.robi, &robi[0][0], RI_COUNT, E, 16, env) || rows_h2d(R.epr, &epr[0][0], 2, E, 16, env))
-      return DYNENV_ERR_HIP;
-    HIP_OK(hipMemcpy(R.envi + (size_t)env * RE_COUNT, envi, sizeof(envi), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(R.envd + (size_t)env * RD_COUNT, envd, sizeof(envd), hipMemcpyHostToDevice));
-    return DYNENV_OK;
-  }
-
-  // many environments in one launch, device memory on both sides (rc_get_states_kernel / rc_set_states_kernel: one wave per blob)
-  int get_states(const int32_t* idx, int32_t n, void* blobs, hipStream_t st) override {
-    hipLaunchKernelGGL(rc_get_states_kernel, dim3(n), dim3(64), 0, st, R, (const int*)idx, (unsigned long long*)blobs);
+  // one wave per blob (rc_get_states_kernel / rc_set_states_kernel)
+  int get_states(const int32_t* idx, int32_t first, int32_t n, void* blobs, hipStream_t st) override {
+    hipLaunchKernelGGL(rc_get_states_kernel, dim3(n), dim3(64), 0, st, R, (const int*)idx, (int)first, (unsigned long long*)blobs);
     return launched();
   }
-  int set_states(const int32_t* idx, int32_t n, const void* blobs, int32_t* status, hipStream_t st) override {
-    hipLaunchKernelGGL(rc_set_states_kernel, dim3(n), dim3(64), 0, st, R, (const int*)idx, (const unsigned long long*)blobs, (int*)status);
+  int set_states(const int32_t* idx, int32_t first, int32_t n, const void* blobs, int32_t* status, bool raise, hipStream_t st) override {
+    hipLaunchKernelGGL(rc_set_states_kernel, dim3(n), dim3(64), 0, st, R, (const int*)idx, (int)first, (const unsigned long long*)blobs, (int*)status,
+                       raise ? 1 : 0);
     return launched();
   }
   int error_flags_env(int32_t* flags, hipStream_t st) override {

@@ -2127,34 +2127,6 @@ rc_step_partial_kernel(RcState S, const int* __restrict__ actions, const double*
   rc_step_body<true, 1>(S, (int)blockIdx.x, actions, headActions, obs, rewards, dones);
 }
 
-// fullOnce = 0: the observation tensor after a reset (nTimeSteps rows per environment, the configured observation type);
-// fullOnce = 1: ONE noise-free Full observation of the current state [E, A, 66], whatever the observation type - what
-// info['Full State'] / info['Recon States'] are made of (RoboCupEnvironment.py:511-512), dynenv_full_obs
-extern "C" __global__ void __launch_bounds__(64) rc_obs_kernel(RcState S, float* __restrict__ obs, int fullOnce) {
-  RcLds& L = g_R;
-  const int e = blockIdx.x, lane = threadIdx.x;
-  rc_load_env(S, L, e, lane, 0ull);
-  __syncthreads();
-  if (fullOnce) {
-    rc_write_obs_ool(lane, S.R, 4 + 8 + (S.R - 1) * 6, obs + (size_t)e * S.R * (4 + 8 + (S.R - 1) * 6));
-    return;
-  }
-  if (S.obs_type == DYNENV_OBS_PARTIAL) {
-    // environment_base.py:217-222: nTimeSteps separate getAgentVision calls on the initial state, each with fresh noise
-    // (draw keys: time word = t); rc_partial_obs_kernel follows on the same stream
-    for (int t = 0; t < 5; ++t) {
-      RvSnap& sn = S.snap[(size_t)e * 5 + t];
-      if (lane < 21) { sn.px[lane] = L.px[lane]; sn.py[lane] = L.py[lane]; }
-      if (lane < 20) sn.ang[lane] = L.ang[lane];
-      if (lane < 10) { sn.head[lane] = L.head[lane]; sn.rflags[lane] = L.rflags[lane]; }
-      if (lane == 0) { sn.owned = L.envi[RE_OWNED]; sn.close0 = L.envi[RE_CLOSE0]; sn.close1 = L.envi[RE_CLOSE1]; sn.tkey = t; }
-    }
-    return;
-  }
-  for (int t = 0; t < 5; ++t)  // environment_base.py:217-222: nTimeSteps copies of the initial observation
-    rc_write_obs_ool(lane, S.R, S.obs_dim, obs + ((size_t)e * 5 + t) * S.R * S.obs_dim);
-}
-
 // getFullState(agent=None) (RoboCupEnvironment.py:1149-1161), what step() stores as info['Full State'] (:511): per environment
 // robots [R][6] = (normalize(x, standardNorm, 0), normalize(y, ...), cos a, sin a, team, fallen | penalized) in FIELD coordinates
 // (no team flip, a different normalisation from the per-agent rows: ((pt * nf) - 0) * 2, cutils.py:318-323), then the ball
@@ -2184,116 +2156,6 @@ extern "C" __global__ void __launch_bounds__(64) rc_global_state_kernel(RcState 
   o[r * 6 + 5] = (f & (RF_FALLEN | RF_PENAL)) ? 1.0f : 0.0f;
 }
 
-// ------------------------------------------------------------------------------------------------
-// reset: one thread per environment (RoboCupEnvironment.__init__ + _setup_scene :73-99, :239-336; both randomInit modes)
-// ------------------------------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(64) rc_reset_kernel(RcState S) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= S.E) return;
-  const size_t E = (size_t)S.E;
-  int* envi = S.envi + (size_t)e * RE_COUNT;
-  double* envd = S.envd + (size_t)e * RD_COUNT;
-  const uint32_t ep = (uint32_t)envi[RE_EPISODE];
-  const uint32_t genv = (uint32_t)(S.env_id_offset + e);
-  for (int k = 0; k < RC_NB; ++k)
-    for (int f = 0; f < RB_COUNT + 4; ++f) S.body[(size_t)f * E * RC_NB + (size_t)e * RC_NB + k] = (f == RB_COUNT + 2) ? 1.0 : 0.0;
-  for (int k = 0; k < 16; ++k) {
-    for (int f = 0; f < RR_COUNT; ++f) S.rob[(size_t)f * E * 16 + (size_t)e * 16 + k] = 0.0;
-    for (int f = 0; f < RI_COUNT; ++f) S.robi[(size_t)f * E * 16 + (size_t)e * 16 + k] = 0;
-    S.epr[(size_t)e * 16 + k] = 0.0; S.epr[E * 16 + (size_t)e * 16 + k] = 0.0; S.epo[(size_t)e * 16 + k] = 0.0;
-  }
-  for (int k = 0; k < RC_NS; ++k) { S.s_pair[(size_t)e * RC_NS + k] = 0xFFFF; S.s_meta[(size_t)e * RC_NS + k] = 0; }
-  double rnd[24];
-  for (int i = 0; i < 24; ++i) rnd[i] = dm_unit(dm_env_rng(S.seed, genv, ep, DM_RNG_ROBO_RESET, (uint32_t)i, 0).v[0]);
-  const double centX = RC_W / 2.0;
-  const bool randomInit = (S.flags & DYNENV_FLAG_RANDOM_INIT) != 0, detTurn = (S.flags & DYNENV_FLAG_DETERMINISTIC_TURN) != 0;
-  V2 spots[2][5];  // _create_robot_spots :275-293
-  V2 ballPos = v2(520.0, 370.0);  // W // 2, H // 2
-  int owned = 1;
-  if (randomInit) {
-    // :241-272: one random spot in each of 10 field cells (20 random.random() draws in source order); the goal-side cells go
-    // to the two teams, np.random.permutation(8) deals the 8 middle ones
-    const double xL[7] = {RC_SIDE + 10.0, RC_SIDE + 50.0, RC_SIDE + 250.0, RC_SIDE + 450.0, RC_SIDE + 650.0, RC_SIDE + 850.0, RC_SIDE + 890.0};
-    const double yL[3] = {RC_SIDE + 20.0, RC_SIDE + 300.0, RC_SIDE + 580.0};
-    V2 rs[10];
-    int k = 0, d = 0;
-    for (int i = 0; i < 6; ++i) {
-      const bool edge = i == 0 || i == 5;
-      for (int j = 0; j < (edge ? 1 : 2); ++j) {
-        const double yBeg = edge ? yL[0] : yL[j], yEnd = edge ? yL[2] : yL[j + 1];
-        const double x = xL[i] + rnd[d] * (xL[i + 1] - xL[i]);
-        const double y = yBeg + rnd[d + 1] * (yEnd - yBeg);
-        d += 2;
-        rs[k++] = v2(x, y);
-      }
-    }
-    int perm8[8];
-    for (int i = 0; i < 8; ++i) perm8[i] = i;
-    for (int i = 0; i < 7; ++i) {
-      dm_u32x4 u = dm_env_rng(S.seed, genv, ep, DM_RNG_ROBO_RESET, (uint32_t)(48 + i), 0);
-      int j = i + dm_randint(u.v[0], 0, 7 - i);
-      int tmp = perm8[i]; perm8[i] = perm8[j]; perm8[j] = tmp;
-    }
-    int cnt[2] = {1, 1};
-    spots[0][0] = rs[0]; spots[1][0] = rs[9];
-    for (int i = 0; i < 8; ++i) { const int t = i < 4 ? 0 : 1; spots[t][cnt[t]++] = rs[perm8[i] + 1]; }
-    // _create_ball :325-331
-    ballPos = v2(rnd[20] * 900.0 + RC_SIDE, rnd[21] * 600.0 + RC_SIDE);
-    owned = rnd[22] > 0.4 ? 1 : 0;
-    if (owned != 0 && rnd[23] > 0.5) owned *= -1;
-  } else {
-  spots[0][0] = v2(centX - (5.0 * 2.0 + ROBOT_TOTAL_RADIUS) - rnd[0] * 50.0, RC_H / 2.0 + (rnd[1] - 0.5) * 25.0);
-  spots[0][1] = v2(centX - (ROBOT_TOTAL_RADIUS + 5.0 * 2.0) - rnd[2] * 50.0, RC_SIDE + 600.0 / 4.0 + (rnd[3] - 0.5) * 50.0);
-  spots[0][2] = v2(centX - (ROBOT_TOTAL_RADIUS + 5.0 * 2.0) - rnd[4] * 50.0, RC_SIDE + 3.0 * 600.0 / 4.0 + (rnd[5] - 0.5) * 50.0);
-  spots[0][3] = v2(centX - (900.0 / 4.0) - (rnd[6] - 0.5) * 50.0, RC_SIDE + 600.0 / 2.0 + (rnd[7] - 0.5) * 50.0);
-  spots[0][4] = v2(RC_SIDE + 20.0, RC_H / 2.0 + (rnd[8] - 0.5) * 50.0);
-  spots[1][0] = v2(centX + (75.0 * 2.0 + ROBOT_TOTAL_RADIUS + 5.0 / 2.0) + rnd[9] * 50.0, RC_H / 2.0 + (rnd[10] - 0.5) * 50.0);
-  spots[1][1] = v2(centX + (ROBOT_TOTAL_RADIUS + 5.0 / 2.0 + 75.0) + rnd[11] * 50.0, RC_SIDE + 600.0 / 4.0 + (rnd[12] - 0.5) * 50.0);
-  spots[1][2] = v2(centX + (ROBOT_TOTAL_RADIUS + 5.0 / 2.0 + 75.0) + rnd[13] * 50.0, RC_SIDE + 3.0 * 600.0 / 4.0 + (rnd[14] - 0.5) * 50.0);
-  spots[1][3] = v2(centX + (RC_SIDE + 900.0 / 4.0) + rnd[15] * 50.0, RC_SIDE + 600.0 / 2.0 + (rnd[16] - 0.5) * 50.0);
-  spots[1][4] = v2(RC_W - (RC_SIDE + 20.0), RC_H / 2.0 + (rnd[17] - 0.5) * 50.0);
-  }
-  int perm[2][5];
-  for (int t = 0; t < 2; ++t) {
-    for (int i = 0; i < 5; ++i) perm[t][i] = i;
-    for (int i = 0; i < 4; ++i) {
-      dm_u32x4 u = dm_env_rng(S.seed, genv, ep, DM_RNG_ROBO_RESET, (uint32_t)(32 + t * 8 + i), 0);
-      int j = i + dm_randint(u.v[0], 0, 4 - i);
-      int tmp = perm[t][i]; perm[t][i] = perm[t][j]; perm[t][j] = tmp;
-    }
-  }
-  for (int id = 0; id < S.R; ++id) {
-    const int team = id < S.n ? 1 : -1;
-    const V2 pos = id < S.n ? spots[0][perm[0][id]] : spots[1][perm[1][id - S.n]];
-    const double angle = team > 0 ? 0.0 : DM_PI;
-    double sn, cs;
-    dm_sincos(angle, &sn, &cs);
-    for (int k = 0; k < 2; ++k) {
-      size_t b = (size_t)e * RC_NB + 2 * id + k;
-      S.body[RB_PX * E * RC_NB + b] = pos.x; S.body[RB_PY * E * RC_NB + b] = pos.y; S.body[RB_ANG * E * RC_NB + b] = angle;
-      S.body[(RB_COUNT + 0) * E * RC_NB + b] = pos.x; S.body[(RB_COUNT + 1) * E * RC_NB + b] = pos.y;
-      S.body[(RB_COUNT + 2) * E * RC_NB + b] = cs; S.body[(RB_COUNT + 3) * E * RC_NB + b] = sn;
-    }
-    size_t r = (size_t)e * 16 + id;
-    // prevPos = getPos() = (p + p) / 2
-    S.rob[RR_PREVX * E * 16 + r] = (pos.x + pos.x) / 2.0; S.rob[RR_PREVY * E * 16 + r] = (pos.y + pos.y) / 2.0;
-    S.robi[RI_FLAGS * E * 16 + r] = team > 0 ? RF_TEAMPOS : 0;
-    if (detTurn) S.rob[RR_HEAD * E * 16 + r] = (double)team * ROBOT_HEAD_MAX;  // :317-319
-  }
-  {
-    size_t b = (size_t)e * RC_NB + RC_BALL;
-    S.body[RB_PX * E * RC_NB + b] = ballPos.x; S.body[RB_PY * E * RC_NB + b] = ballPos.y;
-    S.body[(RB_COUNT + 0) * E * RC_NB + b] = ballPos.x; S.body[(RB_COUNT + 1) * E * RC_NB + b] = ballPos.y;
-  }
-  for (int k = 0; k < RE_COUNT; ++k) envi[k] = 0;
-  envi[RE_OWNED] = owned; envi[RE_EPISODE] = (int)(ep + 1);
-  envi[RE_NCON] = 2 * S.R;
-  for (int k = 0; k < 2 * S.R; ++k) envi[RE_CORDER + k] = k;  // add order: joint, rotJoint per robot (:321-323)
-  for (int k = 0; k < RD_COUNT; ++k) envd[k] = 0.0;
-  envd[RD_FREECNT] = 9999.0; envd[RD_GRACE] = 0.0; envd[RD_PT0] = 20000.0; envd[RD_PT1] = 20000.0;
-  envd[RD_BPREVX] = ballPos.x; envd[RD_BPREVY] = ballPos.y;
-}
-
 extern "C" __global__ void rc_stats_kernel(RcState S, double* ep_r, double* ep_pos_r, double* ep_obs_r, int* goals) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= S.E) return;
@@ -2313,7 +2175,8 @@ extern "C" __global__ void rc_stats_kernel(RcState S, double* ep_r, double* ep_p
 // that the step code keeps its addresses (rc_layout_pad above).  One wave per listed environment (grid n), lane = body slot (feet 2r,
 // 2r + 1 of robot r, the ball at RC_BALL) or robot.  The blob (2552 bytes: 8-byte aligned, not 16) travels between HBM and an LDS tile
 // as contiguous 8-byte words across the wave; the lanes read / write their robot's struct in LDS, and every access to the field-major
-// arrays is one whole row of the environment per instruction.  Same bytes as the per-environment host path of robocup_host.hip.
+// arrays is one whole row of the environment per instruction.  dynenv_get_state / dynenv_set_state are these kernels for one blob
+// (idx == nullptr, first = the environment) through a staging area in device memory.
 // ------------------------------------------------------------------------------------------------
 #define RC_BLOB_WORDS ((int)(sizeof(dynenv_robocup_state_t) / 8))
 static_assert(sizeof(dynenv_robocup_state_t) % 8 == 0, "the blob moves as 8-byte words");
@@ -2326,14 +2189,14 @@ union RcBlobTile {
 DE_DEV double* rc_blob_foot(dynenv_robot_state_t& r, int side) { return reinterpret_cast<double*>(&r) + 6 * side; }
 static_assert(offsetof(dynenv_robot_state_t, rpx) == 6 * sizeof(double) && offsetof(dynenv_robot_state_t, head_angle) == 12 * sizeof(double), "foot blocks");
 
-// idx == nullptr: environments 0..n-1.  An index outside [0, E) leaves its blob untouched.
+// idx == nullptr: environments first..first + n - 1.  An index outside [0, E) leaves its blob untouched.
 extern "C" __global__ void __launch_bounds__(64)
-rc_get_states_kernel(RcState S, const int* __restrict__ idx, unsigned long long* __restrict__ blobs) {
+rc_get_states_kernel(RcState S, const int* __restrict__ idx, int first, unsigned long long* __restrict__ blobs) {
   __shared__ RcBlobTile T;
   __shared__ int envi[64];
   __shared__ double envd[RD_COUNT];
   const int lane = threadIdx.x, k = blockIdx.x, R = S.R;
-  const int e = idx ? uniform_i(idx[k]) : k;
+  const int e = idx ? uniform_i(idx[k]) : first + k;
   if (e < 0 || e >= S.E) return;
   const size_t E = (size_t)S.E, row = (size_t)e * RC_NB, r16 = (size_t)e * 16;
   for (int q = lane; q < RC_BLOB_WORDS; q += 64) T.q[q] = 0ull;  // the pads and the slots of robots this handle does not have read 0
@@ -2386,13 +2249,15 @@ rc_get_states_kernel(RcState S, const int* __restrict__ idx, unsigned long long*
   for (int q = lane; q < RC_BLOB_WORDS; q += 64) out[q] = T.q[q];
 }
 
-// status (may be nullptr): 0 written, 1 blob rejected (error bit 6 raised on the environment, nothing else touched), 2 index outside [0, E)
+// status (may be nullptr): 0 written, 1 blob rejected (nothing of the environment touched but, if `raise`, error bit 6 raised on it: the
+// batched call has nobody to return an error to, the synchronous one has), 2 index outside [0, E).  This is THE test of a blob's fit.
 extern "C" __global__ void __launch_bounds__(64)
-rc_set_states_kernel(RcState S, const int* __restrict__ idx, const unsigned long long* __restrict__ blobs, int* __restrict__ status) {
+rc_set_states_kernel(RcState S, const int* __restrict__ idx, int first, const unsigned long long* __restrict__ blobs, int* __restrict__ status,
+                      int raise) {
   __shared__ RcBlobTile T;
   __shared__ int envi[64];
   const int lane = threadIdx.x, k = blockIdx.x, R = S.R;
-  const int e = idx ? uniform_i(idx[k]) : k;
+  const int e = idx ? uniform_i(idx[k]) : first + k;
   if (e < 0 || e >= S.E) { if (status && lane == 0) status[k] = 2; return; }
   const size_t E = (size_t)S.E, row = (size_t)e * RC_NB, r16 = (size_t)e * 16;
   const unsigned long long* in = blobs + (size_t)k * RC_BLOB_WORDS;
@@ -2408,7 +2273,7 @@ rc_set_states_kernel(RcState S, const int* __restrict__ idx, const unsigned long
       badId = i < (t ? nd1 : nd0) && (id < 0 || id >= DYNENV_MAX_ROBOTS);
     }
     if (bad || wave_ballot(badId) != 0ull) {
-      if (lane == 0) { atomicOr(&S.envi[(size_t)e * RE_COUNT + RE_ERR], 64); if (status) status[k] = 1; }
+      if (lane == 0) { if (raise) atomicOr(&S.envi[(size_t)e * RE_COUNT + RE_ERR], 64); if (status) status[k] = 1; }
       return;
     }
   }
@@ -2419,7 +2284,7 @@ rc_set_states_kernel(RcState S, const int* __restrict__ idx, const unsigned long
     if (lane < 2 * R) {
       const double* d = rc_blob_foot(T.st.robots[lane >> 1], lane & 1);
       b[RB_PX] = d[0]; b[RB_PY] = d[1]; b[RB_VX] = d[2]; b[RB_VY] = d[3]; b[RB_ANG] = d[4]; b[RB_W] = d[5];
-      const DevSC sc = dev_sincos_inl(b[RB_ANG]);  // shape cache = geometry at cpSpaceAddShape time; dm_sincos, as the host path
+      const DevSC sc = dev_sincos_inl(b[RB_ANG]);  // shape cache = geometry at cpSpaceAddShape time
       b[RB_COUNT + 0] = b[RB_PX]; b[RB_COUNT + 1] = b[RB_PY]; b[RB_COUNT + 2] = sc.c; b[RB_COUNT + 3] = sc.s;
     } else if (lane == RC_BALL) {
       b[RB_PX] = T.st.bpx; b[RB_PY] = T.st.bpy; b[RB_VX] = T.st.bvx; b[RB_VY] = T.st.bvy; b[RB_W] = T.st.bw;

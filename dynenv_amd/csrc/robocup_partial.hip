@@ -479,11 +479,7 @@ DE_DEV void rv_env(const RcState& S, RvLds& V, const int e, const int lane, floa
   if (ov && lane == 0) S.envi[(size_t)e * RE_COUNT + RE_ERR] |= 8;
   if (rewards) rv_finalize(S, V.seen, e, lane, rewards);
 }
-// stand-alone launch: after reset / set_state (rewards == nullptr)
-extern "C" __global__ void __launch_bounds__(64, 4)
-rc_partial_obs_kernel(RcState S, float* __restrict__ obs, double* __restrict__ rewards) {
-  rv_env(S, g_V, blockIdx.x, threadIdx.x, obs, rewards);
-}
+// (the stand-alone launch behind a reset, rewards == nullptr: rc_partial_obs_kernel, robocup_reset.hip)
 // Fused call at the end of rc_step_partial_kernel: the wave that has finished environment e's step turns its five snapshots
 // into observation rows right away, while the waves of the environments with contact work are still stepping (two thirds
 // of a RoboCup launch are such a tail).  The tile aliases the step kernel's LDS tile, which is no longer needed; the

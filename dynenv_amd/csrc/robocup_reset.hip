@@ -1,13 +1,19 @@
-// robocup_reset_masked.hip - dynenv_reset_masked for RoboCup: reset exactly the environments whose mask byte is set, one wave per
-// environment (grid E; a wave whose byte is 0 ends at once), and write their first observation.  Included at the very END of
-// dynenv_capi.hip, behind everything the step launches run (rc_layout_pad in robocup_kernels.hip pins their addresses).
+// robocup_reset.hip - the RoboCup reset (dynenv_reset, dynenv_reset_masked) and the stand-alone observation kernels: what runs when no
+// step does.  Included at the very END of dynenv_capi.hip, behind everything the step launches run (rc_layout_pad in
+// robocup_kernels.hip pins their addresses).
 //
-// rc_reset_masked_kernel leaves a listed environment byte for byte as rc_reset_kernel (one thread per environment, which stays)
-// would: the 24 + 7 + 8 draws of DM_RNG_ROBO_RESET are made on lanes 0..23, 24..30 and 32..39 in one Philox evaluation of the wave,
-// the three short Fisher-Yates loops (perm8 of randomInit, the two team permutations) are serial and run wave-uniformly on tables in
-// LDS, lane s < 10 evaluates spot s with rc_reset_kernel's expressions, and every access to the field-major arrays is one whole row
-// of the environment per instruction, as in rc_set_states_kernel.
-DE_DEV double rc_cell_x(int i) {  // xL of rc_reset_kernel's randomInit cells
+// rc_reset_masked_kernel: one wave per environment (grid E).  mask == nullptr resets every environment, otherwise exactly those whose
+// byte is set (a wave whose byte is 0 ends at once).  RoboCupEnvironment.__init__ + _setup_scene (:73-99, :239-336), both randomInit
+// modes: the 24 + 7 + 8 draws of DM_RNG_ROBO_RESET are made on lanes 0..23, 24..30 and 32..39 in one Philox evaluation of the wave, the
+// three short Fisher-Yates loops (perm8 of randomInit, the two team permutations) are serial and run wave-uniformly on tables in LDS,
+// lane s < 10 evaluates spot s, and every access to the field-major arrays is one whole row of the environment per instruction, as
+// in rc_set_states_kernel.
+// A reset WRITES: the body rows (shape cache included), the robot, robot-int and the three episode-reward rows whole, the contact
+// cache's pair and meta words (every slot free), the int row (ball owner, the next episode, the constraints in add order, everything
+// else - error word, cache occupancy, scores - 0) and the double row.
+// It LEAVES ALONE: the contact cache's hashes and impulses, the Partial snapshots (rc_obs_kernel below writes them) and
+// prew0.
+DE_DEV double rc_cell_x(int i) {  // xL of randomInit's field cells
   return i == 0 ? RC_SIDE + 10.0 : i == 1 ? RC_SIDE + 50.0 : i == 2 ? RC_SIDE + 250.0 : i == 3 ? RC_SIDE + 450.0 : i == 4 ? RC_SIDE + 650.0 :
          i == 5 ? RC_SIDE + 850.0 : RC_SIDE + 890.0;
 }
@@ -18,7 +24,7 @@ rc_reset_masked_kernel(RcState S, const uint8_t* __restrict__ mask) {
   __shared__ double rnd[24], spx[10], spy[10];
   __shared__ int perm8[8], perm[2][8];
   const int e = blockIdx.x, lane = threadIdx.x, R = S.R, n = S.n;
-  if (uniform_i(mask[e]) == 0) return;
+  if (mask && uniform_i(mask[e]) == 0) return;
   const size_t E = (size_t)S.E, row = (size_t)e * RC_NB, r16 = (size_t)e * 16;
   const uint32_t ep = (uint32_t)uniform_i(S.envi[(size_t)e * RE_COUNT + RE_EPISODE]);
   const uint32_t genv = (uint32_t)(S.env_id_offset + e);
@@ -128,16 +134,24 @@ rc_reset_masked_kernel(RcState S, const uint8_t* __restrict__ mask) {
                                           lane == RD_BPREVX ? ballPos.x : lane == RD_BPREVY ? ballPos.y : 0.0;
 }
 
-// the first observation of the listed environments: rc_obs_kernel (fullOnce = 0) / rc_partial_obs_kernel (rewards = nullptr) behind the
-// mask test, the same device functions
-extern "C" __global__ void __launch_bounds__(64) rc_obs_masked_kernel(RcState S, const uint8_t* __restrict__ mask, float* __restrict__ obs) {
+// The stand-alone observation kernels, one wave per environment (grid E), mask as above.
+// fullOnce = 0: the observation tensor after a reset (nTimeSteps rows per environment, the configured observation type);
+// fullOnce = 1: ONE noise-free Full observation of the current state [E, A, 66], whatever the observation type - what
+// info['Full State'] / info['Recon States'] are made of (RoboCupEnvironment.py:511-512), dynenv_full_obs
+extern "C" __global__ void __launch_bounds__(64)
+rc_obs_kernel(RcState S, const uint8_t* __restrict__ mask, float* __restrict__ obs, int fullOnce) {
   RcLds& L = g_R;
   const int e = blockIdx.x, lane = threadIdx.x;
-  if (uniform_i(mask[e]) == 0) return;
+  if (mask && uniform_i(mask[e]) == 0) return;
   rc_load_env(S, L, e, lane, 0ull);
   __syncthreads();
+  if (fullOnce) {
+    rc_write_obs_ool(lane, S.R, 4 + 8 + (S.R - 1) * 6, obs + (size_t)e * S.R * (4 + 8 + (S.R - 1) * 6));
+    return;
+  }
   if (S.obs_type == DYNENV_OBS_PARTIAL) {
-    // nTimeSteps separate getAgentVision calls on the initial state (draw keys: time word = t); rc_partial_obs_masked_kernel follows
+    // environment_base.py:217-222: nTimeSteps separate getAgentVision calls on the initial state, each with fresh noise
+    // (draw keys: time word = t); rc_partial_obs_kernel follows on the same stream
     for (int t = 0; t < 5; ++t) {
       RvSnap& sn = S.snap[(size_t)e * 5 + t];
       if (lane < 21) { sn.px[lane] = L.px[lane]; sn.py[lane] = L.py[lane]; }
@@ -147,12 +161,13 @@ extern "C" __global__ void __launch_bounds__(64) rc_obs_masked_kernel(RcState S,
     }
     return;
   }
-  for (int t = 0; t < 5; ++t)  // nTimeSteps copies of the initial observation
+  for (int t = 0; t < 5; ++t)  // environment_base.py:217-222: nTimeSteps copies of the initial observation
     rc_write_obs_ool(lane, S.R, S.obs_dim, obs + ((size_t)e * 5 + t) * S.R * S.obs_dim);
 }
 
+// Partial: the rows of the five snapshots rc_obs_kernel left; no processSeens rewards behind a reset (rewards == nullptr)
 extern "C" __global__ void __launch_bounds__(64, 4)
-rc_partial_obs_masked_kernel(RcState S, const uint8_t* __restrict__ mask, float* __restrict__ obs) {
-  if (uniform_i(mask[blockIdx.x]) == 0) return;
+rc_partial_obs_kernel(RcState S, const uint8_t* __restrict__ mask, float* __restrict__ obs) {
+  if (mask && uniform_i(mask[blockIdx.x]) == 0) return;
   rv_env(S, g_V, blockIdx.x, threadIdx.x, obs, nullptr);
 }

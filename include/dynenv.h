@@ -150,7 +150,8 @@ void dynenv_destroy(dynenv_t* h);
 int dynenv_layout(const dynenv_t* h, dynenv_layout_t* out);
 int dynenv_seed(dynenv_t* h, uint64_t seed);
 
-/* (Re)build every environment's scene and write the first observation(s): obs_dev float32 [E, T, A, obs_dim]. */
+/* (Re)build every environment's scene and write the first observation(s): obs_dev float32 [E, T, A, obs_dim].  The launches of
+ * dynenv_reset_masked without a mask. */
 int dynenv_reset(dynenv_t* h, float* obs_dev, void* stream);
 
 /* Reset exactly the environments e with mask_dev[e] != 0 (uint8 [E]; the dones_dev of the step before it is a valid mask).
@@ -162,7 +163,7 @@ int dynenv_reset(dynenv_t* h, float* obs_dev, void* stream);
  *   observation: T copies for Full, T separate noisy draws (time word t) for Partial.
  *   An UNLISTED environment: no byte of its state and no byte of obs_dev[e] changes.
  * Ordered on `stream`; no host synchronisation, no allocation, no host copy: capturable into a hipGraph behind a captured dynenv_step.
- * One wave per environment, no more launches than dynenv_reset; the scheduler's scratch (timing only) is not touched.
+ * One wave per environment, the launches of dynenv_reset; the scheduler's scratch (timing only) is not touched.
  * Errors: NULL handle or mask -> DYNENV_ERR_ARG. */
 int dynenv_reset_masked(dynenv_t* h, const uint8_t* mask_dev, float* obs_dev, void* stream);
 
@@ -217,7 +218,11 @@ int dynenv_counts(dynenv_t* h, int32_t* counts_dev, void* stream);
 int dynenv_episode_stats(dynenv_t* h, double* ep_r_dev, double* ep_pos_r_dev, double* ep_obs_r_dev,
                          int32_t* goals_dev, void* stream);
 
-/* Copy one environment's canonical state blob to / from HOST memory (synchronous; test + checkpoint path). */
+/* Copy one environment's canonical state blob to / from HOST memory (synchronous; test + checkpoint path): the device is synchronised,
+ * then ONE launch of the kernels behind dynenv_get_states / dynenv_set_states and one copy between host memory and a staging area of
+ * the handle (device memory that is no part of a checkpoint).  dynenv_set_state of a blob that does not fit the handle (the list at
+ * dynenv_set_states) returns DYNENV_ERR_ARG, writes nothing and - unlike the batched call, which has no caller to tell - raises no
+ * error bit. */
 size_t dynenv_state_size(const dynenv_t* h);
 int dynenv_get_state(dynenv_t* h, int32_t env_idx, void* host_blob, size_t nbytes);
 int dynenv_set_state(dynenv_t* h, int32_t env_idx, const void* host_blob, size_t nbytes);

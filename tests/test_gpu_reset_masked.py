@@ -5,7 +5,7 @@ env_id_offset=e, seed=...) IS environment e of a batch, and resetting that objec
 such object per environment ("per-env oracles").  Every comparison is bit for bit: int views of the tensors, or checkpoint() bytes.
 
 Configurations: those of tests/test_gpu_state_batch.py plus robocup5_random (randomInit + deterministicTurn: the other half of
-rc_reset_kernel).  Shapes: E = 1, E = 5 with the listed set {3, 0, 4}, E = 70 with every third environment plus 63 and 64 (both
+rc_reset_masked_kernel).  dynenv_reset is the same kernels with no mask; tests/test_gpu_state_digests.py pins what they write.  Shapes: E = 1, E = 5 with the listed set {3, 0, 4}, E = 70 with every third environment plus 63 and 64 (both
 sides of a 64 boundary).  "Pile" environments: capacity_scenes.drv_full_coupled / rc_chain written into environments 0 and 1 of the
 configurations that have the ten agents the scenes need, and stepped twice: they hold live contacts when they are reset."""
 import warnings

@@ -1,6 +1,7 @@
 """Batched, device-side state transfer (dynenv_get_states / dynenv_set_states / dynenv_error_flags_env; BatchedDynEnv.get_states,
-set_states, fork, error_flags_per_env).  Everything is compared bit for bit, against the per-environment host path (get_state /
-set_state), against whole checkpoints (every non-scratch device array of the handle) and against the CPU oracle.
+set_states, fork, error_flags_per_env).  Everything is compared bit for bit, against the per-environment calls (get_state / set_state:
+the same kernels for ONE blob, through host memory), against whole checkpoints (every non-scratch device array of the handle) and
+against the CPU oracle.  What the per-environment calls themselves produce is pinned by tests/test_gpu_state_digests.py.
 
 Shapes: Driving with 10 cars and with 2 (car slots left empty), RoboCup with 5 and with 1 robot per team, one Partial + Realistic handle per
 environment type; E = 1 with n = 1, E = 5 with the permuted subset [3, 0, 4], E = 70 with every environment (more than one 64-wide
@@ -66,7 +67,7 @@ def _started(cfg, E, seed, act_seed=5):
 
 
 def _donor_blobs(cfg, E, ids):
-    """mid-episode states of a third run, read through the per-environment host path: (ctypes structs, uint8 [n, state_size]); blob k
+    """mid-episode states of a third run, read one by one with get_state: (ctypes structs, uint8 [n, state_size]); blob k
     comes from environment (3 k + 1) % E of the donor, so that a batched write that ignored its index list would not pass"""
     donor = _started(cfg, E, DONOR_SEED, act_seed=9)
     sts = [donor.get_state((3 * k + 1) % E) for k in range(len(ids))]
@@ -273,6 +274,48 @@ def test_a_blob_that_does_not_fit_is_rejected_and_reported(cfg):
         assert env.error_flags_per_env().cpu().tolist() == [0, 0, 0, 0, 64]
     env.reset_flat()
     assert env.error_flags() == 0, "a reset clears the bit"
+    env.close()
+
+
+# what test 5 writes into a blob to make it a misfit, per environment type: (field, value); "n_def" goes to team 1, "defenders" to the
+# first id of team 0 with n_def[0] = 1
+MISFITS = {1: [("n_cars", "A+1"), ("n_peds", 21), ("n_peds", -1), ("n_obst", 21), ("n_obst", -1)],
+           0: [("n_robots", "A+1"), ("n_def", 11), ("n_def", -1), ("defenders", 10), ("defenders", -1)]}
+SYNC_CASES = [(c, f, v) for c in ("driving10", "robocup5") for f, v in MISFITS[CFGS[c][0]]]
+
+
+@pytest.mark.parametrize("cfg,field,val", SYNC_CASES)
+def test_set_state_returns_the_error_of_a_blob_that_does_not_fit(cfg, field, val):
+    """5b. the synchronous call has a return code: a misfit is DYNENV_ERR_ARG ("does not match"), the environment - every environment -
+    stays as it was, NO error bit is raised (a sticky bit 6 would make a later compat step() raise), and a valid set_state of the same
+    environment succeeds.  The staging area the call goes through is not part of a checkpoint: its size is the recorded one."""
+    import json
+    import os
+    from dynenv_amd import _capi
+    E = 5
+    env = _started(cfg, E, SEED)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "state_digests.json")) as f:
+        assert env.checkpoint().size == json.load(f)["digests"]["state/%s/E5_subset" % cfg]["checkpoint_size"]
+    sts, _ = _donor_blobs(cfg, E, [0])
+    good = sts[0]
+    bad = type(good).from_buffer_copy(bytes(good))
+    if field == "n_def":
+        bad.n_def[1] = val
+    elif field == "defenders":
+        bad.n_def[0] = 1
+        bad.defenders[0][0] = val
+    else:
+        setattr(bad, field, env.n_agents + 1 if val == "A+1" else val)
+    before = env.get_states().cpu().numpy().tobytes()
+    ckpt = env.checkpoint().tobytes()
+    with pytest.raises(_capi.DynEnvError, match="does not match"):
+        env.set_state(4, bad)
+    assert env.get_states().cpu().numpy().tobytes() == before, "a rejected blob leaves every environment untouched"
+    assert env.checkpoint().tobytes() == ckpt
+    assert env.error_flags_per_env().cpu().tolist() == [0] * E and env.error_flags() == 0
+    env.set_state(4, good)
+    assert bytes(env.get_state(4)) == bytes(good)
+    assert env.error_flags_per_env().cpu().tolist() == [0] * E
     env.close()
 
 

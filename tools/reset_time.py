@@ -2,8 +2,8 @@
 """What a reset costs, for the whole batch and for chosen environments, for Driving Full with 10 cars and RoboCup Full with 5 robots per
 team.  One process, HIP events around the C entry points on the handle's own buffers, a warm-up, and the variants alternating within
 every repeat (--repeats: the run-to-run spread):
-  (a) dynenv_reset                       the thread-per-environment kernels, all environments
-  (b) dynenv_reset_masked, all listed    the same work, one wave per environment
+  (a) dynenv_reset                       every environment: the reset kernels (one wave per environment) launched without a mask
+  (b) dynenv_reset_masked, all listed    the same kernels and the same work behind a mask of ones: (b) - (a) is what the mask test costs
   (c) dynenv_reset_masked, 0 listed      what the launches cost when nothing is to be done
   (d) dynenv_reset_masked, E / 600 (7 of 4096) and 64 listed, also as a share of the mean step time of (e)
   (e) the mean step time over one whole episode in lock-step, against the mean of step + reset_masked(dones) over as many steps of a

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""What moving every environment's state costs, per environment through the host (get_state / set_state loops) against one batched,
-device-side call (get_states / set_states), for Driving with 10 cars and RoboCup with 5 robots per team.  The loops are timed on the
+"""What moving every environment's state costs, per environment through the host (get_state / set_state loops: one launch of the state
+kernels for ONE blob and one copy through host memory per call) against one batched, device-side call of the same kernels (get_states /
+set_states), for Driving with 10 cars and RoboCup with 5 robots per team.  The loops are timed on the
 wall clock (they synchronise the device themselves); each batched call is timed with a pair of HIP events around the C entry point on
 preallocated buffers, median (min .. max) of --calls calls after a warm-up, next to a plain device-to-device copy of the same
 n x state_size bytes timed the same way in the same run.  "Rate" is blob bytes per second (n x state_size / time) for the kernels and
