@@ -78,7 +78,7 @@ EXPORTS = ["dynenv_abi_version", "dynenv_last_error", "dynenv_create", "dynenv_d
            "dynenv_checkpoint_save", "dynenv_checkpoint_load", "dynenv_obs_pack", "dynenv_obs_unpack", "dynenv_obs_unpack_ranks",
            "dynenv_obs_pack_peers", "dynenv_obs_unpack_peers_ranks", "dynenv_step_head", "dynenv_full_obs", "dynenv_full_obs_dim",
            "dynenv_global_state", "dynenv_global_state_dim", "dynenv_set_step_events", "dynenv_get_states", "dynenv_set_states",
-           "dynenv_error_flags_env", "dynenv_reset_masked"]
+           "dynenv_error_flags_env", "dynenv_reset_masked", "dynenv_step_masked"]
 
 ERR_BAD_BLOB = 64  # error bit 6: a blob given to dynenv_set_states did not fit the handle and was not written
 SET_WRITTEN, SET_REJECTED, SET_BAD_INDEX = 0, 1, 2  # dynenv_set_states' per-blob status
@@ -160,6 +160,7 @@ def load():
     lib.dynenv_reset_masked.argtypes = [vp, vp, vp, vp]
     lib.dynenv_step.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.dynenv_step_head.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.dynenv_step_masked.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     lib.dynenv_full_obs.argtypes = [vp, vp, vp]
     lib.dynenv_full_obs_dim.argtypes = [vp]
     lib.dynenv_global_state.argtypes = [vp, vp, vp]

@@ -1849,9 +1849,13 @@ DE_DEV void drv_iso_report(const DrvState& S, int e, int lane, unsigned long lon
   __atomic_store_n(&S.iso_done[e], tick, __ATOMIC_RELAXED);
 }
 
+// mask (device uint8 [E], dynenv_step_masked; nullptr: every environment): the wave of an environment whose byte is 0 ends as soon as
+// it knows which environment it has - it reads no action and writes no byte of the environment's state, of its output rows or of any
+// list.  What a block does for the LAUNCH (block 0's buffer clear and tick mirror, the placement record, the validator, a
+// placeholder's wait: all in front of or inside drv_iso_assign) does not depend on the mask.
 template <bool PARTIAL>
-DE_DEV void drv_step_body(const DrvState& S, const int* __restrict__ actions, float* __restrict__ obs, double* __restrict__ rewards,
-                          uint8_t* __restrict__ dones, float* __restrict__ pobs, int pvNoise, double pvMagn) {
+DE_DEV void drv_step_body(const DrvState& S, const uint8_t* __restrict__ mask, const int* __restrict__ actions, float* __restrict__ obs,
+                          double* __restrict__ rewards, uint8_t* __restrict__ dones, float* __restrict__ pobs, int pvNoise, double pvMagn) {
   const unsigned long long isoT0 = __builtin_amdgcn_s_memtime();
 DRV_PROF(const unsigned long long KS = isoT0;)
   DrvLds& L = g_L;
@@ -1860,6 +1864,11 @@ DRV_PROF(const unsigned long long KS = isoT0;)
   if (!S.tick_src && blockIdx.x == 0 && lane == 0) { S.iso[13] = S.tick; S.iso[14] = S.pv_par; }  // (mirror for a later switch to tick_src = 1)
   const int e = drv_iso_assign(S, lane, tick);  // (= blockIdx.x unless the slow environments of the previous step are being isolated)
   if (e < 0) return;
+  if (mask && uniform_i(mask[e]) == 0) {
+    // (an isolated environment's placeholders wait for this word whether it steps or not: drv_iso_report)
+    if ((S.iso_on == 1 || S.iso_on == 2) && lane == 0) __atomic_store_n(&S.iso_done[e], tick, __ATOMIC_RELAXED);
+    return;
+  }
 DRV_PROF(if (lane < 8 && e < 4096) { g_dbgp[e * 8 + lane] = 0ull; g_dbgs[e * 8 + lane] = 0ull; })
   const int A = S.A;
   int* envi = S.envi + (size_t)e * EI_COUNT;
@@ -2084,15 +2093,15 @@ extern "C" __global__ void drv_tick_advance_kernel(DrvState S, int flipPv) {
 }
 
 extern "C" __global__ void __launch_bounds__(64, DRV_WAVES_PER_SIMD)
-drv_step_kernel(DrvState S, const int* __restrict__ actions, float* __restrict__ obs, double* __restrict__ rewards,
-                uint8_t* __restrict__ dones) {
-  drv_step_body<false>(S, actions, obs, rewards, dones, nullptr, 0, 0.0);
+drv_step_kernel(DrvState S, const uint8_t* __restrict__ mask, const int* __restrict__ actions, float* __restrict__ obs,
+                double* __restrict__ rewards, uint8_t* __restrict__ dones) {
+  drv_step_body<false>(S, mask, actions, obs, rewards, dones, nullptr, 0, 0.0);
 }
 // Partial observation: same step, then each wave writes its environment's observation (fused getAgentVision)
 extern "C" __global__ void __launch_bounds__(64, DRV_WAVES_PER_SIMD)
-drv_step_partial_kernel(DrvState S, const int* __restrict__ actions, double* __restrict__ rewards, uint8_t* __restrict__ dones,
-                        float* __restrict__ pobs, int pvNoise, double pvMagn) {
-  drv_step_body<true>(S, actions, nullptr, rewards, dones, pobs, pvNoise, pvMagn);
+drv_step_partial_kernel(DrvState S, const uint8_t* __restrict__ mask, const int* __restrict__ actions, double* __restrict__ rewards,
+                        uint8_t* __restrict__ dones, float* __restrict__ pobs, int pvNoise, double pvMagn) {
+  drv_step_body<true>(S, mask, actions, nullptr, rewards, dones, pobs, pvNoise, pvMagn);
 }
 
 // episode_g = [#finished & !crashed, #crashed] (:315-316) + episode accumulators, gathered for the host mirror

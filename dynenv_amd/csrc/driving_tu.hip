@@ -213,7 +213,7 @@ struct HOST_LOCAL DrvHandle final : dynenv {
     return fail(DYNENV_ERR_UNSUPPORTED, "Driving: getFullState(None) is made of columns of dynenv_full_obs (every car's own self block); no separate emit");
   }
 
-  int step(const int* actions, const double* head, float* obs, double* rewards, uint8_t* dones, hipStream_t st) override {
+  int step(const uint8_t* mask, const int* actions, const double* head, float* obs, double* rewards, uint8_t* dones, hipStream_t st) override {
     if (head) return fail(DYNENV_ERR_ARG, "the continuous head channel exists for RoboCup with DYNENV_FLAG_ALLOW_HEAD_TURN only");
     // Partial: getAgentVision for every agent (DrivingEnvironment.py:294) is fused into the step kernel - each wave writes its
     // environment's observation as soon as its step is done, which fills the launch's tail
@@ -255,7 +255,7 @@ struct HOST_LOCAL DrvHandle final : dynenv {
     if (partial && obs)
     {
       if (!S.tick_src) S.pv_par ^= 1;
-      hipLaunchKernelGGL(drv_step_partial_kernel, dim3(stepGrid), dim3(64), 0, st, S, actions, rewards, dones, obs,
+      hipLaunchKernelGGL(drv_step_partial_kernel, dim3(stepGrid), dim3(64), 0, st, S, mask, actions, rewards, dones, obs,
                          (int)cfg.noise_type, (double)cfg.noise_magnitude);
       step_main_done(st);
       // one block per (listed environment, agent) in turn, over a grid that fits the device at once: the step launch left a list
@@ -264,7 +264,7 @@ struct HOST_LOCAL DrvHandle final : dynenv {
                          (int)cfg.noise_type, (double)cfg.noise_magnitude, obs);
     }
     else {
-      hipLaunchKernelGGL(drv_step_kernel, dim3(stepGrid), dim3(64), 0, st, S, actions, partial ? (float*)nullptr : obs, rewards, dones);
+      hipLaunchKernelGGL(drv_step_kernel, dim3(stepGrid), dim3(64), 0, st, S, mask, actions, partial ? (float*)nullptr : obs, rewards, dones);
       step_main_done(st);
     }
     return launched();

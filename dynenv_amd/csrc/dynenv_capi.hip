@@ -104,13 +104,9 @@ int dynenv_global_state(dynenv_t* h, float* state_dev, void* stream) {
   return h->global_state(state_dev, (hipStream_t)stream);
 }
 
-int dynenv_step(dynenv_t* h, const int32_t* actions_dev, float* obs_dev, double* rewards_dev, uint8_t* dones_dev,
-                void* stream) {
-  return dynenv_step_head(h, actions_dev, nullptr, obs_dev, rewards_dev, dones_dev, stream);
-}
-
-int dynenv_step_head(dynenv_t* h, const int32_t* actions_dev, const double* head_dev, float* obs_dev, double* rewards_dev,
-                     uint8_t* dones_dev, void* stream) {
+// the one step: dynenv_step / dynenv_step_head are dynenv_step_masked without a mask (every environment)
+static int step_any(dynenv_t* h, const uint8_t* mask_dev, const int32_t* actions_dev, const double* head_dev, float* obs_dev, double* rewards_dev,
+                    uint8_t* dones_dev, void* stream) {
   if (!h || !actions_dev || !rewards_dev || !dones_dev) return fail(DYNENV_ERR_ARG, "null argument");
   if (head_dev && !(h->cfg.flags & DYNENV_FLAG_ALLOW_HEAD_TURN))  // (RoboCup's switch: a Driving handle has no flags, dynenv_create)
     return fail(DYNENV_ERR_ARG, "the continuous head channel exists for RoboCup with DYNENV_FLAG_ALLOW_HEAD_TURN only");
@@ -122,7 +118,23 @@ int dynenv_step_head(dynenv_t* h, const int32_t* actions_dev, const double* head
     dynenv* h; hipStream_t st;
     ~StepEvents() { if (h->ev_end) (void)hipEventRecord(h->ev_end, st); }
   } sev{h, st};
-  return h->step((const int*)actions_dev, head_dev, obs_dev, rewards_dev, dones_dev, st);
+  return h->step(mask_dev, (const int*)actions_dev, head_dev, obs_dev, rewards_dev, dones_dev, st);
+}
+
+int dynenv_step(dynenv_t* h, const int32_t* actions_dev, float* obs_dev, double* rewards_dev, uint8_t* dones_dev,
+                void* stream) {
+  return step_any(h, nullptr, actions_dev, nullptr, obs_dev, rewards_dev, dones_dev, stream);
+}
+
+int dynenv_step_head(dynenv_t* h, const int32_t* actions_dev, const double* head_dev, float* obs_dev, double* rewards_dev,
+                     uint8_t* dones_dev, void* stream) {
+  return step_any(h, nullptr, actions_dev, head_dev, obs_dev, rewards_dev, dones_dev, stream);
+}
+
+int dynenv_step_masked(dynenv_t* h, const uint8_t* mask_dev, const int32_t* actions_dev, const double* head_dev, float* obs_dev,
+                       double* rewards_dev, uint8_t* dones_dev, void* stream) {
+  if (!h || !mask_dev) return fail(DYNENV_ERR_ARG, "null argument");
+  return step_any(h, mask_dev, actions_dev, head_dev, obs_dev, rewards_dev, dones_dev, stream);
 }
 
 int dynenv_set_step_events(dynenv_t* h, void* ev_begin, void* ev_main_done, void* ev_end) {

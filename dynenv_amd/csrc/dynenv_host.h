@@ -64,8 +64,10 @@ struct HOST_LOCAL dynenv {
   // the reset: every environment (mask == nullptr: dynenv_reset) or exactly the environments e with mask[e] != 0 (device uint8 [E]); one
   // wave per environment, nothing but launches on `st` (capturable behind a captured step); the scheduler's scratch is not touched
   virtual int reset_masked(const uint8_t* mask, float* obs, hipStream_t st) = 0;
+  // the step of every environment (mask == nullptr: dynenv_step / dynenv_step_head) or of exactly the environments e with mask[e] != 0
+  // (device uint8 [E], read by the step kernel: dynenv_step_masked), the others left byte for byte as they are;
   // records ev_begin in front of the step's dominant kernel and ev_main right behind it (step_begin / step_main_done)
-  virtual int step(const int* actions, const double* head, float* obs, double* rewards, uint8_t* dones, hipStream_t st) = 0;
+  virtual int step(const uint8_t* mask, const int* actions, const double* head, float* obs, double* rewards, uint8_t* dones, hipStream_t st) = 0;
   virtual int full_obs(float* full, hipStream_t st) = 0;
   virtual int global_state(float* state, hipStream_t st) = 0;
   virtual int counts(int32_t* out, hipStream_t st) = 0;

@@ -155,11 +155,11 @@ struct HOST_LOCAL RcHandle final : dynenv {
     return launched();
   }
 
-  int step(const int* actions, const double* head, float* obs, double* rewards, uint8_t* dones, hipStream_t st) override {
+  int step(const uint8_t* mask, const int* actions, const double* head, float* obs, double* rewards, uint8_t* dones, hipStream_t st) override {
     if (R.obs_type == DYNENV_OBS_PARTIAL && obs) {  // getAgentVision at the five snapshots + processSeens fused into the launch
       HIP_OK(hipMemsetAsync(R.deferList, 0, sizeof(int), st));
       if (step_begin(st)) return DYNENV_ERR_HIP;
-      hipLaunchKernelGGL(rc_step_partial_kernel, dim3(R.E), dim3(64), 0, st, R, actions, head, obs, rewards, dones);
+      hipLaunchKernelGGL(rc_step_partial_kernel, dim3(R.E), dim3(64), 0, st, R, mask, actions, head, obs, rewards, dones);
       step_main_done(st);
       const int nb = R.E < RC_DEFER_BLOCKS ? R.E : RC_DEFER_BLOCKS;  // the deferred environments are few: blocks stride over their list
       hipLaunchKernelGGL(rc_partial_obs_deferred_kernel, dim3(nb, 5, R.R), dim3(64), 0, st, R, obs);
@@ -169,7 +169,7 @@ struct HOST_LOCAL RcHandle final : dynenv {
       return fail(DYNENV_ERR_ARG, "RoboCup Partial: the observation buffer is required (the processSeens rewards come out of the same pass)");
     else {
       if (step_begin(st)) return DYNENV_ERR_HIP;
-      hipLaunchKernelGGL(rc_step_kernel, dim3(R.E), dim3(64), 0, st, R, actions, head, obs, rewards, dones);
+      hipLaunchKernelGGL(rc_step_kernel, dim3(R.E), dim3(64), 0, st, R, mask, actions, head, obs, rewards, dones);
       step_main_done(st);
     }
     return launched();

@@ -1971,9 +1971,12 @@ RC_PROF(if (lane == 0 && c.genv < 4096u) { unsigned long long* d = g_rcprof3 + c
   ret.pairLo = pairLo; ret.pairHi = pairHi; ret.cand = cand; ret.bits = quiet ? 1 : 0;
   return ret;
 }
+// mask (device uint8 [E], dynenv_step_masked; nullptr: every environment): the wave of an environment whose byte is 0 ends at once - it
+// reads no action and writes no byte of the environment's state, of its output rows or of deferList's entries.  The one thing a block
+// does for the LAUNCH, environment 0's rotation of the forecast words, does not depend on the mask.
 template <bool PARTIAL, int EPW>
-DE_DEV void rc_step_body(const RcState& S, const int e, const int* __restrict__ actions, const double* __restrict__ headActions, float* __restrict__ obs,
-                         double* __restrict__ rewards, uint8_t* __restrict__ dones) {
+DE_DEV void rc_step_body(const RcState& S, const uint8_t* __restrict__ mask, const int e, const int* __restrict__ actions,
+                         const double* __restrict__ headActions, float* __restrict__ obs, double* __restrict__ rewards, uint8_t* __restrict__ dones) {
   typedef Grp<EPW> G;
   constexpr int W = G::W, NROUNDS = (RC_NPAIR_ROUNDS * 64) / W;
   static_assert(RC_NS <= 16, "sLevel packs level and rank into four bits each");
@@ -1981,6 +1984,10 @@ DE_DEV void rc_step_body(const RcState& S, const int e, const int* __restrict__ 
   int lane = G::lane();
   const int R = S.R;
   if (e < 0 || e >= S.E) return;  // (two environments per wave: a half without an environment; its lanes are off from here on)
+  if (mask && G::uniform_i(mask[e]) == 0) {
+    if (PARTIAL && e == 0 && lane == 0) { int* sc = S.deferList + S.E + 1; sc[0] = sc[1]; sc[1] = 0; }  // (as below)
+    return;
+  }
   RcLds& L = G::tile();
   uint64_t occ = (uint64_t)(uint32_t)G::uniform_i(S.envi[(size_t)e * RE_COUNT + RE_OCC]);
   // Environments with live contacts are the long ones and the launch ends with the slowest: their waves get issue priority
@@ -2117,14 +2124,14 @@ RC_PROF(if (lane == 0 && e < 4096) { unsigned long long* d = g_rcprof + e * 12; 
 }
 // Full observations: one environment per wave at four waves per SIMD (128 VGPRs, the general path out of line)
 extern "C" __global__ void __launch_bounds__(64, RC_WAVES_PER_SIMD)
-rc_step_kernel(RcState S, const int* __restrict__ actions, const double* __restrict__ headActions, float* __restrict__ obs,
-               double* __restrict__ rewards, uint8_t* __restrict__ dones) {
-  rc_step_body<false, 1>(S, (int)blockIdx.x, actions, headActions, obs, rewards, dones);
+rc_step_kernel(RcState S, const uint8_t* __restrict__ mask, const int* __restrict__ actions, const double* __restrict__ headActions,
+               float* __restrict__ obs, double* __restrict__ rewards, uint8_t* __restrict__ dones) {
+  rc_step_body<false, 1>(S, mask, (int)blockIdx.x, actions, headActions, obs, rewards, dones);
 }
 extern "C" __global__ void __launch_bounds__(64, RC_WAVES_PER_SIMD)
-rc_step_partial_kernel(RcState S, const int* __restrict__ actions, const double* __restrict__ headActions, float* __restrict__ obs,
-                       double* __restrict__ rewards, uint8_t* __restrict__ dones) {
-  rc_step_body<true, 1>(S, (int)blockIdx.x, actions, headActions, obs, rewards, dones);
+rc_step_partial_kernel(RcState S, const uint8_t* __restrict__ mask, const int* __restrict__ actions, const double* __restrict__ headActions,
+                       float* __restrict__ obs, double* __restrict__ rewards, uint8_t* __restrict__ dones) {
+  rc_step_body<true, 1>(S, mask, (int)blockIdx.x, actions, headActions, obs, rewards, dones);
 }
 
 // getFullState(agent=None) (RoboCupEnvironment.py:1149-1161), what step() stores as info['Full State'] (:511): per environment

@@ -132,8 +132,9 @@ def _robocup_spaces(obs_type, allow_head_turn):
     return observation_space, action_space, reco
 
 
-def reset_mask(envs, num_envs, device=None):
-    """The argument of BatchedDynEnv.reset_envs -> a contiguous uint8 [num_envs] mask tensor (on `device`, if given).
+def reset_mask(envs, num_envs, device=None, what="reset_envs"):
+    """The argument of BatchedDynEnv.reset_envs (or of step_flat(active=...): `what` names the caller in the error messages) -> a contiguous
+    uint8 [num_envs] mask tensor (on `device`, if given).
       * a bool tensor or numpy array, wherever it lives, and a uint8 tensor ON THE DEVICE - `dones` - are the mask itself: [num_envs],
         taken as it is (bool is viewed as uint8: no copy, nothing is read);
       * a list / numpy array / host tensor of integer ids - uint8 included: on the host small integers are ids, never a mask - is
@@ -145,8 +146,8 @@ def reset_mask(envs, num_envs, device=None):
         m = envs
     elif isinstance(envs, torch.Tensor):
         if envs.device.type != "cpu":
-            raise _capi.DynEnvError("reset_envs: a device tensor must be a bool / uint8 mask [%d], not %s ids (they would have to be read back "
-                                    "to be checked; `mask[ids] = 1` is one line)" % (num_envs, envs.dtype))
+            raise _capi.DynEnvError("%s: a device tensor must be a bool / uint8 mask [%d], not %s ids (they would have to be read back "
+                                    "to be checked; `mask[ids] = 1` is one line)" % (what, num_envs, envs.dtype))
         m = envs.numpy()
     else:
         m = np.asarray(envs)
@@ -155,17 +156,17 @@ def reset_mask(envs, num_envs, device=None):
             m = torch.as_tensor(np.ascontiguousarray(m))
         else:
             if m.size and m.dtype.kind not in "iu":
-                raise _capi.DynEnvError("reset_envs: environment ids must be integers, got %s" % m.dtype)
+                raise _capi.DynEnvError("%s: environment ids must be integers, got %s" % (what, m.dtype))
             if m.ndim > 1:
-                raise _capi.DynEnvError("reset_envs: expected a list of environment ids, got shape %s" % (m.shape,))
+                raise _capi.DynEnvError("%s: expected a list of environment ids, got shape %s" % (what, m.shape))
             ids = m.reshape(-1).astype(np.int64)
             if ids.size and (ids.min() < 0 or ids.max() >= num_envs):
-                raise _capi.DynEnvError("reset_envs: environment id %d outside [0, %d)" % (int(ids.min() if ids.min() < 0 else ids.max()), num_envs))
+                raise _capi.DynEnvError("%s: environment id %d outside [0, %d)" % (what, int(ids.min() if ids.min() < 0 else ids.max()), num_envs))
             host = np.zeros((num_envs,), np.uint8)
             host[ids] = 1
             m = torch.as_tensor(host)
     if m.dim() != 1 or m.shape[0] != num_envs:
-        raise _capi.DynEnvError("reset_envs: the mask must be [%d], got shape %s" % (num_envs, tuple(m.shape)))
+        raise _capi.DynEnvError("%s: the mask must be [%d], got shape %s" % (what, num_envs, tuple(m.shape)))
     if m.dtype == torch.bool:
         m = m.view(torch.uint8)
     if device is not None and m.device != torch.device(device):
@@ -328,28 +329,47 @@ class BatchedDynEnv(object):
                             (self.action_dim, "car" if self.env_type == DynEnvType.DRIVE else "robot"))
         return a, head
 
-    def step_flat(self, actions, auto_reset=True, validate=False):
+    def step_flat(self, actions, auto_reset=True, validate=False, active=None):
         """One env step of every environment: ONE kernel launch on torch's current stream.  Nothing is waited for and no flag is
         read here: a consumer of Partial observations that wants to know whether a list ever outgrew the layout's capacity (rows
-        dropped; astronomically unlikely, include/dynenv.h error bit 3) calls error_flags() at its own pace; step() does, and raises."""
+        dropped; astronomically unlikely, include/dynenv.h error bit 3) calls error_flags() at its own pace; step() does, and raises.
+
+        `active` (episodes="per_env" only): step exactly the listed environments and hold the others still (dynenv_step_masked) - a
+        bool / uint8 [num_envs] device tensor, used as it is (nothing is read on the host: a captured call reads the tensor's contents
+        at every replay), or a list / numpy array / host tensor of environment ids (reset_mask).  A listed environment gets exactly the
+        step it would have got; of an unlisted one no byte of state changes, and its rows of the returned `obs`, `rewards` and `dones`
+        are STALE: they keep what the tensors held before the call - usually that environment's last own step.  A caller that sums
+        `rewards` masks them (`rew * active.unsqueeze(1)`); its rows of `actions` are not read.  With auto_reset=True the environments
+        reset are `dones & active` (a stale `dones` byte resets nothing), and last_episode_stats / terminal_obs follow the same mask.
+        validate=True looks at the listed rows only."""
         if self._needs_reset:
             raise _capi.DynEnvError("call reset() before step()")
         torch = self._torch
+        if active is not None and not self.per_env:
+            # dones and the auto-reset of a lock-step handle follow ONE host-side position in the episode: a partial step would make it meaningless
+            raise _capi.DynEnvError("step_flat(active=...) needs a handle with episodes='per_env' (every environment keeps its own time)")
         if auto_reset and not self.per_env and torch.cuda.is_current_stream_capturing():
             # the host's position in the episode does not advance at replay: a reset decided now would be frozen into the graph (or never come)
             raise _capi.DynEnvError("step_flat(auto_reset=True) inside a stream capture: capture with auto_reset=False and reset between replays")
+        mask = reset_mask(active, self.num_envs, self.device, what="step_flat") if active is not None else None
         a, head = self._stage_actions(actions)
+        listed = (lambda bad: bad) if mask is None else (lambda bad: bad & mask.bool().reshape((-1,) + (1,) * (bad.dim() - 1)))
         if validate and self.env_type == DynEnvType.DRIVE:
-            if bool(((a < 0) | (a > 2)).any()):  # DrivingEnvironment.py:365-368
+            if bool(listed((a < 0) | (a > 2)).any()):  # DrivingEnvironment.py:365-368
                 raise Exception("Error: Acceleration must be between +/-3")
         if validate and self.env_type == DynEnvType.ROBO_CUP:  # RoboCupEnvironment.py:543-550
             hi = torch.tensor([4, 2, 2], device=a.device, dtype=a.dtype)
-            if bool(((a[..., :3] < 0) | (a[..., :3] > hi)).any()):
+            if bool(listed((a[..., :3] < 0) | (a[..., :3] > hi)).any()):
                 raise Exception("Error: Robot movement must be categorical in the range [0-4]")
-            bad_head = (head.abs() > 6).any() if head is not None else ((a[..., 3] < 0) | (a[..., 3] > 6)).any()
+            bad_head = listed(head.abs() > 6).any() if head is not None else listed((a[..., 3] < 0) | (a[..., 3] > 6)).any()
             if bool(bad_head):
                 raise Exception("Error: Head turn must be between +/-6")
-        if head is not None:
+        if mask is not None:
+            _capi.check(self._lib.dynenv_step_masked(self._h, C.c_void_p(mask.data_ptr()), C.c_void_p(a.data_ptr()),
+                                                     C.c_void_p(head.data_ptr()) if head is not None else None,
+                                                     C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.rewards.data_ptr()),
+                                                     C.c_void_p(self.dones.data_ptr()), self._stream()), "dynenv_step_masked")
+        elif head is not None:
             _capi.check(self._lib.dynenv_step_head(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(head.data_ptr()),
                                                    C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.rewards.data_ptr()),
                                                    C.c_void_p(self.dones.data_ptr()), self._stream()), "dynenv_step_head")
@@ -360,14 +380,19 @@ class BatchedDynEnv(object):
         if self.per_env:
             # every environment ends on its own: the device's `dones` is the mask, no host counter is read or kept
             if auto_reset:
+                # (with `active`: an unlisted environment's dones byte is stale, so the finished AND listed ones - one op, nothing read)
+                ended = self.dones if mask is None else torch.logical_and(self.dones, mask)
                 if self.keep_terminal_obs:
-                    self.terminal_obs.copy_(self.obs)
+                    if mask is None:
+                        self.terminal_obs.copy_(self.obs)
+                    else:
+                        torch.where(mask.bool().reshape(-1, 1, 1, 1), self.obs, self.terminal_obs, out=self.terminal_obs)
                 if self.track_episode_stats:
                     self.episode_stats(out=self._stats_now)
-                    done = self.dones.bool().unsqueeze(1)
+                    done = ended.bool().unsqueeze(1)
                     for last, now in zip(self.last_episode_stats, self._stats_now):
                         torch.where(done, now, last, out=last)
-                self.reset_envs(self.dones)
+                self.reset_envs(ended)
             return self.obs, self.rewards, self.dones
         self._episode_step += 1
         self.last_done = self._episode_step >= self.steps_per_episode  # fixed-length episodes

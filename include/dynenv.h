@@ -9,6 +9,7 @@
  *                           DynEnv/environment_base.py:205-224 EnvironmentBase.reset
  *   dynenv_reset_masked  <- the same EnvironmentBase.reset (environment_base.py:205-224), for chosen environments: what a
  *                           SubprocVecEnv worker does when ITS environment is done (subproc_vec_env.py:19-22)
+ *   dynenv_step_masked   <- a SubprocVecEnv worker that is sent nothing does nothing: the step for chosen environments
  *   dynenv_step          <- DynEnv/utils/subproc_vec_env.py:102-111 step_async/step_wait ->
  *                           DynEnv/DrivingEnvironment.py:248-322 / DynEnv/RoboCupEnvironment.py:446-524 step
  *   dynenv_episode_stats <- info['episode_r'|'episode_p_r'|'episode_o_r'|'episode_g'] (DrivingEnvironment.py:310-316,
@@ -204,8 +205,24 @@ int dynenv_global_state(dynenv_t* h, float* state_dev, void* stream);
 int dynenv_step_head(dynenv_t* h, const int32_t* actions_dev, const double* head_dev, float* obs_dev, double* rewards_dev,
                      uint8_t* dones_dev, void* stream);
 
+/* One environment step for exactly the environments e with mask_dev[e] != 0 (uint8 [E]); the others stand still.  The buffers are
+ * dynenv_step's; head_dev may be NULL, and non-NULL is allowed under dynenv_step_head's rule only; RoboCup with Partial observations
+ * needs obs_dev, as in dynenv_step.
+ *   A LISTED environment gets exactly what dynenv_step / dynenv_step_head would have done to it - byte for byte, in every device
+ *   array of the handle and in obs_dev[e], rewards_dev[e], dones_dev[e] - however many calls it sat out before: everything it draws is
+ *   keyed by its own elapsed time and episode counter.
+ *   An UNLISTED environment: no byte of its state changes - bodies, contact cache (warm-start impulses), shortcut state, call-to-call
+ *   caches, episode accumulators, diagnostic counters, error word - and no byte of obs_dev[e], rewards_dev[e], dones_dev[e]: those rows
+ *   keep whatever the buffers held (a caller that sums rewards masks them).  Its rows of actions_dev / head_dev are not read.
+ * Ordered on `stream`; no host synchronisation, no allocation, no host copy.  Capturable into a hipGraph like dynenv_step; the mask is
+ * read by the kernel, so a replay uses what mask_dev holds THEN.  The launches of dynenv_step; the scheduler's scratch (timing
+ * only) sees the listed environments alone.
+ * Errors: NULL handle or mask -> DYNENV_ERR_ARG (before a device is looked for); then dynenv_step_head's. */
+int dynenv_step_masked(dynenv_t* h, const uint8_t* mask_dev, const int32_t* actions_dev, const double* head_dev,
+                       float* obs_dev, double* rewards_dev, uint8_t* dones_dev, void* stream);
+
 /* Measurement hook (bench.py's roofline leg): three caller-owned hipEvent_t (as void*; NULL = none, all NULL = off) that every
- * following dynenv_step / dynenv_step_head records on ITS launch stream - before the step's dominant kernel (drv_step_kernel,
+ * following dynenv_step / dynenv_step_head / dynenv_step_masked records on ITS launch stream - before the step's dominant kernel (drv_step_kernel,
  * rc_step_kernel, drv_step_partial_kernel, rc_step_partial_kernel), right after it, and after the step's last kernel (the
  * deferred-observation / finalize launches of the Partial paths).  hipEventElapsedTime(begin, main_done) is that kernel's own
  * launch duration.  The events are overwritten by the next step: synchronise on ev_end before stepping again. */
