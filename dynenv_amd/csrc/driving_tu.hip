@@ -197,6 +197,7 @@ struct HOST_LOCAL DrvHandle final : dynenv {
   void set_seed(uint64_t seed) override { cfg.seed = seed; S.seed = seed; }
 
   int reset_masked(const uint8_t* mask, float* obs, hipStream_t st) override {
+    note_capture(st);
     hipLaunchKernelGGL(drv_reset_masked_kernel, dim3(S.E), dim3(64), 0, st, S, mask);
     if (obs && partial)
       hipLaunchKernelGGL(drv_partial_obs_kernel, dim3(S.E), dim3(64), 0, st, S, mask, (int)cfg.noise_type, cfg.noise_magnitude, obs);
@@ -231,7 +232,7 @@ struct HOST_LOCAL DrvHandle final : dynenv {
     // validation still holds isolation off on a shared device), and a paused isolation stays paused.
     if (!S.tick_src) {
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) S.tick_src = 1;
+      if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) { S.tick_src = 1; captured = true; }  // (the one query serves both)
     }
     if (S.tick_src) hipLaunchKernelGGL(drv_tick_advance_kernel, dim3(1), dim3(64), 0, st, S, (partial && obs) ? 1 : 0);
     if (step_begin(st)) return DYNENV_ERR_HIP;  // (behind the advance kernel: the event window is the step kernel's own duration)

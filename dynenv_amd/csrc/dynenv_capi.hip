@@ -72,8 +72,16 @@ int dynenv_layout(const dynenv_t* h, dynenv_layout_t* L) {
   return DYNENV_OK;
 }
 
+// The seed is a by-value kernel argument: a launch that was captured keeps the one it was captured with at every replay, whatever the
+// handle holds by then, while the eager launches of the same handle would follow the new one.  Never silently.
+static int frozen_seed(const char* who) {
+  return fail(DYNENV_ERR_UNSUPPORTED, std::string(who) + ": a step or masked reset of this handle has been captured into a graph, and a captured "
+              "step replays with the seed it was captured with: the handle keeps that seed for good - create a new handle for another seed");
+}
+
 int dynenv_seed(dynenv_t* h, uint64_t seed) {
   if (!h) return fail(DYNENV_ERR_ARG, "null handle");
+  if (h->captured && seed != h->cfg.seed) return frozen_seed("dynenv_seed");
   h->set_seed(seed);
   return DYNENV_OK;
 }
@@ -454,6 +462,7 @@ int dynenv_checkpoint_load(dynenv_t* h, const void* buf_host, size_t nbytes) {
     return fail(DYNENV_ERR_ARG, "checkpoint was taken from a differently configured handle");
   if (hd.n_arrays != (int32_t)h->allocs.size() || hd.payload_bytes != ckpt_payload(h) || nbytes < sizeof(hd) + hd.payload_bytes)
     return fail(DYNENV_ERR_ARG, "checkpoint layout does not match this build");
+  if (h->captured && a.seed != b.seed) return frozen_seed("dynenv_checkpoint_load (the checkpoint was taken under another seed)");  // (nothing copied yet)
   HIP_OK(hipDeviceSynchronize());
   const char* in = (const char*)buf_host + sizeof(hd);
   // ABI 2 kept "an invalid action was seen" and, for Partial observations, "rows beyond the layout's capacity were dropped" in ONE bit

@@ -52,6 +52,14 @@ struct HOST_LOCAL dynenv {
   // where the kernels keep the per-environment error word: err_array[env * err_stride + err_index] (err_array is one of `allocs`)
   const int* err_array = nullptr;
   int err_stride = 0, err_index = 0;
+  // set by the first step or masked reset issued on a capturing stream, for the rest of the handle's life: the seed is a by-value
+  // kernel argument, so a replay draws from the seed of the capture whatever the handle holds by then - from here on dynenv_seed and
+  // dynenv_checkpoint_load refuse any other seed (dynenv_capi.hip)
+  bool captured = false;
+  void note_capture(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (!captured && hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) captured = true;
+  }
 
   virtual ~dynenv() {  // (on the handle's device: dynenv_destroy)
     for (void* p : allocs) (void)hipFree(p);

@@ -137,6 +137,7 @@ struct HOST_LOCAL RcHandle final : dynenv {
   void set_seed(uint64_t seed) override { cfg.seed = seed; R.seed = seed; }
 
   int reset_masked(const uint8_t* mask, float* obs, hipStream_t st) override {
+    note_capture(st);
     hipLaunchKernelGGL(rc_reset_masked_kernel, dim3(R.E), dim3(64), 0, st, R, mask);
     if (obs) {
       hipLaunchKernelGGL(rc_obs_kernel, dim3(R.E), dim3(64), 0, st, R, mask, obs, 0);
@@ -156,6 +157,7 @@ struct HOST_LOCAL RcHandle final : dynenv {
   }
 
   int step(const uint8_t* mask, const int* actions, const double* head, float* obs, double* rewards, uint8_t* dones, hipStream_t st) override {
+    note_capture(st);  // (R.seed is frozen into a captured launch: dynenv_host.h)
     if (R.obs_type == DYNENV_OBS_PARTIAL && obs) {  // getAgentVision at the five snapshots + processSeens fused into the launch
       HIP_OK(hipMemsetAsync(R.deferList, 0, sizeof(int), st));
       if (step_begin(st)) return DYNENV_ERR_HIP;

@@ -587,6 +587,10 @@ class BatchedDynEnv(object):
         return buf
 
     def restore(self, buf):
+        """Load a checkpoint() of a handle with this configuration: every device array, and the checkpoint's seed - whatever seed this
+        handle was created with or given by seed() since.  After a step_flat() / reset_envs() of this handle has been captured into a
+        graph, a checkpoint taken under another seed raises DynEnvError and nothing is copied (a replay would keep drawing from the
+        captured seed): restore it into a new handle."""
         import numpy as np
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         _capi.check(self._lib.dynenv_checkpoint_load(self._h, C.c_void_p(buf.ctypes.data), buf.size), "dynenv_checkpoint_load")
@@ -763,7 +767,12 @@ class BatchedDynEnv(object):
         return self.step_wait()
 
     def seed(self, seed=None):
-        """Working replacement for SubprocVecEnv.seed (which calls a non-existent env.seed, quirk C5)."""
+        """Working replacement for SubprocVecEnv.seed (which calls a non-existent env.seed, quirk C5); env_method("set_random_seed", s)
+        is this call.  Every environment draws from `seed` from now on (dynenv_seed): the next reset's scene, and - mid-episode - the
+        step-time draws of the running one (pedestrian moves, dice, observation noise).  No state blob changes; a later checkpoint()
+        carries the new seed, restore() brings back the checkpoint's.
+        Once a step_flat() / reset_envs() of this handle has been captured into a graph the seed is frozen: a replay draws from the seed
+        it was captured with.  seed() with any other value raises DynEnvError then and changes nothing; make a new handle."""
         _capi.check(self._lib.dynenv_seed(self._h, int(seed if seed is not None else 0)), "dynenv_seed")
         return [seed] * self.num_envs
 

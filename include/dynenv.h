@@ -149,6 +149,19 @@ const char* dynenv_last_error(void);
 int dynenv_create(const dynenv_cfg_t* cfg, dynenv_t** out);
 void dynenv_destroy(dynenv_t* h);
 int dynenv_layout(const dynenv_t* h, dynenv_layout_t* out);
+
+/* set_random_seed for every environment of the handle: all 64 bits of `seed` key every draw from now on (include/dynenv_math.h
+ * dm_env_rng: seed, global id, episode counter, purpose, entity, time).  Host state only: nothing is launched, copied or synchronised.
+ *   Before a reset: the reset draws its scene from (seed, global id, episode) - the handle is then what a handle created with `seed`
+ *   and brought to the same episode counters would be.
+ *   Mid-episode: no byte of any environment's state changes (the seed is in no state blob); the step-time draws of the running
+ *   episode - pedestrian moves, RoboCup's dice and kicks, observation noise - come from the new seed from the next step on.
+ *   Checkpoints: dynenv_checkpoint_save stores the handle's current seed, dynenv_checkpoint_load adopts the checkpoint's, whatever
+ *   dynenv_seed set before; a dynenv_seed after a load holds until the next load.
+ *   After a capture: the seed travels as a by-value kernel argument, so a dynenv_step / dynenv_step_masked / dynenv_reset_masked that
+ *   was captured into a hipGraph replays with the seed it was captured with.  From the first such call issued on a capturing stream,
+ *   for the rest of the handle's life, a `seed` other than the handle's returns DYNENV_ERR_UNSUPPORTED and changes nothing (the
+ *   handle's own seed again is accepted): create a new handle for another seed. */
 int dynenv_seed(dynenv_t* h, uint64_t seed);
 
 /* (Re)build every environment's scene and write the first observation(s): obs_dev float32 [E, T, A, obs_dim].  The launches of
@@ -326,7 +339,9 @@ int dynenv_obs_unpack_peers_ranks(const float* packed_dev, int64_t src_stride_fl
  * dynenv_get_state (which drops the contact cache), a checkpoint is every device array of the handle bit for bit -
  * bodies, contact cache, shortcut state, episode counters, seed - so that load + the same actions reproduces the run
  * exactly from the middle of an episode.  Host buffers; the handle must have the configuration the checkpoint was taken
- * with (env type, sizes, observation/noise type, flags, env_id_offset). ---- */
+ * with (env type, sizes, observation/noise type, flags, env_id_offset).  The seed need not match: a load adopts the checkpoint's
+ * seed - except on a handle of which a step or masked reset has been captured into a hipGraph (see dynenv_seed: a replay keeps the
+ * captured seed), where a checkpoint taken under another seed returns DYNENV_ERR_UNSUPPORTED before anything is copied. ---- */
 size_t dynenv_checkpoint_size(const dynenv_t* h);
 int dynenv_checkpoint_save(dynenv_t* h, void* buf_host, size_t nbytes);
 int dynenv_checkpoint_load(dynenv_t* h, const void* buf_host, size_t nbytes);

@@ -203,6 +203,17 @@ int oracle_set_state(oracle_t* o, int32_t env, const void* blob, size_t n) {
   else rc_set_state(&o->rc[env], (const dynenv_robocup_state_t*)blob);
   return DYNENV_OK;
 }
+/* the stand-in for set_random_seed (environment_base.py:190-193), like dynenv_seed: every environment draws from `seed` from now on -
+ * the next reset's scene, and the step-time draws of the running episode; nothing else changes (no blob does: the seed is in none) */
+int oracle_seed(oracle_t* o, uint64_t seed) {
+  int e;
+  o->cfg.seed = seed;
+  for (e = 0; e < o->cfg.num_envs; ++e) {
+    if (o->drv) o->drv[e].seed = seed;
+    else o->rc[e].seed = seed;
+  }
+  return DYNENV_OK;
+}
 int oracle_overflow(oracle_t* o) {
   int e, f = 0;
   for (e = 0; e < o->cfg.num_envs; ++e) f |= o->drv ? o->drv[e].space.overflow : o->rc[e].space.overflow;
@@ -250,6 +261,11 @@ void oracle_math_f(const double* x, int n, double* out) { /* dm_sincos_f: out[2 
 void oracle_philox(uint32_t k0, uint32_t k1, const uint32_t* ctr, uint32_t* out) {
   dm_u32x4 r = dm_philox(k0, k1, ctr[0], ctr[1], ctr[2], ctr[3]);
   memcpy(out, r.v, 16);
+}
+/* dm_env_rng itself: the key derivation every draw of both environments goes through (tests/test_rng_key_oracle.py) */
+void oracle_env_rng(uint64_t seed, uint32_t genv, uint32_t episode, uint32_t purpose, uint32_t entity, uint32_t t, uint32_t* out4) {
+  dm_u32x4 r = dm_env_rng(seed, genv, episode, purpose, entity, t);
+  memcpy(out4, r.v, 16);
 }
 void oracle_apply_friction(double m, double* vxyw, double friction, double rotFriction, double spin) {
   cpBody b;

@@ -96,6 +96,9 @@ def lib():
         _lib.oracle_road_is_point_on_road.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double]
         _lib.oracle_road_get_walk_spot.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
         _lib.oracle_apply_friction.argtypes = [C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_double]
+        _lib.oracle_seed.argtypes = [C.c_void_p, C.c_uint64]
+        _lib.oracle_env_rng.argtypes = [C.c_uint64] + [C.c_uint32] * 5 + [C.c_void_p]
+        _lib.oracle_env_rng.restype = None
     return _lib
 
 
@@ -138,6 +141,12 @@ class OracleEnv:
     def reset(self):
         self.l.oracle_reset(self.h, _p(self.obs))
         return self.obs
+
+    def seed(self, s):
+        """set_random_seed: every environment draws from seed `s` from now on; no state blob changes (oracle_seed)"""
+        rc = self.l.oracle_seed(self.h, int(s))
+        assert rc == 0
+        self.cfg.seed = int(s)
 
     def step(self, actions, head=None):
         """head: the continuous head channel [E, A] float64 of RoboCup with allowHeadTurn (Box(-3, 3)), else None"""
