@@ -78,10 +78,11 @@ EXPORTS = ["dynenv_abi_version", "dynenv_last_error", "dynenv_create", "dynenv_d
            "dynenv_checkpoint_save", "dynenv_checkpoint_load", "dynenv_obs_pack", "dynenv_obs_unpack", "dynenv_obs_unpack_ranks",
            "dynenv_obs_pack_peers", "dynenv_obs_unpack_peers_ranks", "dynenv_step_head", "dynenv_full_obs", "dynenv_full_obs_dim",
            "dynenv_global_state", "dynenv_global_state_dim", "dynenv_set_step_events", "dynenv_get_states", "dynenv_set_states",
-           "dynenv_error_flags_env", "dynenv_reset_masked", "dynenv_step_masked"]
+           "dynenv_error_flags_env", "dynenv_reset_masked", "dynenv_step_masked", "dynenv_exact_size", "dynenv_get_exact",
+           "dynenv_set_exact"]
 
-ERR_BAD_BLOB = 64  # error bit 6: a blob given to dynenv_set_states did not fit the handle and was not written
-SET_WRITTEN, SET_REJECTED, SET_BAD_INDEX = 0, 1, 2  # dynenv_set_states' per-blob status
+ERR_BAD_BLOB = 64  # error bit 6: a blob given to dynenv_set_states / dynenv_set_exact did not fit the handle and was not written
+SET_WRITTEN, SET_REJECTED, SET_BAD_INDEX = 0, 1, 2  # the per-blob status of dynenv_set_states and dynenv_set_exact
 
 
 def state_struct(env_type):
@@ -192,6 +193,10 @@ def load():
     lib.dynenv_get_states.argtypes = [vp, vp, C.c_int32, vp, vp]
     lib.dynenv_set_states.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
     lib.dynenv_error_flags_env.argtypes = [vp, vp, vp]
+    lib.dynenv_exact_size.argtypes = [vp]
+    lib.dynenv_exact_size.restype = C.c_size_t
+    lib.dynenv_get_exact.argtypes = [vp, vp, C.c_int32, vp, vp]
+    lib.dynenv_set_exact.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
     lib.dynenv_sync.argtypes = [vp, vp]
     lib.dynenv_math_selftest.argtypes = [vp, vp, C.c_int32, vp, C.c_int32]
     lib.dynenv_error_flags.argtypes = [vp, C.POINTER(C.c_int32)]

@@ -134,18 +134,19 @@ struct HOST_LOCAL DrvHandle final : dynenv {
     const size_t E = (size_t)cfg.num_envs;
     S.E = (int)E; S.A = A; S.obs_dim = full_dim; S.seed = cfg.seed; S.env_id_offset = cfg.env_id_offset;
     int rc = 0;
-    rc |= alloc(&S.body, (size_t)BF_COUNT * E * DRV_NB);
-    rc |= alloc(&S.carx, (size_t)CF_COUNT * E * 16);
-    rc |= alloc(&S.flags, E * DRV_NB);
-    rc |= alloc(&S.aux, E * DRV_NB);
-    rc |= alloc(&S.obst, 2 * E * DRV_MAXO);
-    rc |= alloc(&S.envi, E * EI_COUNT);
-    rc |= alloc(&S.epr, 2 * E * 16);
-    rc |= alloc(&S.s_pair, E * DRV_NS);
-    rc |= alloc(&S.s_meta, E * DRV_NS);
-    rc |= alloc(&S.s_hash, 2 * E * DRV_NS);
-    rc |= alloc(&S.s_imp, 4 * E * DRV_NS);
-    rc |= alloc(&S.lastcand, E * 64);
+    // (every checkpointed array is per-environment, [fields][E][row]: the row table of dynenv_get_exact / dynenv_set_exact)
+    rc |= alloc_rows(&S.body, BF_COUNT, DRV_NB);
+    rc |= alloc_rows(&S.carx, CF_COUNT, 16);
+    rc |= alloc_rows(&S.flags, 1, DRV_NB);
+    rc |= alloc_rows(&S.aux, 1, DRV_NB);
+    rc |= alloc_rows(&S.obst, 2, DRV_MAXO);
+    rc |= alloc_rows(&S.envi, 1, EI_COUNT);
+    rc |= alloc_rows(&S.epr, 2, 16);
+    rc |= alloc_rows(&S.s_pair, 1, DRV_NS);
+    rc |= alloc_rows(&S.s_meta, 1, DRV_NS);
+    rc |= alloc_rows(&S.s_hash, 2, DRV_NS);
+    rc |= alloc_rows(&S.s_imp, 4, DRV_NS);
+    rc |= alloc_rows(&S.lastcand, 1, 64);
     rc |= alloc(&S.iso, DRV_ISO_WORDS, SCRATCH);
     rc |= alloc(&S.iso_done, E, SCRATCH);
     rc |= alloc(&S.iso_hw, 2 * 4 * DRV_ISO_GROUPS, SCRATCH);

@@ -12,6 +12,10 @@
 #include "dynenv_host.h"
 #include "robocup_host.hip"
 
+// the kernels of env_rows_kernels.hip, which this unit includes last (behind everything the step launches run)
+extern "C" __global__ void env_rows_save_kernel(EnvRowTable T, const int* __restrict__ idx, unsigned char* __restrict__ blobs);
+extern "C" __global__ void env_rows_load_kernel(EnvRowTable T, const int* __restrict__ idx, const unsigned char* __restrict__ blobs, int* __restrict__ status);
+
 static thread_local std::string g_err;
 int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -51,6 +55,7 @@ int dynenv_create(const dynenv_cfg_t* cfg, dynenv_t** out) {
   dynenv* h = cfg->env_type == DYNENV_ROBO_CUP ? new RcHandle() : drv_new_handle();
   h->cfg = *cfg;
   int rc = h->init();
+  if (!rc) rc = h->rows_finish();
   if (!rc) rc = h->alloc(&h->stage, h->state_bytes / 8 + 1, SCRATCH);  // (scratch: the checkpoint is `allocs`, in init()'s order)
   if (rc) { dynenv_destroy(h); return rc; }
   *out = h;
@@ -242,6 +247,33 @@ int dynenv_set_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const 
   ON_DEVICE(h);
   return h->set_states(env_idx_dev, 0, n, blobs_dev, status_dev, true, (hipStream_t)stream);
 }
+
+// exact save / restore of chosen environments: every row of the handle's row table (dynenv_host.h), one launch each way of the two
+// kernels both handles share (env_rows_kernels.hip); the rules of dynenv_get_states / dynenv_set_states, 16-byte aligned blobs
+size_t dynenv_exact_size(const dynenv_t* h) { return h ? h->rows.blobBytes : 0; }
+static int exact_args(const dynenv_t* h, const int32_t* idx, int32_t n, const void* blobs) {
+  if (!h || (!blobs && n > 0)) return fail(DYNENV_ERR_ARG, "null argument");
+  if (n < 0) return fail(DYNENV_ERR_ARG, "negative blob count");
+  if (!idx && n > h->cfg.num_envs) return fail(DYNENV_ERR_ARG, "more blobs than environments and no index list");
+  if ((uintptr_t)blobs % 16) return fail(DYNENV_ERR_ARG, "the exact blobs must be 16-byte aligned");
+  return DYNENV_OK;
+}
+int dynenv_get_exact(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, void* blobs_dev, void* stream) {
+  if (int rc = exact_args(h, env_idx_dev, n, blobs_dev)) return rc;
+  if (n == 0) return DYNENV_OK;
+  ON_DEVICE(h);
+  hipLaunchKernelGGL(env_rows_save_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, h->rows, (const int*)env_idx_dev, (unsigned char*)blobs_dev);
+  return launched();
+}
+int dynenv_set_exact(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const void* blobs_dev, int32_t* status_dev, void* stream) {
+  if (int rc = exact_args(h, env_idx_dev, n, blobs_dev)) return rc;
+  if (n == 0) return DYNENV_OK;
+  ON_DEVICE(h);
+  hipLaunchKernelGGL(env_rows_load_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, h->rows, (const int*)env_idx_dev, (const unsigned char*)blobs_dev,
+                     (int*)status_dev);
+  return launched();
+}
+
 int dynenv_error_flags_env(dynenv_t* h, int32_t* flags_dev, void* stream) {
   if (!h || !flags_dev) return fail(DYNENV_ERR_ARG, "null argument");
   ON_DEVICE(h);
@@ -488,3 +520,4 @@ int dynenv_checkpoint_load(dynenv_t* h, const void* buf_host, size_t nbytes) {
 
 // device code only, behind everything above: no kernel a step launches moves (rc_layout_pad, robocup_kernels.hip)
 #include "robocup_reset.hip"
+#include "env_rows_kernels.hip"

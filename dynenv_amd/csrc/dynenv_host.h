@@ -37,6 +37,33 @@ struct DeviceGuard {
   } while (0)
 static inline int launched() { HIP_OK(hipGetLastError()); return DYNENV_OK; }  // behind an entry point's (last) kernel launch
 
+// One description of a handle's per-environment rows: every checkpointed array of the shape [fields][E][row], in allocation order
+// (alloc_rows below).  env_rows_save_kernel / env_rows_load_kernel (env_rows_kernels.hip, in the dynenv_capi.hip unit) take it by value
+// and copy an environment's rows to / from an exact blob: a 16-byte header (the layout tag, then zeros), then every array's rows
+// field-major at blobOff, each array's part padded with zero words to a multiple of 16 bytes.  A "unit" is one access of 1 << wlog
+// bytes: 16 or 8 where the row's size allows (bases come from hipMalloc, blobs are 16-byte aligned and each part starts 16-byte
+// aligned), else 4.
+#define ENV_ROWS_MAX 16
+struct EnvRowArr {
+  char* base;
+  unsigned long long fieldStride;   // bytes between two fields = E * rowBytes
+  uint32_t rowBytes, blobOff;       // bytes of one environment's row of one field; where the array's rows start in the blob
+  uint32_t unitsPerRow, units;      // units of one row, and of all `fields` rows
+  uint16_t fields, elemBytes;
+  uint8_t wlog, trips, padWords, next;  // trips = wave iterations = ceil(units / 64); padWords = zero words behind the rows (the kernel takes them from padAt); next array of this wlog (n: none)
+};
+struct EnvRowTable {
+  int n, E;
+  int errStride, errIndex;          // the environment's error word: err[e * errStride + errIndex]
+  int* err;
+  unsigned long long tag;           // layout tag: never 0, so a zero-filled buffer is no blob
+  uint32_t blobBytes;               // dynenv_exact_size
+  int first[3];                     // first array whose wlog is 4, 3, 2 (n: none)
+  int nPad;                         // the zero words behind the arrays' parts, all of them: lane l < nPad writes the word at byte padAt[l]
+  uint32_t padAt[3 * ENV_ROWS_MAX];
+  EnvRowArr arr[ENV_ROWS_MAX];
+};
+
 struct HOST_LOCAL dynenv {
   dynenv_cfg_t cfg;
   int A = 0, obs_dim = 0, T = 0, action_dim = 0;
@@ -45,6 +72,7 @@ struct HOST_LOCAL dynenv {
   std::vector<void*> allocs;
   std::vector<size_t> alloc_bytes;  // checkpoint = these arrays, in allocation order
   std::vector<void*> scratch;       // scheduling scratch (SIMD-isolation lists), `stage`: NOT simulation state, never checkpointed
+  EnvRowTable rows = {};            // the per-environment arrays among `allocs` (alloc_rows), completed by rows_finish()
   // where dynenv_get_state / dynenv_set_state keep their one blob on the device: state_bytes, then the status word (dynenv_create;
   // a handle is used by one thread at a time: dynenv.h)
   unsigned long long* stage = nullptr;
@@ -103,6 +131,51 @@ struct HOST_LOCAL dynenv {
     if (is_scratch) scratch.push_back(p);
     else { allocs.push_back(p); alloc_bytes.push_back(count * sizeof(X)); }
     *out = (X*)p;
+    return 0;
+  }
+  // a checkpointed array of the shape [fields][E][rowElems]: alloc() of that many elements, and one entry of the row table
+  template <typename X>
+  int alloc_rows(X** out, size_t fields, size_t rowElems) {
+    const size_t E = (size_t)cfg.num_envs;
+    if (rows.n >= ENV_ROWS_MAX || fields > 0xFFFF || sizeof(X) > 0xFFFF || rowElems * sizeof(X) % 4 || rowElems * sizeof(X) > 0x7FFFFFFF)
+      return fail(DYNENV_ERR_HIP, "internal: a per-environment array does not fit the row table");
+    if (int rc = alloc(out, fields * E * rowElems)) return rc;
+    EnvRowArr& a = rows.arr[rows.n++];
+    a.base = (char*)*out; a.rowBytes = (uint32_t)(rowElems * sizeof(X)); a.fieldStride = (unsigned long long)E * a.rowBytes;
+    a.fields = (uint16_t)fields; a.elemBytes = (uint16_t)sizeof(X);
+    return 0;
+  }
+  // behind init(): access widths, blob offsets and the layout tag - a function of the configuration's env_type, n_players, obs_type and
+  // flags and of every array's shape, NOT of num_envs, env_id_offset, seed or noise: a blob fits any handle of the same configuration
+  int rows_finish() {
+    unsigned long long tag = 0xcbf29ce484222325ull;  // FNV-1a over 32-bit words
+    auto mix = [&tag](uint32_t w) { for (int k = 0; k < 4; ++k) { tag ^= (w >> (8 * k)) & 0xFF; tag *= 0x100000001b3ull; } };
+    mix(0x58455644u /* "DVEX" */); mix((uint32_t)cfg.env_type); mix((uint32_t)cfg.n_players); mix((uint32_t)cfg.obs_type); mix((uint32_t)cfg.flags);
+    size_t off = 16;
+    rows.nPad = 0;
+    for (int i = 0; i < rows.n; ++i) {
+      EnvRowArr& a = rows.arr[i];
+      a.wlog = a.rowBytes % 16 == 0 ? 4 : a.rowBytes % 8 == 0 ? 3 : 2;
+      a.unitsPerRow = a.rowBytes >> a.wlog; a.units = a.unitsPerRow * a.fields;
+      const size_t bytes = (size_t)a.rowBytes * a.fields, trips = (a.units + 63) / 64;
+      if (trips > 0xFF || off + bytes + 16 > 0x7FFFFFFF) return fail(DYNENV_ERR_HIP, "internal: a per-environment array does not fit the row table");
+      a.trips = (uint8_t)trips; a.blobOff = (uint32_t)off; a.padWords = (uint8_t)((16 - bytes % 16) % 16 / 4);
+      for (int k = 0; k < a.padWords; ++k) rows.padAt[rows.nPad++] = (uint32_t)(off + bytes) + 4 * k;
+      off += bytes + 4 * a.padWords;
+      mix(a.fields); mix(a.rowBytes); mix(a.elemBytes);
+    }
+    for (int w = 0; w < 3; ++w) {  // the arrays of one access width, chained in table order
+      int prev = -1;
+      rows.first[w] = rows.n;
+      for (int i = 0; i < rows.n; ++i) {
+        if (rows.arr[i].wlog != 4 - w) continue;
+        if (prev < 0) rows.first[w] = i; else rows.arr[prev].next = (uint8_t)i;
+        rows.arr[i].next = (uint8_t)rows.n;
+        prev = i;
+      }
+    }
+    rows.E = cfg.num_envs; rows.err = const_cast<int*>(err_array); rows.errStride = err_stride; rows.errIndex = err_index;
+    rows.tag = tag ? tag : 1; rows.blobBytes = (uint32_t)off;
     return 0;
   }
 };

@@ -32,25 +32,26 @@ struct HOST_LOCAL RcHandle final : dynenv {
     A = R.R; obs_dim = R.obs_dim; T = 5; action_dim = 4;
     full_dim = rc_full_row(R.R); global_dim = R.R * 6 + 3; state_bytes = sizeof(dynenv_robocup_state_t);
     int rc = 0;
-    rc |= alloc(&R.body, (size_t)(RB_COUNT + 4) * E * RC_NB);
-    rc |= alloc(&R.rob, (size_t)RR_COUNT * E * 16);
-    rc |= alloc(&R.robi, (size_t)RI_COUNT * E * 16);
-    rc |= alloc(&R.envi, E * RE_COUNT);
-    rc |= alloc(&R.envd, E * RD_COUNT);
-    rc |= alloc(&R.epr, 2 * E * 16);
-    rc |= alloc(&R.epo, E * 16);
-    rc |= alloc(&R.snap, E * 5);
-    rc |= alloc(&R.prew0, E * 16);
+    // (per-environment arrays, [fields][E][row]: the row table of dynenv_get_exact / dynenv_set_exact)
+    rc |= alloc_rows(&R.body, RB_COUNT + 4, RC_NB);
+    rc |= alloc_rows(&R.rob, RR_COUNT, 16);
+    rc |= alloc_rows(&R.robi, RI_COUNT, 16);
+    rc |= alloc_rows(&R.envi, 1, RE_COUNT);
+    rc |= alloc_rows(&R.envd, 1, RD_COUNT);
+    rc |= alloc_rows(&R.epr, 2, 16);
+    rc |= alloc_rows(&R.epo, 1, 16);
+    rc |= alloc_rows(&R.snap, 1, 5);
+    rc |= alloc_rows(&R.prew0, 1, 16);
     // (per-step scratch of the Partial observation - who deferred what, the seen counts in transit, the scheduling forecast: rebuilt
     //  by every step, never part of a checkpoint, whose bytes stay a function of the simulation state alone)
     rc |= alloc(&R.seenPart, (size_t)E * 5 * 10 * RCP_SEEN_STRIDE, SCRATCH);
     rc |= alloc(&R.deferList, (size_t)E + 1 + 8, SCRATCH);
-    rc |= alloc(&R.s_pair, E * RC_NS);
-    rc |= alloc(&R.s_meta, E * RC_NS);
-    rc |= alloc(&R.s_hash, 2 * E * RC_NS);
-    rc |= alloc(&R.s_imp, 4 * E * RC_NS);
+    rc |= alloc_rows(&R.s_pair, 1, RC_NS);
+    rc |= alloc_rows(&R.s_meta, 1, RC_NS);
+    rc |= alloc_rows(&R.s_hash, 2, RC_NS);
+    rc |= alloc_rows(&R.s_imp, 4, RC_NS);
     uint64_t* pairTab = nullptr;
-    rc |= alloc(&pairTab, 64 * 2);
+    rc |= alloc(&pairTab, 64 * 2);  // (constant, not per-environment: checkpointed, but no row of the table)
     if (rc) return DYNENV_ERR_HIP;
     R.pairTab = pairTab;
     err_array = R.envi; err_stride = RE_COUNT; err_index = RE_ERR;

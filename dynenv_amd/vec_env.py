@@ -492,7 +492,7 @@ class BatchedDynEnv(object):
             return ids, int(ids.numel())
         host = np.asarray(env_ids.numpy() if isinstance(env_ids, torch.Tensor) else env_ids).reshape(-1).astype(np.int64)
         if unique and np.unique(host).size != host.size:
-            raise _capi.DynEnvError("set_states: an environment id is listed twice (its state would be unspecified)")
+            raise _capi.DynEnvError("set_states / set_exact: an environment id is listed twice (its state would be unspecified)")
         if host.size and (host.min() < -2 ** 31 or host.max() >= 2 ** 31):
             raise _capi.DynEnvError("environment ids must fit int32")
         return torch.as_tensor(host.astype(np.int32)).to(self.device), int(host.size)
@@ -555,14 +555,94 @@ class BatchedDynEnv(object):
             self._needs_reset = False
         return status
 
-    def fork(self, src_ids, dst_ids):
+    def fork(self, src_ids, dst_ids, exact=False):
         """Copy the state of environment src_ids[k] over environment dst_ids[k] - set_states(dst_ids, get_states(src_ids)): two launches,
         no host copy.  One source may be listed many times (branch one state into many environments), a destination once.  Like
         set_state, the copy drops the contact cache (warm-started impulses), so source and copy are the same canonical state, not the
         same checkpoint.  A forked environment keeps its OWN random stream: draws are keyed by the environment's global id, the
         episode counter and the time inside the episode, and the id is the destination's - so the copy's later random events
-        (pedestrian starts, observation noise, ...) are its own, not a replay of the source's.  Returns set_states' status tensor."""
+        (pedestrian starts, observation noise, ...) are its own, not a replay of the source's.  Returns set_states' status tensor.
+
+        exact=True: the copy goes through get_exact / set_exact instead and carries EVERY row of the source - the contact cache with its
+        warm-start impulses, the shortcut state and call-to-call caches, the diagnostic counters and the error word (a source with a
+        sticky error bit hands it on; nothing is cleared) - so source and copy are the same checkpoint.  The copy still draws from the
+        destination's own random streams.  Returns set_exact's status tensor."""
+        if exact:
+            return self.set_exact(dst_ids, self.get_exact(src_ids))
         return self.set_states(dst_ids, self.get_states(src_ids))
+
+    # ------------------------------------------------------------------ exact, device-side save and restore
+    @property
+    def exact_size(self):
+        """bytes of one exact blob (a multiple of 16)"""
+        return int(self._lib.dynenv_exact_size(self._h))
+
+    def get_exact(self, env_ids=None, out=None):
+        """The exact blobs of `env_ids` (a list, a numpy array or a device tensor; None = all environments, in order) as a torch.uint8
+        [n, exact_size] tensor on the device: ONE launch on torch's current stream, nothing is waited for and nothing touches the
+        host; capturable.  An exact blob is every simulation-state row of the environment, bit for bit - what checkpoint() keeps of it,
+        contact cache, shortcut state, counters and error word included - behind a 16-byte header; its format is opaque and valid for
+        this library build and this configuration (environment type, players, observation type, flags; NOT num_envs, env_id_offset,
+        seed or noise: a blob fits another environment and another handle of the same configuration).  set_exact() of it followed by
+        the same actions reproduces the run bit for bit, random draws included (they are keyed by the environment's id, episode
+        counter and time, and the last two travel in the blob).  `out`: a contiguous uint8 [n, exact_size] device tensor to write into;
+        the row of an id outside [0, num_envs) is left as it is."""
+        torch = self._torch
+        ids, n = self._env_ids(env_ids)
+        size = self.exact_size
+        if out is None:
+            out = torch.empty((n, size), dtype=torch.uint8, device=self.device)
+        elif (out.dtype != torch.uint8 or out.device != self.device or tuple(out.shape) != (n, size) or not out.is_contiguous()
+              or out.data_ptr() % 16):
+            raise _capi.DynEnvError("get_exact: out must be a contiguous, 16-byte aligned uint8 [%d, %d] tensor on %s" % (n, size, self.device))
+        _capi.check(self._lib.dynenv_get_exact(self._h, C.c_void_p(ids.data_ptr() if ids is not None and n else None), n,
+                                               C.c_void_p(out.data_ptr() if n else None), self._stream()), "dynenv_get_exact")
+        return out
+
+    def set_exact(self, env_ids, blobs, episode_step=None):
+        """Write exact blob blobs[k] (get_exact) into environment env_ids[k] (None = environments 0..n-1), all in ONE launch on torch's
+        current stream; capturable when `env_ids` and `blobs` are device tensors (their contents are read at replay; an id of -1
+        switches its slot off).  `blobs` is a uint8 [n, exact_size] device tensor (used in place) or a numpy array (one upload).  Every
+        row of a listed environment ends up with exactly the saved bytes - error word and diagnostic counters included - and nothing
+        else changes.  Returns the per-blob status as an int32 [n] device tensor (not read here): 0 written, 1 the blob does not carry
+        this configuration's layout tag (a buffer nobody wrote, a blob of another configuration) - the environment is untouched and
+        carries error bit 6 until it is reset or validly set, step() raises on it -, 2 id outside [0, num_envs).
+
+        Lock-step handles: the host's position in the episode stays where it is unless `episode_step` says where the batch now stands
+        (set_states' rule; a roll-back of k steps of the whole batch passes the position it saved at); on a handle that was never reset
+        pass `episode_step`.  Duplicate ids in one call are an error (raised when the ids live on the host)."""
+        torch = self._torch
+        if self._needs_reset and episode_step is None and not self.per_env:
+            raise _capi.DynEnvError("set_exact before the first reset(): pass episode_step (the batch's position in its lock-step episode)")
+        ids, n = self._env_ids(env_ids, unique=True)
+        size = self.exact_size
+        if isinstance(blobs, torch.Tensor):
+            b = blobs
+            if b.dtype != torch.uint8:
+                raise _capi.DynEnvError("set_exact: blobs must be uint8 [n, %d]" % size)
+            if b.device != self.device or not b.is_contiguous() or b.data_ptr() % 16:
+                b = b.to(self.device).contiguous().clone()
+        else:
+            b = torch.as_tensor(np.ascontiguousarray(blobs, dtype=np.uint8)).to(self.device)
+        if b.dim() != 2 or b.shape[1] != size:
+            raise _capi.DynEnvError("set_exact: blobs must be uint8 [n, %d], got shape %s" % (size, tuple(b.shape)))
+        if ids is None:
+            n = int(b.shape[0])  # environments 0..n-1
+            if n > self.num_envs:
+                raise _capi.DynEnvError("set_exact: %d blobs for %d environments" % (n, self.num_envs))
+        elif int(b.shape[0]) != n:
+            raise _capi.DynEnvError("set_exact: %d environment ids but %d blobs" % (n, int(b.shape[0])))
+        status = torch.empty((n,), dtype=torch.int32, device=self.device)
+        _capi.check(self._lib.dynenv_set_exact(self._h, C.c_void_p(ids.data_ptr() if ids is not None and n else None), n,
+                                               C.c_void_p(b.data_ptr() if n else None), C.c_void_p(status.data_ptr() if n else None),
+                                               self._stream()), "dynenv_set_exact")
+        self._counts_np = None  # the scenes (obstacle / pedestrian counts) may have changed
+        if episode_step is not None:
+            self._episode_step = int(episode_step)
+            self._needs_reset = False
+        elif self.per_env:
+            self._needs_reset = False
+        return status
 
     def error_flags_per_env(self):
         """Every environment's error word (the bits of include/dynenv.h's dynenv_error_flags) as an int32 [num_envs] device tensor: one
@@ -718,8 +798,8 @@ class BatchedDynEnv(object):
                                     % self._first_env_with(16))
         if flags & _capi.ERR_BAD_BLOB:
             # a blob that did not fit the handle was refused by set_states: that environment still holds its OLD state - never silently
-            raise _capi.DynEnvError("set_states: a blob did not fit this handle and was not written (error bit 6): environment %d still holds its "
-                                    "earlier state; a valid set_states() of it or reset() clears the bit" % self._first_env_with(_capi.ERR_BAD_BLOB))
+            raise _capi.DynEnvError("set_states / set_exact: a blob did not fit this handle and was not written (error bit 6): environment %d still holds its "
+                                    "earlier state; a valid set_states() / set_exact() of it or reset() clears the bit" % self._first_env_with(_capi.ERR_BAD_BLOB))
         done = bool(self.last_done)
         dones = np.full((self.num_envs,), done, dtype=bool)
         # The step's observations stay in HBM (a snapshot: self.obs is rewritten by the next step) until somebody looks at them:

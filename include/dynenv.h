@@ -16,6 +16,7 @@
  *                           RoboCupEnvironment.py:516-521)
  *   dynenv_seed          <- DynEnv/environment_base.py:190-193 set_random_seed
  *   dynenv_get/set_state <- (no reference equivalent; SURVEY §5 "checkpoint/resume" + parity tests)
+ *   dynenv_get/set_exact <- (no reference equivalent: exact save / restore of chosen environments on the device, for lookahead)
  *   dynenv_destroy       <- SubprocVecEnv.close (subproc_vec_env.py:124-133)
  *
  * All functions return 0 on success, <0 on error (dynenv_last_error() gives the text).  Pointers named *_dev are
@@ -272,6 +273,36 @@ int dynenv_set_state(dynenv_t* h, int32_t env_idx, const void* host_blob, size_t
 int dynenv_get_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, void* blobs_dev, void* stream);
 int dynenv_set_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const void* blobs_dev, int32_t* status_dev, void* stream);
 
+/* ---- exact save / restore of CHOSEN environments on the device (no reference equivalent; the reference has no state transfer at all).
+ * The canonical blob above drops the contact cache, so an environment in contact that is set and replayed is not the run it was saved
+ * from; dynenv_checkpoint_save is exact but goes through host memory, for the whole handle, and synchronises.  An EXACT BLOB is every
+ * simulation-state row of one environment bit for bit - bodies, contact cache (pair / meta / hash tables, warm-start impulses), shortcut
+ * state and call-to-call caches, joints' accumulated impulses and pending forces, episode accumulators and counter, elapsed time,
+ * diagnostic counters, the error word - i.e. the environment's part of every checkpointed per-environment array; the scheduler's
+ * scratch (timing only) is no part of it.  Since every random draw is keyed by (seed, global id, episode, purpose, entity, time) and
+ * episode and time are in those rows, dynenv_set_exact + the same actions reproduces the run from dynenv_get_exact bit for bit.
+ *   The blob: a 16-byte header (a 64-bit layout tag, then zeros), then the rows.  dynenv_exact_size(h) bytes, a multiple of 16 (0 for
+ *   a NULL handle).  The format is opaque: valid for the same library build and the same configuration.  The tag is a hash of env_type,
+ *   n_players, obs_type, flags and the shape of every per-environment array - NOT of num_envs, env_id_offset, seed or noise settings: a
+ *   blob may go into another environment index and into another handle of the same configuration with another batch size (it then
+ *   draws from that environment's own random streams).
+ * blobs_dev holds n blobs dynenv_exact_size(h) apart, 16-byte aligned; env_idx_dev int32 [n] names the environment of each, NULL =
+ * environments 0..n-1.  Both calls are ONE launch ordered on `stream` - no host synchronisation, no allocation, no host copy - and may
+ * be captured into a hipGraph: pointers and n are frozen, indices and blob contents are read at replay (an index of -1 switches a slot
+ * off).
+ *   dynenv_get_exact  writes every byte of the blob of each listed environment; an index outside [0, E) leaves its blob untouched.
+ *   dynenv_set_exact  a blob with this handle's tag: every per-environment row of the destination ends up with exactly the saved bytes
+ *                     (error word, diagnostic counters and Driving Partial's deferred-observation word included); nothing else changes.
+ *                     What stands behind a valid tag is trusted, as dynenv_checkpoint_load trusts its buffer.  Any other tag (a buffer
+ *                     nobody wrote, a blob of another configuration): the environment is untouched and error bit 6 is raised on it.
+ *                     status_dev (may be NULL) int32 [n]: 0 written, 1 blob rejected, 2 index outside [0, E) (entry skipped).
+ *                     The same index twice in one call is a caller error: that environment's state is unspecified then.
+ * Errors: NULL handle, n < 0, NULL blobs_dev with n > 0, blobs_dev not 16-byte aligned, more blobs than environments without an index
+ * list -> DYNENV_ERR_ARG (before a device is looked for); n == 0 -> DYNENV_OK, nothing launched. */
+size_t dynenv_exact_size(const dynenv_t* h);
+int dynenv_get_exact(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, void* blobs_dev, void* stream);
+int dynenv_set_exact(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const void* blobs_dev, int32_t* status_dev, void* stream);
+
 int dynenv_sync(dynenv_t* h, void* stream);
 
 /* OR over all environments of the kernels' error flags (bit 0: contact cache or candidate list overflow - an environment had
@@ -292,8 +323,9 @@ int dynenv_sync(dynenv_t* h, void* stream);
  * set_state; the host mirror's step() raises on it; bit 5 (value 32):
  * RoboCup, a foot velocity or a joint impulse left the finite range during a solve (never seen): the joints' arithmetic drops
  * products that are zeros for finite operands only, so that substep is not the reference's - reported like bit 4.
- * bit 6 (value 64): a blob given to dynenv_set_states did not fit the handle's layout and was NOT written; sticky on that environment until
- * the next reset or the next valid set_state / set_states of it; the host mirror's step() raises on it.
+ * bit 6 (value 64): a blob given to dynenv_set_states did not fit the handle's layout, or a blob given to dynenv_set_exact did not
+ * carry the handle's layout tag, and was NOT written; sticky on that environment until the next reset or the next valid set_state /
+ * set_states / set_exact of it (a valid exact blob brings its own error word, saved with the rest); the host mirror's step() raises on it.
  * Synchronises the device. */
 int dynenv_error_flags(dynenv_t* h, int32_t* out);
 /* The per-environment error words themselves (the bits above): flags_dev int32 [E], ordered on `stream`, no synchronisation - to
