@@ -910,29 +910,27 @@ DE_DEV int drv_slot_verdicts(int lane, int pk, int a_pair, bool restIn, bool bia
   // steady: re-running this slot on identical inputs (same frozen positions, bodies at rest) reproduces this substep
   // bit for bit: the slot record is unchanged (same contact ids, same accumulated impulses, NORMAL before and after, or
   // ignored) and both bodies were at rest before the prestep and after the solve.  See DESIGN.md "steady replay".
-  bool steady = true;
-  if (slotOcc && !skipped) {
-    steady = touched && !freeMe && hashSame;
-    if (steady && a_state != ARB_IGNORE) {
-      steady = a_state == ARB_NORMAL && wasNormal && restIn && L.s_jn0[lane] == jn0 && L.s_jt0[lane] == jt0 &&
-               L.s_jn1[lane] == jn1 && L.s_jt1[lane] == jt1;
-      if (steady) {
-        const int i = a_pair >> 8, j = a_pair & 0xFF;
-        steady = L.vx[i] == 0.0 && L.vy[i] == 0.0 && L.w[i] == 0.0;
-        if (j < DRV_SLOT_OBST) steady = steady && L.vx[j] == 0.0 && L.vy[j] == 0.0 && L.w[j] == 0.0;
-      }
-    }
-  }
+  // Its ten LDS operands - the slot's four stored impulses, three velocity words of either body - are loaded in ONE batch ahead
+  // of every comparison and the comparisons are joined without short circuit: written as a chain of &&, each load was issued
+  // behind the comparison of the one before it, ten LDS round trips in a row for exactly the slots that pass (a resting pile).
+  // Every lane reads in bounds: a lane without a slot reads slot 0, a free slot's pair 0xFFFF and a static partner read the
+  // all-zero body slot (body_rd), whose +0 words compare as the test that used to be skipped came out.
+  const int sl = lane < DRV_NS ? lane : 0;
+  const int vi = body_rd(a_pair >> 8), vj = body_rd(a_pair & 0xFF);
+  double o_jn0 = L.s_jn0[sl], o_jt0 = L.s_jt0[sl], o_jn1 = L.s_jn1[sl], o_jt1 = L.s_jt1[sl];
+  double vix = L.vx[vi], viy = L.vy[vi], wi = L.w[vi], vjx = L.vx[vj], vjy = L.vy[vj], wj = L.w[vj];
+  // (all ten live at one point: without it the scheduler, which minimises registers, issues them in three groups, each behind the
+  //  comparisons of the group before - seen in the ISA)
+  asm volatile("" : "+v"(o_jn0), "+v"(o_jt0), "+v"(o_jn1), "+v"(o_jt1), "+v"(vix), "+v"(viy), "+v"(wi), "+v"(vjx), "+v"(vjy), "+v"(wj));
+  const bool sameImpulses = (o_jn0 == jn0) & (o_jt0 == jt0) & (o_jn1 == jn1) & (o_jt1 == jt1);
+  const bool restOut = (vix == 0.0) & (viy == 0.0) & (wi == 0.0) & (vjx == 0.0) & (vjy == 0.0) & (wj == 0.0);
+  // (both verdicts as straight-line logic on registers: as nested ifs they were three and four branch regions a call)
+  const bool fresh = touched & !freeMe, ignored = a_state == ARB_IGNORE, normalRun = (a_state == ARB_NORMAL) & wasNormal;
+  const bool steady = !(slotOcc & !skipped) | (fresh & hashSame & (ignored | (normalRun & restIn & sameImpulses & restOut)));
   const bool allSteady = wave_ballot(!steady) == 0ull;
   // inert: touched, not first contact, and (ignored | zero bias and zero accumulated impulses on every contact)
-  bool inert = true;
-  if (slotOcc && skipped) inert = prevInert;
-  else if (slotOcc) {
-    inert = touched && !freeMe &&
-            (a_state == ARB_IGNORE ||
-             (a_state == ARB_NORMAL && wasNormal && biasZ0 && biasZ1 && jn0 == 0.0 && jt0 == 0.0 &&
-              jn1 == 0.0 && jt1 == 0.0 && jBias0 == 0.0 && jBias1 == 0.0));
-  }
+  const bool zeroImpulses = biasZ0 & biasZ1 & (jn0 == 0.0) & (jt0 == 0.0) & (jn1 == 0.0) & (jt1 == 0.0) & (jBias0 == 0.0) & (jBias1 == 0.0);
+  const bool inert = !slotOcc | (skipped ? prevInert : (fresh & (ignored | (normalRun & zeroImpulses))));
   if (slotOcc) {
     if (freeMe) L.s_pair[lane] = 0xFFFF;
     L.s_meta[lane] = a_state | (a_count << 8) | (a_age << 16) | (steady ? (1 << 24) : 0) | (inert ? (1 << 25) : 0);
@@ -1254,11 +1252,17 @@ DRV_PROF(const unsigned long long T1 = __builtin_amdgcn_s_memtime();)
   double jn[2] = {0.0, 0.0}, jt[2] = {0.0, 0.0};
   V2 n = v2(0.0, 0.0), r1[2], r2[2];
   r1[0] = r1[1] = r2[0] = r2[1] = v2(0.0, 0.0);
+  // Everything the slot lanes read of the mailbox and of the slot record, in one batch (as in drv_slot_verdicts: count and contact ids
+  // waited for the flag, the stored ids for the count, each carried impulse for the comparison of two ids - five LDS round trips in a
+  // row on every touched slot).  A lane without a slot reads slot 0, an untouched slot reads mailbox words nobody wrote: unused.
+  const int sl = lane < DRV_NS ? lane : 0;
+  int flag = M.flag[sl], cnt = M.count[sl], h0 = M.hash[sl][0], mh1 = M.hash[sl][1];
+  int s_pair = L.s_pair[sl], meta = L.s_meta[sl], oh0 = L.s_hash0[sl], oh1 = L.s_hash1[sl];
+  double o_jn0 = L.s_jn0[sl], o_jt0 = L.s_jt0[sl], o_jn1 = L.s_jn1[sl], o_jt1 = L.s_jt1[sl];
+  asm volatile("" : "+v"(flag), "+v"(cnt), "+v"(h0), "+v"(mh1), "+v"(s_pair), "+v"(meta), "+v"(oh0), "+v"(oh1), "+v"(o_jn0), "+v"(o_jt0), "+v"(o_jn1), "+v"(o_jt1));
   if (slotOcc) {
-    const int flag = M.flag[lane];
     touched = flag != 0;
-    a_pair = L.s_pair[lane];
-    int meta = L.s_meta[lane];
+    a_pair = s_pair;
     a_state = meta & 0xFF; a_count = (meta >> 8) & 0xFF; a_age = (meta >> 16) & 0xFF;
     prevSteady = (meta >> 24) & 1; prevInert = (meta >> 25) & 1;
     if (flag & 2) { a_state = ARB_FIRST; a_count = 0; a_age = 0; prevSteady = false; prevInert = false; }
@@ -1268,15 +1272,13 @@ DRV_PROF(const unsigned long long T1 = __builtin_amdgcn_s_memtime();)
       if (j >= DRV_SLOT_PED && j < DRV_SLOT_OBST) { bodyA = j; bodyB = i; } else { bodyA = i; bodyB = j; }
       const V2 pa = bodyA < DRV_SLOT_OBST ? v2(L.px[bodyA], L.py[bodyA]) : static_pos(L, bodyA);
       const V2 pb = bodyB < DRV_SLOT_OBST ? v2(L.px[bodyB], L.py[bodyB]) : static_pos(L, bodyB);
-      const int cnt = M.count[lane];
-      const int h0 = M.hash[lane][0], h1 = cnt > 1 ? M.hash[lane][1] : 0;
-      const int oh0 = L.s_hash0[lane], oh1 = L.s_hash1[lane];
+      const int h1 = cnt > 1 ? mh1 : 0;
       // carry impulses of contacts with matching hash (later match wins, as in Chipmunk's loop)
-      if (a_count > 0 && h0 == oh0) { jn[0] = L.s_jn0[lane]; jt[0] = L.s_jt0[lane]; }
-      if (a_count > 1 && h0 == oh1) { jn[0] = L.s_jn1[lane]; jt[0] = L.s_jt1[lane]; }
+      if (a_count > 0 && h0 == oh0) { jn[0] = o_jn0; jt[0] = o_jt0; }
+      if (a_count > 1 && h0 == oh1) { jn[0] = o_jn1; jt[0] = o_jt1; }
       if (cnt > 1) {
-        if (a_count > 0 && h1 == oh0) { jn[1] = L.s_jn0[lane]; jt[1] = L.s_jt0[lane]; }
-        if (a_count > 1 && h1 == oh1) { jn[1] = L.s_jn1[lane]; jt[1] = L.s_jt1[lane]; }
+        if (a_count > 0 && h1 == oh0) { jn[1] = o_jn0; jt[1] = o_jt0; }
+        if (a_count > 1 && h1 == oh1) { jn[1] = o_jn1; jt[1] = o_jt1; }
       }
       r1[0] = vsub(v2(M.p1x[lane][0], M.p1y[lane][0]), pa);
       r2[0] = vsub(v2(M.p2x[lane][0], M.p2y[lane][0]), pb);
@@ -1353,8 +1355,8 @@ DRV_PROF(const unsigned long long U3 = __builtin_amdgcn_s_memtime();)
   if (slotOcc) {
     const int pi = a_pair >> 8, pj = a_pair & 0xFF;
     myBodies = (1 << pi) | (pj < DRV_SLOT_OBST ? (1 << pj) : 0);
-    cleanSlot = solvable && prevSteady && a_state == ARB_NORMAL && hashSame && (L.still[pi] & 2) &&
-                (pj >= DRV_SLOT_OBST || (L.still[pj] & 2));
+    const int stillI = L.still[pi], stillJ = L.still[body_rd(pj)];  // (both loads issued; a static partner's word is not looked at)
+    cleanSlot = solvable && prevSteady && a_state == ARB_NORMAL && hashSame && ((stillI & 2) != 0) & (pj >= DRV_SLOT_OBST || (stillJ & 2));
   }
   int dirtyBodies = 0;
   if (wave_ballot(cleanSlot) != 0ull) {  // (usually nothing is clean: no closure to compute)
