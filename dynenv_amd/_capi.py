@@ -70,16 +70,74 @@ class RoboCupState(C.Structure):
 
 FLAG_RANDOM_INIT, FLAG_DETERMINISTIC_TURN, FLAG_CAN_FALL, FLAG_USE_OBS_REWARDS, FLAG_ALLOW_HEAD_TURN = 1, 2, 4, 8, 16
 
-EXPORTS = ["dynenv_abi_version", "dynenv_last_error", "dynenv_create", "dynenv_destroy", "dynenv_layout",
-           "dynenv_seed", "dynenv_reset", "dynenv_step", "dynenv_counts", "dynenv_episode_stats",
-           "dynenv_state_size", "dynenv_get_state", "dynenv_set_state", "dynenv_sync", "dynenv_math_selftest",
-           "dynenv_error_flags", "dynenv_debug_counters", "dynenv_debug_placement", "dynenv_arrange_scratch_ints", "dynenv_arrange_plan",
-           "dynenv_arrange_gather", "dynenv_arrange_scatter", "dynenv_arrange_pad", "dynenv_checkpoint_size",
-           "dynenv_checkpoint_save", "dynenv_checkpoint_load", "dynenv_obs_pack", "dynenv_obs_unpack", "dynenv_obs_unpack_ranks",
-           "dynenv_obs_pack_peers", "dynenv_obs_unpack_peers_ranks", "dynenv_step_head", "dynenv_full_obs", "dynenv_full_obs_dim",
-           "dynenv_global_state", "dynenv_global_state_dim", "dynenv_set_step_events", "dynenv_get_states", "dynenv_set_states",
-           "dynenv_error_flags_env", "dynenv_reset_masked", "dynenv_step_masked", "dynenv_exact_size", "dynenv_get_exact",
-           "dynenv_set_exact"]
+ARR_MAX_TYPES = 4
+ARR_COUNT_CONST, ARR_COUNT_ENV, ARR_COUNT_ROW = 0, 1, 2
+
+
+class ArrType(C.Structure):  # dynenv_arr_type_t
+    _fields_ = [("offset", C.c_int32), ("feat", C.c_int32), ("cap", C.c_int32), ("count_mode", C.c_int32),
+                ("count_value", C.c_int32), ("count_index", C.c_int32), ("count_stride", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class ArrPlan(C.Structure):  # dynenv_arr_plan_t
+    _fields_ = [("n_types", C.c_int32), ("n_time", C.c_int32), ("n_players", C.c_int32), ("max_count", C.c_int32),
+                ("total", C.c_int64 * ARR_MAX_TYPES)]
+
+
+vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
+
+# THE binding of include/dynenv.h: name -> (restype, argtypes), in the header's order of growth.  load() sets exactly these, so an entry
+# point cannot be exported without its argument types (a missing list would truncate pointers to int); tests/test_host_and_abi.py
+# holds every line against the header's prototype.
+SIGNATURES = {
+    "dynenv_abi_version": (C.c_int, []),
+    "dynenv_last_error": (C.c_char_p, []),
+    "dynenv_create": (C.c_int, [C.POINTER(Cfg), C.POINTER(vp)]),
+    "dynenv_destroy": (None, [vp]),
+    "dynenv_layout": (C.c_int, [vp, C.POINTER(Layout)]),
+    "dynenv_seed": (C.c_int, [vp, C.c_uint64]),
+    "dynenv_reset": (C.c_int, [vp, vp, vp]),
+    "dynenv_step": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "dynenv_counts": (C.c_int, [vp, vp, vp]),
+    "dynenv_episode_stats": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "dynenv_state_size": (sz, [vp]),
+    "dynenv_get_state": (C.c_int, [vp, i32, vp, sz]),
+    "dynenv_set_state": (C.c_int, [vp, i32, vp, sz]),
+    "dynenv_sync": (C.c_int, [vp, vp]),
+    "dynenv_math_selftest": (C.c_int, [vp, vp, i32, vp, i32]),
+    "dynenv_error_flags": (C.c_int, [vp, C.POINTER(i32)]),
+    "dynenv_debug_counters": (C.c_int, [vp, C.POINTER(i64)]),
+    "dynenv_debug_placement": (C.c_int, [vp, vp, i32]),
+    "dynenv_arrange_scratch_ints": (i64, [i32, i32, i32, i32]),
+    "dynenv_arrange_plan": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, vp, vp, vp, vp, C.POINTER(ArrPlan), vp]),
+    "dynenv_arrange_gather": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, vp, i32, C.POINTER(vp), C.POINTER(vp), vp, vp]),
+    "dynenv_arrange_scatter": (C.c_int, [vp, vp, i64, i32, vp, vp]),
+    "dynenv_arrange_pad": (C.c_int, [C.POINTER(vp), vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "dynenv_checkpoint_size": (sz, [vp]),
+    "dynenv_checkpoint_save": (C.c_int, [vp, vp, sz]),
+    "dynenv_checkpoint_load": (C.c_int, [vp, vp, sz]),
+    "dynenv_obs_pack": (C.c_int, [vp, i64, i32, i32, i32, vp, vp]),
+    "dynenv_obs_unpack": (C.c_int, [vp, i64, i32, i32, i32, vp, vp]),
+    "dynenv_obs_unpack_ranks": (C.c_int, [vp, i64, i32, i64, i32, i32, i32, vp, vp]),
+    "dynenv_obs_pack_peers": (C.c_int, [vp, i64, i32, i32, vp, vp]),
+    "dynenv_obs_unpack_peers_ranks": (C.c_int, [vp, i64, i32, i64, i32, i32, vp, vp]),
+    "dynenv_step_head": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+    "dynenv_full_obs": (C.c_int, [vp, vp, vp]),
+    "dynenv_full_obs_dim": (C.c_int, [vp]),
+    "dynenv_global_state": (C.c_int, [vp, vp, vp]),
+    "dynenv_global_state_dim": (C.c_int, [vp]),
+    "dynenv_set_step_events": (C.c_int, [vp, vp, vp, vp]),
+    "dynenv_get_states": (C.c_int, [vp, vp, i32, vp, vp]),
+    "dynenv_set_states": (C.c_int, [vp, vp, i32, vp, vp, vp]),
+    "dynenv_error_flags_env": (C.c_int, [vp, vp, vp]),
+    "dynenv_reset_masked": (C.c_int, [vp, vp, vp, vp]),
+    "dynenv_step_masked": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dynenv_exact_size": (sz, [vp]),
+    "dynenv_get_exact": (C.c_int, [vp, vp, i32, vp, vp]),
+    "dynenv_set_exact": (C.c_int, [vp, vp, i32, vp, vp, vp]),
+}
+EXPORTS = list(SIGNATURES)
 
 ERR_BAD_BLOB = 64  # error bit 6: a blob given to dynenv_set_states / dynenv_set_exact did not fit the handle and was not written
 SET_WRITTEN, SET_REJECTED, SET_BAD_INDEX = 0, 1, 2  # the per-blob status of dynenv_set_states and dynenv_set_exact
@@ -119,21 +177,6 @@ def states_as_blobs(states):
     a = np.ascontiguousarray(states)
     return a.reshape(-1).view(np.uint8).reshape(a.size, a.dtype.itemsize)
 
-ARR_MAX_TYPES = 4
-ARR_COUNT_CONST, ARR_COUNT_ENV, ARR_COUNT_ROW = 0, 1, 2
-
-
-class ArrType(C.Structure):  # dynenv_arr_type_t
-    _fields_ = [("offset", C.c_int32), ("feat", C.c_int32), ("cap", C.c_int32), ("count_mode", C.c_int32),
-                ("count_value", C.c_int32), ("count_index", C.c_int32), ("count_stride", C.c_int32),
-                ("reserved", C.c_int32)]
-
-
-class ArrPlan(C.Structure):  # dynenv_arr_plan_t
-    _fields_ = [("n_types", C.c_int32), ("n_time", C.c_int32), ("n_players", C.c_int32), ("max_count", C.c_int32),
-                ("total", C.c_int64 * ARR_MAX_TYPES)]
-
-
 _lib = None
 
 
@@ -146,66 +189,22 @@ def load():
         raise DynEnvError("libdynenv_hip.so is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(dynenv_amd has no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS:
+    for name, (restype, argtypes) in SIGNATURES.items():
         if not hasattr(lib, name):
             raise DynEnvError("libdynenv_hip.so does not export " + name)
-    lib.dynenv_last_error.restype = C.c_char_p
-    lib.dynenv_state_size.restype = C.c_size_t
-    vp = C.c_void_p
-    lib.dynenv_create.argtypes = [C.POINTER(Cfg), C.POINTER(vp)]
-    lib.dynenv_destroy.argtypes = [vp]
-    lib.dynenv_destroy.restype = None
-    lib.dynenv_layout.argtypes = [vp, C.POINTER(Layout)]
-    lib.dynenv_seed.argtypes = [vp, C.c_uint64]
-    lib.dynenv_reset.argtypes = [vp, vp, vp]
-    lib.dynenv_reset_masked.argtypes = [vp, vp, vp, vp]
-    lib.dynenv_step.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.dynenv_step_head.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.dynenv_step_masked.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.dynenv_full_obs.argtypes = [vp, vp, vp]
-    lib.dynenv_full_obs_dim.argtypes = [vp]
-    lib.dynenv_global_state.argtypes = [vp, vp, vp]
-    lib.dynenv_global_state_dim.argtypes = [vp]
-    lib.dynenv_set_step_events.argtypes = [vp, vp, vp, vp]
-    i32 = C.c_int32
-    lib.dynenv_arrange_scratch_ints.argtypes = [i32, i32, i32, i32]
-    lib.dynenv_arrange_scratch_ints.restype = C.c_int64
-    lib.dynenv_arrange_plan.argtypes = [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, vp, vp, vp, vp,
-                                        C.POINTER(ArrPlan), vp]
-    lib.dynenv_arrange_gather.argtypes = [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, vp, i32,
-                                          C.POINTER(vp), C.POINTER(vp), vp, vp]
-    lib.dynenv_arrange_scatter.argtypes = [vp, vp, C.c_int64, i32, vp, vp]
-    lib.dynenv_obs_pack.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
-    lib.dynenv_obs_unpack.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
-    lib.dynenv_obs_unpack_ranks.argtypes = [vp, C.c_int64, i32, C.c_int64, i32, i32, i32, vp, vp]
-    lib.dynenv_obs_pack_peers.argtypes = [vp, C.c_int64, i32, i32, vp, vp]
-    lib.dynenv_obs_unpack_peers_ranks.argtypes = [vp, C.c_int64, i32, C.c_int64, i32, i32, vp, vp]
-    lib.dynenv_checkpoint_size.argtypes = [vp]
-    lib.dynenv_checkpoint_size.restype = C.c_size_t
-    lib.dynenv_checkpoint_save.argtypes = [vp, vp, C.c_size_t]
-    lib.dynenv_checkpoint_load.argtypes = [vp, vp, C.c_size_t]
-    lib.dynenv_arrange_pad.argtypes = [C.POINTER(vp), vp, vp, i32, i32, i32, i32, i32, vp, vp]
-    lib.dynenv_counts.argtypes = [vp, vp, vp]
-    lib.dynenv_episode_stats.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.dynenv_state_size.argtypes = [vp]
-    lib.dynenv_get_state.argtypes = [vp, C.c_int32, vp, C.c_size_t]
-    lib.dynenv_set_state.argtypes = [vp, C.c_int32, vp, C.c_size_t]
-    lib.dynenv_get_states.argtypes = [vp, vp, C.c_int32, vp, vp]
-    lib.dynenv_set_states.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
-    lib.dynenv_error_flags_env.argtypes = [vp, vp, vp]
-    lib.dynenv_exact_size.argtypes = [vp]
-    lib.dynenv_exact_size.restype = C.c_size_t
-    lib.dynenv_get_exact.argtypes = [vp, vp, C.c_int32, vp, vp]
-    lib.dynenv_set_exact.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
-    lib.dynenv_sync.argtypes = [vp, vp]
-    lib.dynenv_math_selftest.argtypes = [vp, vp, C.c_int32, vp, C.c_int32]
-    lib.dynenv_error_flags.argtypes = [vp, C.POINTER(C.c_int32)]
-    lib.dynenv_debug_counters.argtypes = [vp, C.POINTER(C.c_int64)]
-    lib.dynenv_debug_placement.argtypes = [vp, vp, C.c_int32]
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        if restype is not C.c_int:  # (ctypes' default, and faster left unset: ~50 ns a call, which step_flat's host cost shows)
+            fn.restype = restype
     if lib.dynenv_abi_version() != DYNENV_ABI_VERSION:
         raise DynEnvError("ABI version mismatch between dynenv_amd and libdynenv_hip.so")
     _lib = lib
     return lib
+
+
+def ptr(t):
+    """c_void_p of a tensor's data; None (an optional argument left out) stays None, the C side's NULL"""
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def check(rc, what):

@@ -52,10 +52,6 @@ class GpuInOutArranger(object):
     def _stream(self):
         return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
 
-    @staticmethod
-    def _p(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
     def rearrange_inputs(self, obs, count_env=None):
         """obs: dense float32 device tensor [E, T, A, D]; count_env: int32 [E, 2] from BatchedDynEnv.counts() when a type
         counts per environment.  Returns (inputs, (counts, maxCount, objCounts, slots)) like models.py:219-250:
@@ -64,9 +60,9 @@ class GpuInOutArranger(object):
         assert obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous()
         assert tuple(obs.shape) == (self.E, self.nTime, self.A, self.D), (tuple(obs.shape), (self.E, self.nTime, self.A, self.D))
         plan = _capi.ArrPlan()
-        _capi.check(self._lib.dynenv_arrange_plan(self._p(obs), self.E, self.nTime, self.A, self.D, self.types,
-                                                  self.nObjectTypes, self._p(count_env), self._p(self._counts),
-                                                  self._p(self._obj_counts), self._p(self._base), self._p(self._scratch),
+        _capi.check(self._lib.dynenv_arrange_plan(_capi.ptr(obs), self.E, self.nTime, self.A, self.D, self.types,
+                                                  self.nObjectTypes, _capi.ptr(count_env), _capi.ptr(self._counts),
+                                                  _capi.ptr(self._obj_counts), _capi.ptr(self._base), _capi.ptr(self._scratch),
                                                   C.byref(plan), self._stream()), "dynenv_arrange_plan")
         max_count = int(plan.max_count)
         inputs = [torch.empty((int(plan.total[i]), self.feats[i]), dtype=torch.float32, device=self.device)
@@ -76,9 +72,9 @@ class GpuInOutArranger(object):
         vp = C.c_void_p
         in_ptrs = (vp * self.nObjectTypes)(*[t.data_ptr() if t.numel() else None for t in inputs])
         sl_ptrs = (vp * self.nObjectTypes)(*[t.data_ptr() if t.numel() else None for t in slots])
-        _capi.check(self._lib.dynenv_arrange_gather(self._p(obs), self.E, self.nTime, self.A, self.D, self.types,
-                                                    self.nObjectTypes, self._p(self._counts), self._p(self._base), max_count,
-                                                    in_ptrs, sl_ptrs, self._p(mask) if max_count else vp(0), self._stream()),
+        _capi.check(self._lib.dynenv_arrange_gather(_capi.ptr(obs), self.E, self.nTime, self.A, self.D, self.types,
+                                                    self.nObjectTypes, _capi.ptr(self._counts), _capi.ptr(self._base), max_count,
+                                                    in_ptrs, sl_ptrs, _capi.ptr(mask) if max_count else vp(0), self._stream()),
                     "dynenv_arrange_gather")
         return inputs, (self._counts, max_count, self._obj_counts, slots, mask)
 
@@ -107,8 +103,8 @@ class GpuInOutArranger(object):
             padded = torch.empty((self.nTime, max_count, self.nPlayers, F), dtype=torch.float32, device=self.device)
             vp = C.c_void_p
             ptrs = (vp * self.nObjectTypes)(*[o.data_ptr() if (o is not None and o.shape[0]) else None for o in outs])
-            _capi.check(self._lib.dynenv_arrange_pad(ptrs, self._p(self._counts), self._p(self._base), self.nObjectTypes,
-                                                     self.nTime, self.nPlayers, max_count, F, self._p(padded),
+            _capi.check(self._lib.dynenv_arrange_pad(ptrs, _capi.ptr(self._counts), _capi.ptr(self._base), self.nObjectTypes,
+                                                     self.nTime, self.nPlayers, max_count, F, _capi.ptr(padded),
                                                      self._stream()), "dynenv_arrange_pad")
         else:  # odd widths: zero fill + one scatter per type
             padded = torch.zeros((self.nTime, max_count, self.nPlayers, F), dtype=torch.float32, device=self.device)
@@ -116,7 +112,7 @@ class GpuInOutArranger(object):
                 if out is None or out.shape[0] == 0:
                     continue
                 out = out.contiguous().float()
-                _capi.check(self._lib.dynenv_arrange_scatter(self._p(out), self._p(slots[i]), int(out.shape[0]), F,
-                                                             self._p(padded), self._stream()), "dynenv_arrange_scatter")
+                _capi.check(self._lib.dynenv_arrange_scatter(_capi.ptr(out), _capi.ptr(slots[i]), int(out.shape[0]), F,
+                                                             _capi.ptr(padded), self._stream()), "dynenv_arrange_scatter")
         masks = [mask[t].bool() for t in range(self.nTime)]
         return padded, masks

@@ -152,7 +152,7 @@ struct HOST_LOCAL DrvHandle final : dynenv {
     rc |= alloc(&S.iso_hw, 2 * 4 * DRV_ISO_GROUPS, SCRATCH);
     rc |= alloc(&S.pvq, 32 + 2 * (size_t)S.E, SCRATCH);
     if (rc) return DYNENV_ERR_HIP;
-    err_array = S.envi; err_stride = EI_COUNT; err_index = EI_ERR;
+    rows.err = S.envi; rows.errStride = EI_COUNT; rows.errIndex = EI_ERR;
     {
       // The slowest environments of the previous step get a SIMD to themselves (drv_iso_assign): only where the block -> SIMD
       // pattern it relies on was measured - 4096 environments = one residency round of a 256-CU device, four waves per SIMD.

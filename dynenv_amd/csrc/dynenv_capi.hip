@@ -182,10 +182,10 @@ int dynenv_error_flags(dynenv_t* h, int32_t* out) {
   if (!h || !out) return fail(DYNENV_ERR_ARG, "null argument");
   ON_DEVICE(h);
   HIP_OK(hipDeviceSynchronize());
-  std::vector<int> w((size_t)h->cfg.num_envs * h->err_stride);
-  HIP_OK(hipMemcpy(w.data(), h->err_array, w.size() * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> w((size_t)h->cfg.num_envs * h->rows.errStride);
+  HIP_OK(hipMemcpy(w.data(), h->rows.err, w.size() * sizeof(int), hipMemcpyDeviceToHost));
   int fl = 0;
-  for (size_t e = 0; e < (size_t)h->cfg.num_envs; ++e) fl |= w[e * h->err_stride + h->err_index];
+  for (size_t e = 0; e < (size_t)h->cfg.num_envs; ++e) fl |= w[e * h->rows.errStride + h->rows.errIndex];
   *out = fl;
   return DYNENV_OK;
 }
@@ -228,21 +228,22 @@ int dynenv_set_state(dynenv_t* h, int32_t env, const void* blob, size_t nbytes) 
 }
 
 // the batched, device-side forms: ordered on `stream`, no host synchronisation, no allocation, no host copy
-static int states_args(const dynenv_t* h, const int32_t* idx, int32_t n, const void* blobs) {
-  if (!h || (!blobs && n != 0)) return fail(DYNENV_ERR_ARG, "null argument");
+// (what: "the" canonical blobs, 8-byte aligned; "the exact" blobs, 16-byte aligned)
+static int blobs_args(const dynenv_t* h, const int32_t* idx, int32_t n, const void* blobs, unsigned align, const char* what) {
+  if (!h || (!blobs && n > 0)) return fail(DYNENV_ERR_ARG, "null argument");
   if (n < 0) return fail(DYNENV_ERR_ARG, "negative blob count");
   if (!idx && n > h->cfg.num_envs) return fail(DYNENV_ERR_ARG, "more blobs than environments and no index list");
-  if ((uintptr_t)blobs % 8) return fail(DYNENV_ERR_ARG, "the blobs must be 8-byte aligned");
+  if ((uintptr_t)blobs % align) return fail(DYNENV_ERR_ARG, std::string(what) + " blobs must be " + std::to_string(align) + "-byte aligned");
   return DYNENV_OK;
 }
 int dynenv_get_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, void* blobs_dev, void* stream) {
-  if (int rc = states_args(h, env_idx_dev, n, blobs_dev)) return rc;
+  if (int rc = blobs_args(h, env_idx_dev, n, blobs_dev, 8, "the")) return rc;
   if (n == 0) return DYNENV_OK;
   ON_DEVICE(h);
   return h->get_states(env_idx_dev, 0, n, blobs_dev, (hipStream_t)stream);
 }
 int dynenv_set_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const void* blobs_dev, int32_t* status_dev, void* stream) {
-  if (int rc = states_args(h, env_idx_dev, n, blobs_dev)) return rc;
+  if (int rc = blobs_args(h, env_idx_dev, n, blobs_dev, 8, "the")) return rc;
   if (n == 0) return DYNENV_OK;
   ON_DEVICE(h);
   return h->set_states(env_idx_dev, 0, n, blobs_dev, status_dev, true, (hipStream_t)stream);
@@ -251,22 +252,15 @@ int dynenv_set_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const 
 // exact save / restore of chosen environments: every row of the handle's row table (dynenv_host.h), one launch each way of the two
 // kernels both handles share (env_rows_kernels.hip); the rules of dynenv_get_states / dynenv_set_states, 16-byte aligned blobs
 size_t dynenv_exact_size(const dynenv_t* h) { return h ? h->rows.blobBytes : 0; }
-static int exact_args(const dynenv_t* h, const int32_t* idx, int32_t n, const void* blobs) {
-  if (!h || (!blobs && n > 0)) return fail(DYNENV_ERR_ARG, "null argument");
-  if (n < 0) return fail(DYNENV_ERR_ARG, "negative blob count");
-  if (!idx && n > h->cfg.num_envs) return fail(DYNENV_ERR_ARG, "more blobs than environments and no index list");
-  if ((uintptr_t)blobs % 16) return fail(DYNENV_ERR_ARG, "the exact blobs must be 16-byte aligned");
-  return DYNENV_OK;
-}
 int dynenv_get_exact(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, void* blobs_dev, void* stream) {
-  if (int rc = exact_args(h, env_idx_dev, n, blobs_dev)) return rc;
+  if (int rc = blobs_args(h, env_idx_dev, n, blobs_dev, 16, "the exact")) return rc;
   if (n == 0) return DYNENV_OK;
   ON_DEVICE(h);
   hipLaunchKernelGGL(env_rows_save_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, h->rows, (const int*)env_idx_dev, (unsigned char*)blobs_dev);
   return launched();
 }
 int dynenv_set_exact(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const void* blobs_dev, int32_t* status_dev, void* stream) {
-  if (int rc = exact_args(h, env_idx_dev, n, blobs_dev)) return rc;
+  if (int rc = blobs_args(h, env_idx_dev, n, blobs_dev, 16, "the exact")) return rc;
   if (n == 0) return DYNENV_OK;
   ON_DEVICE(h);
   hipLaunchKernelGGL(env_rows_load_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, h->rows, (const int*)env_idx_dev, (const unsigned char*)blobs_dev,
@@ -501,8 +495,8 @@ int dynenv_checkpoint_load(dynenv_t* h, const void* buf_host, size_t nbytes) {
   // (1) of the per-environment error word, which is part of the checkpointed array; ABI 3 gave the second its own bit 3.  A set bit 1
   // of an ABI 2 blob of a Partial handle may mean either: it is loaded as both (nothing that was reported goes unreported).
   for (size_t i = 0; i < h->allocs.size(); ++i) {
-    if (hd.abi_version == 2 && b.obs_type == DYNENV_OBS_PARTIAL && h->allocs[i] == (const void*)h->err_array) {
-      const size_t errStride = (size_t)h->err_stride, errWord = (size_t)h->err_index;
+    if (hd.abi_version == 2 && b.obs_type == DYNENV_OBS_PARTIAL && h->allocs[i] == (const void*)h->rows.err) {
+      const size_t errStride = (size_t)h->rows.errStride, errWord = (size_t)h->rows.errIndex;
       std::vector<int> w(h->alloc_bytes[i] / sizeof(int));
       memcpy(w.data(), in, w.size() * sizeof(int));
       for (size_t e = 0; (e + 1) * errStride <= w.size(); ++e) if (w[e * errStride + errWord] & 2) w[e * errStride + errWord] |= 8;

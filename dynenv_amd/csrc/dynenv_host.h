@@ -72,14 +72,13 @@ struct HOST_LOCAL dynenv {
   std::vector<void*> allocs;
   std::vector<size_t> alloc_bytes;  // checkpoint = these arrays, in allocation order
   std::vector<void*> scratch;       // scheduling scratch (SIMD-isolation lists), `stage`: NOT simulation state, never checkpointed
-  EnvRowTable rows = {};            // the per-environment arrays among `allocs` (alloc_rows), completed by rows_finish()
+  // the per-environment arrays among `allocs` (alloc_rows), completed by rows_finish(), and - set by init() - where the kernels keep the
+  // per-environment error word: rows.err[env * rows.errStride + rows.errIndex] (rows.err is one of `allocs`)
+  EnvRowTable rows = {};
   // where dynenv_get_state / dynenv_set_state keep their one blob on the device: state_bytes, then the status word (dynenv_create;
   // a handle is used by one thread at a time: dynenv.h)
   unsigned long long* stage = nullptr;
   hipEvent_t ev_begin = nullptr, ev_main = nullptr, ev_end = nullptr;  // dynenv_set_step_events (caller-owned)
-  // where the kernels keep the per-environment error word: err_array[env * err_stride + err_index] (err_array is one of `allocs`)
-  const int* err_array = nullptr;
-  int err_stride = 0, err_index = 0;
   // set by the first step or masked reset issued on a capturing stream, for the rest of the handle's life: the seed is a by-value
   // kernel argument, so a replay draws from the seed of the capture whatever the handle holds by then - from here on dynenv_seed and
   // dynenv_checkpoint_load refuse any other seed (dynenv_capi.hip)
@@ -174,7 +173,7 @@ struct HOST_LOCAL dynenv {
         prev = i;
       }
     }
-    rows.E = cfg.num_envs; rows.err = const_cast<int*>(err_array); rows.errStride = err_stride; rows.errIndex = err_index;
+    rows.E = cfg.num_envs;
     rows.tag = tag ? tag : 1; rows.blobBytes = (uint32_t)off;
     return 0;
   }

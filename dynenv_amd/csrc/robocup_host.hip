@@ -54,7 +54,7 @@ struct HOST_LOCAL RcHandle final : dynenv {
     rc |= alloc(&pairTab, 64 * 2);  // (constant, not per-environment: checkpointed, but no row of the table)
     if (rc) return DYNENV_ERR_HIP;
     R.pairTab = pairTab;
-    err_array = R.envi; err_stride = RE_COUNT; err_index = RE_ERR;
+    rows.err = R.envi; rows.errStride = RE_COUNT; rows.errIndex = RE_ERR;
     RcConst c;
     memset(&c, 0, sizeof(c));
     c.footInertia = moment_for_segment_host(4000.0, v2(-10.0, 10.0), v2(10.0, 10.0), 7.5);  // Robot.py:34

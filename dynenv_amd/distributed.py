@@ -125,7 +125,7 @@ class PackedSlab(object):
         import ctypes as C
         capi, lib = self._capi()
         st = C.c_void_p(self.torch.cuda.current_stream(self.buf.device).cuda_stream)
-        src, dst = C.c_void_p(self.obs.data_ptr()), C.c_void_p(self._packed.data_ptr())
+        src, dst = capi.ptr(self.obs), capi.ptr(self._packed)
         if self.peers:
             capi.check(lib.dynenv_obs_pack_peers(src, self.E * self.T, self.A, self.D, dst, st), "dynenv_obs_pack_peers")
         else:
@@ -148,7 +148,7 @@ class PackedSlab(object):
         import ctypes as C
         capi, lib = self._capi()
         st = C.c_void_p(t.cuda.current_stream(self.buf.device).cuda_stream)
-        src, dst = C.c_void_p(g.data_ptr()), C.c_void_p(dense_out.data_ptr())
+        src, dst = capi.ptr(g), capi.ptr(dense_out)
         # the compacted obs regions of the ranks sit `nbytes` apart in the gathered buffer: one launch expands them all
         if self.peers:
             capi.check(lib.dynenv_obs_unpack_peers_ranks(src, self.nbytes // 4, world_size, self.E * self.T, self.A, self.D, dst, st),

@@ -174,6 +174,46 @@ def reset_mask(envs, num_envs, device=None, what="reset_envs"):
     return m if m.is_contiguous() else m.contiguous()
 
 
+# The error bits of include/dynenv.h that the compat step raises on - never silently -: (bit, the handles it is looked at on, message % the first
+# environment that carries it).
+#   0: the reference's arbiter set has no cap; the contact tables have (DRV_NS / RC_NS slots, 128 candidate pairs a substep), and a pair
+#      beyond them was dropped: not the reference's state any more
+#   3: the reference's observation lists have no cap (DrivingEnvironment.py:816-890); the dense layout has, and rows beyond it were dropped
+#   4: two capsule cores exactly collinear / exactly touching: the sign of the contact normal is a convention there (Robot.py:38-52) -
+#      possibly not pymunk's trajectory from here on
+#   6: a blob that did not fit the handle was refused by set_states / set_exact: that environment still holds its OLD state
+_STEP_ERRORS = (
+    (1, "any",
+     "contact cache or candidate list overflow: a colliding pair was dropped (error bit 0): the state is not the "
+     "reference's any more; reset() or set_state() clears it; first in environment %d"),
+    (8, "partial",
+     "Partial observation: a list had more rows than the dense layout's capacity; rows were dropped (error bit 3), "
+     "first in environment %d"),
+    (32, "robocup",
+     "RoboCup: a velocity or joint impulse left the finite range (error bit 5): the state is not the reference's any more; "
+     "first in environment %d"),
+    (16, "robocup",
+     "RoboCup: the cores of two feet are exactly collinear / touching: the contact normal's sign is a convention "
+     "(error bit 4); reset() or set_state() clears it; first in environment %d (set_states() repairs that one alone)"),
+    (_capi.ERR_BAD_BLOB, "any",
+     "set_states / set_exact: a blob did not fit this handle and was not written (error bit 6): environment %d still holds its "
+     "earlier state; a valid set_states() / set_exact() of it or reset() clears the bit"),
+)
+
+
+@dataclass(frozen=True)
+class _BlobKind:
+    """What tells the canonical state blobs (get_states / set_states) from the exact ones (get_exact / set_exact)"""
+    name: str      # dynenv_get_<name> / dynenv_set_<name>, and the name in the messages
+    size: str      # the property that holds a blob's bytes
+    align: int     # the address a blob buffer is held to HERE: a misaligned device tensor is cloned, a misaligned `out` refused
+    structs: bool  # set_*: structured arrays and ctypes structs are accepted next to uint8 arrays
+
+
+_STATES = _BlobKind("states", "state_size", 1, True)   # (the C side asks for 8 bytes and says so itself)
+_EXACT = _BlobKind("exact", "exact_size", 16, False)
+
+
 class BatchedDynEnv(object):
     """All `num_envs` environments of one GPU shard behind the reference's VecEnv surface.
 
@@ -279,7 +319,7 @@ class BatchedDynEnv(object):
         return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
 
     def reset_flat(self):
-        _capi.check(self._lib.dynenv_reset(self._h, C.c_void_p(self.obs.data_ptr()), self._stream()), "dynenv_reset")
+        _capi.check(self._lib.dynenv_reset(self._h, _capi.ptr(self.obs), self._stream()), "dynenv_reset")
         self._episode_step = 0
         self._needs_reset = False
         self._counts_np = None  # the scene (obstacle / pedestrian counts) changed
@@ -293,7 +333,7 @@ class BatchedDynEnv(object):
         time 0, a fresh scene, contact cache, shortcut state and error word cleared.  With episodes="lockstep" the host's position in
         the episode stays where it is: `dones` of an environment reset on its own then comes from its own time on the device."""
         mask = reset_mask(envs, self.num_envs, self.device)
-        _capi.check(self._lib.dynenv_reset_masked(self._h, C.c_void_p(mask.data_ptr()), C.c_void_p(self.obs.data_ptr()), self._stream()),
+        _capi.check(self._lib.dynenv_reset_masked(self._h, _capi.ptr(mask), _capi.ptr(self.obs), self._stream()),
                     "dynenv_reset_masked")
         self._counts_np = None  # the scenes (obstacle / pedestrian counts) changed
         return self.obs
@@ -365,6 +405,7 @@ class BatchedDynEnv(object):
             if bool(bad_head):
                 raise Exception("Error: Head turn must be between +/-6")
         if mask is not None:
+            # (the casts spelled out in this method alone: the per-step path pays for no helper call)
             _capi.check(self._lib.dynenv_step_masked(self._h, C.c_void_p(mask.data_ptr()), C.c_void_p(a.data_ptr()),
                                                      C.c_void_p(head.data_ptr()) if head is not None else None,
                                                      C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.rewards.data_ptr()),
@@ -414,14 +455,14 @@ class BatchedDynEnv(object):
             p = torch.empty_like(r)
             o = torch.empty_like(r)
             g = torch.empty((E, 2), dtype=torch.int32, device=self.device)
-        _capi.check(self._lib.dynenv_episode_stats(self._h, C.c_void_p(r.data_ptr()), C.c_void_p(p.data_ptr()),
-                                                   C.c_void_p(o.data_ptr()), C.c_void_p(g.data_ptr()), self._stream()),
+        _capi.check(self._lib.dynenv_episode_stats(self._h, _capi.ptr(r), _capi.ptr(p),
+                                                   _capi.ptr(o), _capi.ptr(g), self._stream()),
                     "dynenv_episode_stats")
         return r, p, o, g
 
     def counts(self):
         c = self._torch.empty((self.num_envs, 2), dtype=self._torch.int32, device=self.device)
-        _capi.check(self._lib.dynenv_counts(self._h, C.c_void_p(c.data_ptr()), self._stream()), "dynenv_counts")
+        _capi.check(self._lib.dynenv_counts(self._h, _capi.ptr(c), self._stream()), "dynenv_counts")
         return c
 
     def error_flags(self):
@@ -438,7 +479,6 @@ class BatchedDynEnv(object):
 
     def debug_placement(self):
         """uint32 [4096]: XCC << 16 | SE, SH, CU, SIMD bits of HW_ID of every regular block of the last step (mode 1 handles), else empty"""
-        import numpy as np
         out = np.zeros((4096,), np.uint32)
         n = self._lib.dynenv_debug_placement(self._h, C.c_void_p(out.ctypes.data), out.size)
         if n < 0:
@@ -497,16 +537,67 @@ class BatchedDynEnv(object):
             raise _capi.DynEnvError("environment ids must fit int32")
         return torch.as_tensor(host.astype(np.int32)).to(self.device), int(host.size)
 
+    def _get_blobs(self, kind, env_ids, out):
+        """get_states / get_exact: one launch that writes the `kind` blobs of `env_ids` into `out` (None: a new tensor)"""
+        torch = self._torch
+        ids, n = self._env_ids(env_ids)
+        size = getattr(self, kind.size)
+        if out is None:
+            out = torch.empty((n, size), dtype=torch.uint8, device=self.device)
+        elif (out.dtype != torch.uint8 or out.device != self.device or tuple(out.shape) != (n, size) or not out.is_contiguous()
+              or out.data_ptr() % kind.align):
+            raise _capi.DynEnvError("get_%s: out must be a contiguous, %d-byte aligned uint8 [%d, %d] tensor on %s"
+                                    % (kind.name, kind.align, n, size, self.device))
+        fn = "dynenv_get_" + kind.name
+        _capi.check(getattr(self._lib, fn)(self._h, _capi.ptr(ids if n else None), n, _capi.ptr(out if n else None), self._stream()), fn)
+        return out
+
+    def _set_blobs(self, kind, env_ids, blobs, episode_step):
+        """set_states / set_exact: one launch that writes blobs[k] into environment env_ids[k]; -> the int32 [n] status tensor"""
+        torch = self._torch
+        what = "set_" + kind.name
+        if self._needs_reset and episode_step is None and not self.per_env:
+            raise _capi.DynEnvError("%s before the first reset(): pass episode_step (the batch's position in its lock-step episode)" % what)
+        ids, n = self._env_ids(env_ids, unique=True)
+        size = getattr(self, kind.size)
+        if isinstance(blobs, torch.Tensor):
+            b = blobs
+            if b.dtype != torch.uint8:
+                raise _capi.DynEnvError("%s: blobs must be uint8 [n, %d]" % (what, size))
+            if b.device != self.device or not b.is_contiguous():
+                b = b.to(self.device).contiguous()
+            if b.data_ptr() % kind.align:  # (a view into a larger tensor: a copy starts at an allocation)
+                b = b.clone()
+        elif kind.structs and not (isinstance(blobs, np.ndarray) and blobs.dtype == np.uint8):
+            b = torch.as_tensor(np.ascontiguousarray(_capi.states_as_blobs(blobs))).to(self.device)
+        else:
+            b = torch.as_tensor(np.ascontiguousarray(blobs, dtype=np.uint8)).to(self.device)
+        if b.dim() != 2 or b.shape[1] != size:
+            raise _capi.DynEnvError("%s: blobs must be uint8 [n, %d], got shape %s" % (what, size, tuple(b.shape)))
+        if ids is None:
+            n = int(b.shape[0])  # environments 0..n-1
+            if n > self.num_envs:
+                raise _capi.DynEnvError("%s: %d blobs for %d environments" % (what, n, self.num_envs))
+        elif int(b.shape[0]) != n:
+            raise _capi.DynEnvError("%s: %d environment ids but %d blobs" % (what, n, int(b.shape[0])))
+        status = torch.empty((n,), dtype=torch.int32, device=self.device)
+        fn = "dynenv_" + what
+        _capi.check(getattr(self._lib, fn)(self._h, _capi.ptr(ids if n else None), n, _capi.ptr(b if n else None),
+                                           _capi.ptr(status if n else None), self._stream()), fn)
+        self._counts_np = None  # the scenes (obstacle / pedestrian counts) may have changed
+        if episode_step is not None:
+            self._episode_step = int(episode_step)
+            self._needs_reset = False
+        elif self.per_env:
+            self._needs_reset = False
+        return status
+
     def get_states(self, env_ids=None):
         """The canonical state blobs of `env_ids` (a list, a numpy array or a device tensor; None = all environments, in order) as a
         torch.uint8 [n, state_size] tensor on the device: ONE launch on torch's current stream, nothing is waited for and nothing
         touches the host.  Row k holds exactly the bytes get_state(env_ids[k]) returns; `_capi.blobs_as_states(t.cpu().numpy(),
         env_type)` views them as a numpy structured array.  An id outside [0, num_envs) leaves its row as allocated (unspecified)."""
-        ids, n = self._env_ids(env_ids)
-        out = self._torch.empty((n, self.state_size), dtype=self._torch.uint8, device=self.device)
-        _capi.check(self._lib.dynenv_get_states(self._h, C.c_void_p(ids.data_ptr() if ids is not None and n else None), n,
-                                                C.c_void_p(out.data_ptr() if n else None), self._stream()), "dynenv_get_states")
-        return out
+        return self._get_blobs(_STATES, env_ids, None)
 
     def set_states(self, env_ids, blobs, episode_step=None):
         """Write blobs[k] into environment env_ids[k] (None = environments 0..n-1), all in ONE launch on torch's current stream.  `blobs`
@@ -521,39 +612,7 @@ class BatchedDynEnv(object):
         says where the batch now stands; blobs whose `elapsed` differs from it keep their own time on the device, and `dones` is not
         meaningful for them.  On a handle that was never reset there is no position to keep: pass `episode_step` then.
         Duplicate ids in one call are an error (raised when the ids live on the host, unspecified state otherwise)."""
-        torch = self._torch
-        if self._needs_reset and episode_step is None and not self.per_env:
-            raise _capi.DynEnvError("set_states before the first reset(): pass episode_step (the batch's position in its lock-step episode)")
-        ids, n = self._env_ids(env_ids, unique=True)
-        size = self.state_size
-        if isinstance(blobs, torch.Tensor):
-            b = blobs
-            if b.dtype != torch.uint8:
-                raise _capi.DynEnvError("set_states: blobs must be uint8 [n, %d]" % size)
-            if b.device != self.device or not b.is_contiguous():
-                b = b.to(self.device).contiguous()
-        else:
-            host = blobs if isinstance(blobs, np.ndarray) and blobs.dtype == np.uint8 else _capi.states_as_blobs(blobs)
-            b = torch.as_tensor(np.ascontiguousarray(host)).to(self.device)
-        if b.dim() != 2 or b.shape[1] != size:
-            raise _capi.DynEnvError("set_states: blobs must be uint8 [n, %d], got shape %s" % (size, tuple(b.shape)))
-        if ids is None:
-            n = int(b.shape[0])  # environments 0..n-1
-            if n > self.num_envs:
-                raise _capi.DynEnvError("set_states: %d blobs for %d environments" % (n, self.num_envs))
-        elif int(b.shape[0]) != n:
-            raise _capi.DynEnvError("set_states: %d environment ids but %d blobs" % (n, int(b.shape[0])))
-        status = torch.empty((n,), dtype=torch.int32, device=self.device)
-        _capi.check(self._lib.dynenv_set_states(self._h, C.c_void_p(ids.data_ptr() if ids is not None and n else None), n,
-                                                C.c_void_p(b.data_ptr() if n else None), C.c_void_p(status.data_ptr() if n else None),
-                                                self._stream()), "dynenv_set_states")
-        self._counts_np = None  # the scenes (obstacle / pedestrian counts) may have changed
-        if episode_step is not None:
-            self._episode_step = int(episode_step)
-            self._needs_reset = False
-        elif self.per_env:
-            self._needs_reset = False
-        return status
+        return self._set_blobs(_STATES, env_ids, blobs, episode_step)
 
     def fork(self, src_ids, dst_ids, exact=False):
         """Copy the state of environment src_ids[k] over environment dst_ids[k] - set_states(dst_ids, get_states(src_ids)): two launches,
@@ -587,17 +646,7 @@ class BatchedDynEnv(object):
         the same actions reproduces the run bit for bit, random draws included (they are keyed by the environment's id, episode
         counter and time, and the last two travel in the blob).  `out`: a contiguous uint8 [n, exact_size] device tensor to write into;
         the row of an id outside [0, num_envs) is left as it is."""
-        torch = self._torch
-        ids, n = self._env_ids(env_ids)
-        size = self.exact_size
-        if out is None:
-            out = torch.empty((n, size), dtype=torch.uint8, device=self.device)
-        elif (out.dtype != torch.uint8 or out.device != self.device or tuple(out.shape) != (n, size) or not out.is_contiguous()
-              or out.data_ptr() % 16):
-            raise _capi.DynEnvError("get_exact: out must be a contiguous, 16-byte aligned uint8 [%d, %d] tensor on %s" % (n, size, self.device))
-        _capi.check(self._lib.dynenv_get_exact(self._h, C.c_void_p(ids.data_ptr() if ids is not None and n else None), n,
-                                               C.c_void_p(out.data_ptr() if n else None), self._stream()), "dynenv_get_exact")
-        return out
+        return self._get_blobs(_EXACT, env_ids, out)
 
     def set_exact(self, env_ids, blobs, episode_step=None):
         """Write exact blob blobs[k] (get_exact) into environment env_ids[k] (None = environments 0..n-1), all in ONE launch on torch's
@@ -611,44 +660,13 @@ class BatchedDynEnv(object):
         Lock-step handles: the host's position in the episode stays where it is unless `episode_step` says where the batch now stands
         (set_states' rule; a roll-back of k steps of the whole batch passes the position it saved at); on a handle that was never reset
         pass `episode_step`.  Duplicate ids in one call are an error (raised when the ids live on the host)."""
-        torch = self._torch
-        if self._needs_reset and episode_step is None and not self.per_env:
-            raise _capi.DynEnvError("set_exact before the first reset(): pass episode_step (the batch's position in its lock-step episode)")
-        ids, n = self._env_ids(env_ids, unique=True)
-        size = self.exact_size
-        if isinstance(blobs, torch.Tensor):
-            b = blobs
-            if b.dtype != torch.uint8:
-                raise _capi.DynEnvError("set_exact: blobs must be uint8 [n, %d]" % size)
-            if b.device != self.device or not b.is_contiguous() or b.data_ptr() % 16:
-                b = b.to(self.device).contiguous().clone()
-        else:
-            b = torch.as_tensor(np.ascontiguousarray(blobs, dtype=np.uint8)).to(self.device)
-        if b.dim() != 2 or b.shape[1] != size:
-            raise _capi.DynEnvError("set_exact: blobs must be uint8 [n, %d], got shape %s" % (size, tuple(b.shape)))
-        if ids is None:
-            n = int(b.shape[0])  # environments 0..n-1
-            if n > self.num_envs:
-                raise _capi.DynEnvError("set_exact: %d blobs for %d environments" % (n, self.num_envs))
-        elif int(b.shape[0]) != n:
-            raise _capi.DynEnvError("set_exact: %d environment ids but %d blobs" % (n, int(b.shape[0])))
-        status = torch.empty((n,), dtype=torch.int32, device=self.device)
-        _capi.check(self._lib.dynenv_set_exact(self._h, C.c_void_p(ids.data_ptr() if ids is not None and n else None), n,
-                                               C.c_void_p(b.data_ptr() if n else None), C.c_void_p(status.data_ptr() if n else None),
-                                               self._stream()), "dynenv_set_exact")
-        self._counts_np = None  # the scenes (obstacle / pedestrian counts) may have changed
-        if episode_step is not None:
-            self._episode_step = int(episode_step)
-            self._needs_reset = False
-        elif self.per_env:
-            self._needs_reset = False
-        return status
+        return self._set_blobs(_EXACT, env_ids, blobs, episode_step)
 
     def error_flags_per_env(self):
         """Every environment's error word (the bits of include/dynenv.h's dynenv_error_flags) as an int32 [num_envs] device tensor: one
         launch, nothing waited for.  Its OR over the environments is error_flags()."""
         f = self._torch.empty((self.num_envs,), dtype=self._torch.int32, device=self.device)
-        _capi.check(self._lib.dynenv_error_flags_env(self._h, C.c_void_p(f.data_ptr()), self._stream()), "dynenv_error_flags_env")
+        _capi.check(self._lib.dynenv_error_flags_env(self._h, _capi.ptr(f), self._stream()), "dynenv_error_flags_env")
         return f
 
     def _first_env_with(self, bit):
@@ -660,7 +678,6 @@ class BatchedDynEnv(object):
     def checkpoint(self):
         """Every device array of the handle, bit for bit, as a numpy uint8 array (contact cache, shortcut state, episode
         counters and seed included): restore() + the same actions reproduces the run exactly, mid-episode too."""
-        import numpy as np
         n = int(self._lib.dynenv_checkpoint_size(self._h))
         buf = np.empty((n,), np.uint8)
         _capi.check(self._lib.dynenv_checkpoint_save(self._h, C.c_void_p(buf.ctypes.data), n), "dynenv_checkpoint_save")
@@ -671,7 +688,6 @@ class BatchedDynEnv(object):
         handle was created with or given by seed() since.  After a step_flat() / reset_envs() of this handle has been captured into a
         graph, a checkpoint taken under another seed raises DynEnvError and nothing is copied (a replay would keep drawing from the
         captured seed): restore it into a new handle."""
-        import numpy as np
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         _capi.check(self._lib.dynenv_checkpoint_load(self._h, C.c_void_p(buf.ctypes.data), buf.size), "dynenv_checkpoint_load")
         self._needs_reset = False
@@ -686,7 +702,7 @@ class BatchedDynEnv(object):
         """The noise-free Full observation of the current state, [E, A, full_obs_dim] float32 on the device, whatever the
         observation type (getFullState: what info['Full State'] / info['Recon States'] are made of)."""
         out = self._torch.empty((self.num_envs, self.n_agents, self.full_obs_dim), dtype=self._torch.float32, device=self.device)
-        _capi.check(self._lib.dynenv_full_obs(self._h, C.c_void_p(out.data_ptr()), self._stream()), "dynenv_full_obs")
+        _capi.check(self._lib.dynenv_full_obs(self._h, _capi.ptr(out), self._stream()), "dynenv_full_obs")
         return out
 
     def global_state(self):
@@ -696,7 +712,7 @@ class BatchedDynEnv(object):
         if self.env_type != DynEnvType.ROBO_CUP:
             raise NotImplementedError("Driving's getFullState(None) is made of columns of full_state_obs()")
         out = self._torch.empty((self.num_envs, 6 * self.n_agents + 3), dtype=self._torch.float32, device=self.device)
-        _capi.check(self._lib.dynenv_global_state(self._h, C.c_void_p(out.data_ptr()), self._stream()), "dynenv_global_state")
+        _capi.check(self._lib.dynenv_global_state(self._h, _capi.ptr(out), self._stream()), "dynenv_global_state")
         return out
 
     def refresh_obs(self):
@@ -777,29 +793,10 @@ class BatchedDynEnv(object):
         rewards = self.rewards.cpu().numpy().copy()
         robocup, partial = self.env_type == DynEnvType.ROBO_CUP, self.observationType == ObservationType.PARTIAL
         flags = self.error_flags()  # ONE read per step: it is a device synchronisation and a copy of the flags
-        if flags & 1:
-            # the reference's arbiter set has no cap; the contact tables have (DRV_NS / RC_NS slots, 128 candidate pairs a substep), and a
-            # pair beyond them was dropped: not the reference's state any more - never silently (include/dynenv.h, error bit 0)
-            raise _capi.DynEnvError("contact cache or candidate list overflow: a colliding pair was dropped (error bit 0): the state is not the "
-                                    "reference's any more; reset() or set_state() clears it; first in environment %d" % self._first_env_with(1))
-        if partial and flags & 8:
-            # the reference's observation lists have no cap (DrivingEnvironment.py:816-890); the dense layout has, and rows beyond it were
-            # dropped: not the reference's observation any more - never silently (include/dynenv.h, error bit 3)
-            raise _capi.DynEnvError("Partial observation: a list had more rows than the dense layout's capacity; rows were dropped (error bit 3), "
-                                    "first in environment %d" % self._first_env_with(8))
-        if robocup and flags & 32:
-            raise _capi.DynEnvError("RoboCup: a velocity or joint impulse left the finite range (error bit 5): the state is not the reference's any more; "
-                                    "first in environment %d" % self._first_env_with(32))
-        if robocup and flags & 16:
-            # two capsule cores exactly collinear / exactly touching: the sign of the contact normal is a convention there
-            # (Robot.py:38-52; include/dynenv.h, error bit 4) - possibly not pymunk's trajectory from here on, never silently
-            raise _capi.DynEnvError("RoboCup: the cores of two feet are exactly collinear / touching: the contact normal's sign is a convention "
-                                    "(error bit 4); reset() or set_state() clears it; first in environment %d (set_states() repairs that one alone)"
-                                    % self._first_env_with(16))
-        if flags & _capi.ERR_BAD_BLOB:
-            # a blob that did not fit the handle was refused by set_states: that environment still holds its OLD state - never silently
-            raise _capi.DynEnvError("set_states / set_exact: a blob did not fit this handle and was not written (error bit 6): environment %d still holds its "
-                                    "earlier state; a valid set_states() / set_exact() of it or reset() clears the bit" % self._first_env_with(_capi.ERR_BAD_BLOB))
+        applies = {"any": True, "robocup": robocup, "partial": partial}
+        for bit, where, message in _STEP_ERRORS:  # in this order: the first bit set is the one reported
+            if flags & bit and applies[where]:
+                raise _capi.DynEnvError(message % self._first_env_with(bit))
         done = bool(self.last_done)
         dones = np.full((self.num_envs,), done, dtype=bool)
         # The step's observations stay in HBM (a snapshot: self.obs is rewritten by the next step) until somebody looks at them:

@@ -153,6 +153,35 @@ def drv_chain10(st, seed, mixed=False):
 R3 = (CAR_HX[3] + CAR_HY[3]) * S2   # half the bounding box of a type-3 car (50 x 16) at 45 degrees: 23.33
 
 
+def resting_chain_scene(st, rng):
+    """2..4 crashed cars in a row (random types, lateral offsets, overlaps above and below the collision slop), optionally a dead
+    pedestrian wedged in and an obstacle at the end: resting contacts that share bodies - the two- and three-level solves a launch's
+    slowest environments run (drv_solve_bias_multi / drv_solve_general_split), in every arrangement of who is shape a and shape b."""
+    n = int(rng.integers(2, 5))
+    st.n_peds, st.n_obst = 0, 0
+    x, cy = 300.0 + float(rng.uniform(0, 50)), CY
+    order = list(rng.permutation(n))         # which car index stands where: canonical pair order != spatial order
+    prev_hx = None
+    for pos, k in enumerate(order):
+        t = int(rng.integers(0, 4))
+        hx = [10.0, 15.0, 20.0, 25.0][t]
+        if prev_hx is not None:
+            x += prev_hx + hx - float(rng.choice([0.03, 0.5, 1.5, 3.0]))
+        _place_crashed_car(st.cars[k], t, x, cy + float(rng.uniform(-3.0, 3.0)), float(rng.choice([0.0, 0.0, 0.0, 2.0])) if pos == 0 else 0.0)
+        prev_hx = hx
+    for k in range(n, st.n_cars):
+        _place_crashed_car(st.cars[k], 0, 1500.0, 480.0 + 45.0 * k, 0.0)
+    if rng.random() < 0.6:
+        st.n_obst = 1
+        st.obst_x[0], st.obst_y[0] = x + prev_hx + 10.0 - float(rng.choice([0.03, 0.8, 2.0])), cy + float(rng.uniform(-6.0, 6.0))
+    if rng.random() < 0.3:   # a dead pedestrian (a circle, dynamic, shape a of its pair) leaning on the first car
+        st.n_peds = 1
+        p = st.peds[0]
+        c = st.cars[order[0]]
+        p.px, p.py, p.vx, p.vy = c.px - [10.0, 15.0, 20.0, 25.0][c.type] - 5.0 + float(rng.choice([0.05, 0.7])), c.py, 0.0, 0.0
+        p.road, p.side, p.dead, p.moving, p.speed, p.crossing, p.begin_crossing = 1, 0, 1, 0, 4, 0, 0
+
+
 def _cars_around_stack(st, ks, sx, sy, d=8.0):
     """four type-3 cars at +-45 degrees around the point (sx, sy): the bounding box of each overlaps a 20 x 20 box centred there by d
     in x and y, at a corner its own rotated box leaves free (the nearest the box comes is 25 - d * sqrt 2 from that corner, d < 17).

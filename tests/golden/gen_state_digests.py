@@ -6,9 +6,9 @@ dynenv_get_states / dynenv_set_states, which dynenv_get_state / dynenv_set_state
 the library that still had a second one - a reset kernel with one thread per environment, a host path that moved an environment row by
 row - and pins the bytes of both: tests/test_gpu_state_digests.py recomputes every entry.
 
-  reset/<cfg>/<shape>   _situation(cfg, E) of tests/test_gpu_reset_masked.py, then reset_flat() twice: after each, the digest of
+  reset/<cfg>/<shape>   situation(cfg, E) of tests/per_env_common.py, then reset_flat() twice: after each, the digest of
                         _ckpt(env) (the checkpoint without Driving Partial's EI_DEFER_OBS) and of the observation's int32 view
-  state/<cfg>/<shape>   _started(cfg, E, SEED) of tests/test_gpu_state_batch.py: the digest of get_state(e) for e in range(E),
+  state/<cfg>/<shape>   started(cfg, E, SEED) of tests/per_env_common.py: the digest of get_state(e) for e in range(E),
                         concatenated, and of checkpoint() after the set_state(e, blob) loop over _donor_blobs
   every entry           checkpoint().size: the staging area of the synchronous calls is scratch, not part of a checkpoint
 
@@ -33,23 +33,23 @@ def _sha(data):
 
 
 def reset_entry(cfg, shape):
-    import test_gpu_reset_masked as rm
-    env = rm._situation(cfg, rm.SHAPES[shape][0])
+    import per_env_common as pc
+    env = pc.situation(cfg, pc.SHAPES[shape][0])
     entry = dict(checkpoint_size=int(env.checkpoint().size), ckpt=[], obs=[])
     for _ in range(2):
         obs = env.reset_flat()
-        entry["ckpt"].append(_sha(rm._ckpt(env).tobytes()))
-        entry["obs"].append(_sha(rm._i32(obs).tobytes()))
+        entry["ckpt"].append(_sha(pc.ckpt(env).tobytes()))
+        entry["obs"].append(_sha(pc.bits32(obs).tobytes()))
     env.close()
     return entry
 
 
 def state_entry(cfg, shape):
-    import test_gpu_state_batch as sb
-    E, listed = sb.SHAPES[shape]
-    ids = sb._ids(E, listed)
-    sts, _ = sb._donor_blobs(cfg, E, ids)
-    env = sb._started(cfg, E, sb.SEED)
+    import per_env_common as pc
+    E, listed = pc.STATE_SHAPES[shape]
+    ids = pc.listed_ids(E, listed)
+    sts, _ = pc.donor_blobs(cfg, E, ids)
+    env = pc.started(cfg, E, pc.SEED)
     entry = dict(checkpoint_size=int(env.checkpoint().size), get_state=_sha(b"".join(bytes(env.get_state(e)) for e in range(E))))
     for e, st in zip(ids, sts):
         env.set_state(e, st)
@@ -60,9 +60,8 @@ def state_entry(cfg, shape):
 
 def cases():
     """-> [(key, function, cfg, shape)] in the order of the two test modules' CASES"""
-    import test_gpu_reset_masked as rm
-    import test_gpu_state_batch as sb
-    return [("reset/%s/%s" % c, reset_entry) + c for c in rm.CASES] + [("state/%s/%s" % c, state_entry) + c for c in sb.CASES]
+    import per_env_common as pc
+    return [("reset/%s/%s" % c, reset_entry) + c for c in pc.CASES] + [("state/%s/%s" % c, state_entry) + c for c in pc.STATE_CASES]
 
 
 def main(out):

@@ -1,5 +1,5 @@
-"""What tests/test_rng_key_oracle.py (CPU) and tests/test_gpu_rng_key.py (-m gpu) share: the key tuples, the six configurations, an
-independent Philox4x32-10 with the key derivation of include/dynenv_math.h's dm_env_rng, blob helpers and the twin experiment.
+"""What tests/test_rng_key_oracle.py (CPU) and tests/test_gpu_rng_key.py (-m gpu) share on top of tests/per_env_common.py: the key tuples,
+the six configurations they run in, an independent Philox4x32-10 with the key derivation of include/dynenv_math.h's dm_env_rng, blob helpers and the twin experiment.
 No test in here.
 
 Every random draw of both environments is dm_env_rng(seed, genv, episode, purpose, entity, t)
@@ -15,6 +15,8 @@ import ctypes as C
 import numpy as np
 
 import oracle_lib as ol
+import per_env_common as pc
+from per_env_common import bits32, bits64, driving  # noqa: F401  (the tests of both files reach them as rk.*)
 
 E = 32
 M32 = 0xFFFFFFFF
@@ -31,24 +33,11 @@ KEYS = {
 }
 HIGH_WORD_KEYS = [k for k, v in KEYS.items() if v[0] >> 32]
 
-RC_RANDOM = ol.FLAG_RANDOM_INIT | ol.FLAG_CAN_FALL | ol.FLAG_USE_OBS_REWARDS
-# name: (oracle env_type, players, action highs, Partial + Realistic noise of magnitude 3?, flags, steps a step test runs)
-CFGS = {
-    "drv10": (1, 10, [3, 3], False, 0, 12),
-    "drv2": (1, 2, [3, 3], False, 0, 12),
-    "drvp": (1, 10, [3, 3], True, 0, 12),
-    "rc5": (0, 5, [5, 3, 3, 7], False, ol.ROBOCUP_DEFAULT_FLAGS, 40),
-    "rc5r": (0, 5, [5, 3, 3, 7], False, RC_RANDOM, 40),
-    "rcp": (0, 5, [5, 3, 3, 7], True, ol.ROBOCUP_DEFAULT_FLAGS, 12),
-}
-
-
-def driving(cfg):
-    return CFGS[cfg][0] == 1
+CFGS = pc.select("drv10", "drv2", "drvp", "rc5", "rc5r", "rcp")   # (tests/per_env_common.py's records under their short names)
 
 
 def steps_of(cfg):
-    return CFGS[cfg][5]
+    return CFGS[cfg].steps
 
 
 # ------------------------------------------------------------------------------------------------ Philox4x32-10, from its definition
@@ -80,17 +69,12 @@ def oracle_env_rng(seed, genv, episode, purpose, entity, t):
 
 # ------------------------------------------------------------------------------------------------ simulators and blobs
 def oracle(cfg, num_envs=E, seed=42, env_id_offset=0, threads=8):
-    oet, n, hi, partial, flags, _ = CFGS[cfg]
-    kw = dict(obs_type=1, noise_type=1, noise_magnitude=3.0) if partial else {}
-    return ol.OracleEnv(env_type=oet, num_envs=num_envs, n_players=n, seed=seed, env_id_offset=env_id_offset, flags=flags, threads=threads, **kw)
+    return pc.oracle(cfg, num_envs, seed, env_id_offset, threads=threads)
 
 
 def actions(cfg, num_envs, steps, seed):
     """[steps] of int32 [num_envs, A, K], uniformly random in the action space"""
-    oet, n, hi, _, _, _ = CFGS[cfg]
-    A = n if oet == 1 else 2 * n
-    rng = np.random.default_rng(seed)
-    return [np.stack([rng.integers(0, h, (num_envs, A)) for h in hi], -1).astype(np.int32) for _ in range(steps)]
+    return pc.actions(cfg, num_envs, pc.agents(cfg), steps, seed)
 
 
 def as_states(blobs, cfg):
@@ -130,14 +114,6 @@ def blob_diff(a, b, cfg):
         if rows.size:
             bad.append("%s (environments %s)" % (name, rows[:6].tolist()))
     return "state blobs differ in " + ", ".join(bad)
-
-
-def bits32(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.int32)
-
-
-def bits64(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.int64)
 
 
 # ------------------------------------------------------------------------------------------------ the twin experiment

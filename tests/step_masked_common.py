@@ -1,17 +1,11 @@
-"""What tests/test_gpu_step_masked.py shares with tests/test_gpu_reset_masked.py, taken from there by import - the configurations, the
-shapes, the pile environments, the per-env oracles and the checkpoint comparison that leaves Driving Partial's EI_DEFER_OBS out - plus
-the helpers only the masked step needs.  No test in here."""
+"""What only the masked step's tests need on top of tests/per_env_common.py (tests/test_gpu_step_masked.py; the exact transfer's tests
+freeze environments with them too): the sentinels every output tensor is pre-filled with, the output triples as bit patterns, and the
+random masks of the soak.  No test in here."""
 import numpy as np
 
-import test_gpu_reset_masked as rm
+from per_env_common import SENTINEL, bits32, bits64
 
-CFGS, PILE_CFGS, SHAPES, CASES, HISTORY, SEED = rm.CFGS, rm.PILE_CFGS, rm.SHAPES, rm.CASES, rm.HISTORY, rm.SEED
-driving, sub, make, oracle, pile_envs, actions, step, write_pile = (rm._driving, rm._sub, rm._make, rm._oracle, rm._pile_envs, rm._actions,
-                                                                    rm._step, rm._write_pile)
-situation, staggered, ckpt, ckpt_diff, i32, i64, same_f32, same_f64 = (rm._situation, rm._staggered, rm._ckpt, rm._ckpt_diff, rm._i32, rm._i64,
-                                                                       rm._same_f32, rm._same_f64)
-
-OBS_SENTINEL = rm.SENTINEL            # int32 pattern of an observation word nobody wrote
+OBS_SENTINEL = SENTINEL               # int32 pattern of an observation word nobody wrote
 REW_SENTINEL = 0x5EA71E555EA71E55     # int64 pattern of a reward nobody wrote
 DONE_SENTINEL = 0xA5                  # a dones byte nobody wrote
 
@@ -25,7 +19,7 @@ def fill_sentinels(env):
 
 def outputs(env):
     """(obs as int32, rewards as int64, dones) on the host: bit patterns"""
-    return i32(env.obs), i64(env.rewards), env.dones.cpu().numpy().copy()
+    return bits32(env.obs), bits64(env.rewards), env.dones.cpu().numpy().copy()
 
 
 def rows_are_sentinel(out, rows):

@@ -2,13 +2,12 @@
 entry points, the binding lists them and the library exports them, the ABI version is what it was, and a NULL handle is refused before
 any device is looked for."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG = -1
+from host_common import ERR_ARG, built_capi, comment_before, header_text, header_without_comments
+
 PROTOTYPES = (
     "size_t dynenv_exact_size(const dynenv_t* h);",
     "int dynenv_get_exact(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, void* blobs_dev, void* stream);",
@@ -19,20 +18,17 @@ NAMES = ("dynenv_exact_size", "dynenv_get_exact", "dynenv_set_exact")
 
 @pytest.fixture(scope="module")
 def capi():
-    from dynenv_amd import _capi, build
-    build.build()
-    return _capi
+    return built_capi()
 
 
 def test_header_declares_the_entry_points_and_the_abi_version_stays():
-    txt = open(os.path.join(ROOT, "include", "dynenv.h")).read()
-    h = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    txt, h = header_text(), header_without_comments()
     for p in PROTOTYPES:
         assert re.sub(r"\s+", " ", p) in h, p
     assert "#define DYNENV_ABI_VERSION 3" in h, "additions only: the ABI version stays"
     # like dynenv_get_state, the entries say that the reference has nothing of the kind
     assert re.search(r"dynenv_get/set_exact\s*<-\s*\(no reference equivalent", txt)
-    comment = re.sub(r"\s+", " ", txt[:txt.index("size_t dynenv_exact_size(")].rsplit("/*", 1)[1])
+    comment = comment_before("dynenv_exact_size")
     for phrase in ("no reference equivalent", "16-byte aligned", "no host synchronisation, no allocation, no host copy", "captured", "replay",
                    "error bit 6", "0 written, 1 blob rejected, 2 index outside [0, E)"):
         assert phrase in comment, phrase

@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, ROOT)
 import arranger as oa  # noqa: E402
 from compat_ref import compat_obs_of  # noqa: E402
-from test_oracle_golden_arranger import CASES, G, ragged_from_golden  # noqa: E402
+from arranger_golden import CASES, G, ragged_from_golden  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

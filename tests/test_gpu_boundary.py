@@ -411,7 +411,7 @@ def test_crossed_capsule_cores_on_both_sides(gpu):
     sticky until set_state / reset, and the compat step() raises; feet that merely overlap raise nothing.  The 4096 x 240 soaks assert
     the flag stays down in play."""
     import math
-    from test_kat_general import _feet_scene
+    from kat_scenes_common import _feet_scene
     dynenv_amd, torch, _ = gpu
     flags = ol.FLAG_USE_OBS_REWARDS
     env = dynenv_amd.BatchedDynEnv(dynenv_amd.DynEnvType.ROBO_CUP, 4, 5, seed=3, flags=flags)

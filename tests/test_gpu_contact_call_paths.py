@@ -10,7 +10,7 @@ and in the observations a step later.  One handle of 16 environments, 24 steps, 
                      into an obstacle a few steps later (single-level, general)
   drv_full_coupled   five groups of two cars and obstacles, everything at rest 0.5 deep: arbiters share bodies, only bias moves
   drv_chain10 mixed  ten moving cars and three pedestrians in one row: thirteen levels deep, general - the split path
-  pile-up            three cars driven into each other (tests/test_gpu_parity.py): the split path while they collide, other solves once
+  pile-up            three cars driven into each other (tests/parity_common.py): the split path while they collide, other solves once
                      they have come apart or to rest - both within one step
 
 The oracle solves every contact graph with the same sequential sweep, so it cannot tell the four apart; what it can tell -
@@ -23,7 +23,7 @@ import pytest
 
 import capacity_scenes as cs
 import oracle_lib as ol
-from test_gpu_parity import _assert_state_equal, _scenario
+from parity_common import _assert_state_equal, _scenario
 
 SEED = 21
 STEPS = 24

@@ -17,7 +17,7 @@ import pytest
 
 import capacity_scenes as cs
 import oracle_lib as ol
-from test_gpu_parity import _assert_rc_state_equal, _assert_state_equal, _rc_actions
+from parity_common import _assert_rc_state_equal, _assert_state_equal, _rc_actions
 
 pytestmark = pytest.mark.gpu
 

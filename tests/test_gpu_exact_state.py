@@ -4,27 +4,27 @@ fork(exact=True)).  -m gpu.
 An exact blob is every simulation-state row of an environment, so a restore followed by the same actions must be the run the blob was
 saved from, bit for bit: every comparison is of int views or of checkpoint() bytes.  Configurations, shapes, pile environments, per-env
 oracles and the checkpoint comparison (which leaves Driving Partial's timing word EI_DEFER_OBS out) are those of the masked reset and
-the masked step, by import (tests/step_masked_common.py)."""
+the masked step (tests/per_env_common.py, tests/step_masked_common.py)."""
 import numpy as np
 import pytest
 
+import per_env_common as pc
 import step_masked_common as sm
 
 pytestmark = pytest.mark.gpu
 
 STEPS = 6
-RC_PAIRTAB_BYTES = 64 * 2 * 8   # RoboCup's constant pair table: the last array of its checkpoint, no row of any environment
 
 
 def _situation(cfg, E, **kw):
-    return sm.situation(cfg, E, episodes="per_env", **kw)
+    return pc.situation(cfg, E, episodes="per_env", **kw)
 
 
 def _scribble(env, cfg):
     """every byte of every per-environment array of the handle inverted (through a checkpoint; nothing is stepped on it)"""
     junk = env.checkpoint().copy()
-    end = junk.size if sm.driving(cfg) else junk.size - RC_PAIRTAB_BYTES
-    junk[sm.rm.CKPT_HEADER:end] ^= 0xFF
+    end = junk.size if pc.driving(cfg) else junk.size - pc.RC_PAIRTAB_BYTES
+    junk[pc.CKPT_HEADER:end] ^= 0xFF
     env.restore(junk)
 
 
@@ -34,131 +34,131 @@ def _eq(a, b):
 
 
 # ------------------------------------------------------------------------------------------------ 1, 2
-@pytest.mark.parametrize("cfg,shape", sm.CASES)
+@pytest.mark.parametrize("cfg,shape", pc.CASES)
 def test_round_trip_then_replay(cfg, shape):
     """1. save every environment, take six steps, restore: the checkpoint is the one from before, byte for byte, and every status is 0.
     Between the steps and the restore EVERY byte of every per-environment array is inverted, so no array can come back right by not
     having changed (the piles alone do not move the obstacles, say).
     2. the same six actions again: every step's observations, rewards and dones are the first pass's, and so is the final checkpoint."""
-    E, _ = sm.SHAPES[shape]
+    E, _ = pc.SHAPES[shape]
     env = _situation(cfg, E)
     assert env.exact_size % 16 == 0 and env.exact_size > env.state_size
-    c0 = sm.ckpt(env)
+    c0 = pc.ckpt(env)
     blobs = env.get_exact()
     assert tuple(blobs.shape) == (E, env.exact_size)
-    assert sm.ckpt(env).tobytes() == c0.tobytes(), "a save changes nothing"
-    acts = sm.actions(cfg, E, env.n_agents, STEPS, 7, idle=sm.pile_envs(cfg, E))
+    assert pc.ckpt(env).tobytes() == c0.tobytes(), "a save changes nothing"
+    acts = pc.actions(cfg, E, env.n_agents, STEPS, 7, idle=pc.pile_envs(cfg, E))
     first = []
     for a in acts:
-        sm.step(env, a, auto_reset=False)
+        pc.step(env, a, auto_reset=False)
         first.append(sm.outputs(env))
-    c1 = sm.ckpt(env)
+    c1 = pc.ckpt(env)
     assert c1.tobytes() != c0.tobytes()
     _scribble(env, cfg)
     status = env.set_exact(None, blobs)
     assert status.cpu().tolist() == [0] * E
-    back = sm.ckpt(env)
+    back = pc.ckpt(env)
     diff = np.nonzero(back != c0)[0]
     assert diff.size == 0, "after the restore the checkpoint differs in %d bytes, first at offset %d of %d" % (diff.size, diff[0], c0.size)
     assert _eq(env.get_exact(), blobs), "saving again gives the same blobs"
     for s, a in enumerate(acts):
-        sm.step(env, a, auto_reset=False)
+        pc.step(env, a, auto_reset=False)
         assert sm.same_outputs(first[s], sm.outputs(env)) == "", "replayed step %d" % s
-    assert sm.ckpt(env).tobytes() == c1.tobytes(), "the replay ends where the first pass ended"
+    assert pc.ckpt(env).tobytes() == c1.tobytes(), "the replay ends where the first pass ended"
     assert env.error_flags() == 0
     env.close()
 
 
 # ------------------------------------------------------------------------------------------------ 2'
-@pytest.mark.parametrize("cfg,shape", [(c, s) for c, s in sm.CASES if c in ("driving_partial", "robocup_partial")])
+@pytest.mark.parametrize("cfg,shape", [(c, s) for c, s in pc.CASES if c in ("driving_partial", "robocup_partial")])
 def test_replay_with_the_scheduler_left_as_it_is(cfg, shape):
     """2'. the Partial configurations once more WITHOUT the inversion in between (which goes through restore() and so starts the
     scheduler's scratch - Driving Partial's deferred-observation lists and their parity, the forecasts - over): the restore comes
     straight behind the sixth step's deferred launch, and the replayed steps are still the first pass's."""
-    E, _ = sm.SHAPES[shape]
+    E, _ = pc.SHAPES[shape]
     env = _situation(cfg, E)
-    c0 = sm.ckpt(env)
+    c0 = pc.ckpt(env)
     blobs = env.get_exact()
-    acts = sm.actions(cfg, E, env.n_agents, STEPS, 7, idle=sm.pile_envs(cfg, E))
+    acts = pc.actions(cfg, E, env.n_agents, STEPS, 7, idle=pc.pile_envs(cfg, E))
     first = []
     for a in acts:
-        sm.step(env, a, auto_reset=False)
+        pc.step(env, a, auto_reset=False)
         first.append(sm.outputs(env))
-    c1 = sm.ckpt(env)
+    c1 = pc.ckpt(env)
     assert env.set_exact(None, blobs).cpu().tolist() == [0] * E
-    assert sm.ckpt(env).tobytes() == c0.tobytes()
+    assert pc.ckpt(env).tobytes() == c0.tobytes()
     for s, a in enumerate(acts):
-        sm.step(env, a, auto_reset=False)
+        pc.step(env, a, auto_reset=False)
         assert sm.same_outputs(first[s], sm.outputs(env)) == "", "replayed step %d" % s
-    assert sm.ckpt(env).tobytes() == c1.tobytes(), "the replay ends where the first pass ended"
+    assert pc.ckpt(env).tobytes() == c1.tobytes(), "the replay ends where the first pass ended"
     assert env.error_flags() == 0
     env.close()
 
 
 # ------------------------------------------------------------------------------------------------ 3
-@pytest.mark.parametrize("cfg,shape", [(c, s) for c, s in sm.CASES if s != "E1"])
+@pytest.mark.parametrize("cfg,shape", [(c, s) for c, s in pc.CASES if s != "E1"])
 def test_a_subset_against_the_masked_step(cfg, shape):
     """3. A saves M, steps everyone six times and restores M; its twin B steps the complement of M alone.  The handles are the same
     bytes: the listed environments are back where they were and no byte of an unlisted one was touched."""
-    E, M = sm.SHAPES[shape]
+    E, M = pc.SHAPES[shape]
     rest = [e for e in range(E) if e not in M]
     a, b = _situation(cfg, E), _situation(cfg, E)
-    assert sm.ckpt_diff(a, b) == "", "same configuration, same history"
+    assert pc.ckpt_diff(a, b) == "", "same configuration, same history"
     blobs = a.get_exact(M)
-    for act in sm.actions(cfg, E, a.n_agents, STEPS, 7, idle=sm.pile_envs(cfg, E)):
-        sm.step(a, act, auto_reset=False)
-        sm.step(b, act, auto_reset=False, active=rest)
-    assert sm.ckpt_diff(a, b) != "", "the listed environments moved"
+    for act in pc.actions(cfg, E, a.n_agents, STEPS, 7, idle=pc.pile_envs(cfg, E)):
+        pc.step(a, act, auto_reset=False)
+        pc.step(b, act, auto_reset=False, active=rest)
+    assert pc.ckpt_diff(a, b) != "", "the listed environments moved"
     import torch
     ids = M if E <= 5 else torch.tensor(M, dtype=torch.int32, device="cuda")
     assert a.set_exact(ids, blobs).cpu().tolist() == [0] * len(M)
-    assert sm.ckpt_diff(a, b) == ""
+    assert pc.ckpt_diff(a, b) == ""
     assert a.error_flags() == b.error_flags() == 0
     a.close()
     b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 4
-@pytest.mark.parametrize("cfg", sm.PILE_CFGS)
+@pytest.mark.parametrize("cfg", pc.PILE_CFGS)
 def test_the_detour_the_oracle_never_sees(cfg, oracle_built):
     """4. environments 0 and 1 hold a pile with live contacts (asserted on the per-env oracles) when they are saved.  Three steps with
     other actions, a restore, and the next eight steps are the oracle's next eight: which takes the contact cache with its warm-start
     impulses, the shortcut state and the call-to-call caches to be the saved ones - what get_states / set_states cannot do."""
     E, piles = 5, [0, 1]
-    env = sm.make(cfg, E, episodes="per_env")
+    env = pc.make(cfg, E, episodes="per_env")
     env.reset_flat()
-    ora = {e: sm.oracle(cfg, e) for e in piles}
+    ora = {e: pc.env_oracle(cfg, e) for e in piles}
     A = env.n_agents
-    for a in sm.actions(cfg, E, A, sm.HISTORY, 5):
-        sm.step(env, a, auto_reset=False)
+    for a in pc.actions(cfg, E, A, pc.HISTORY, 5):
+        pc.step(env, a, auto_reset=False)
     for e in piles:
         ora[e].reset()
-        st = sm.write_pile(cfg, ora[e].get_state(0), sm.HISTORY)
+        st = pc.write_pile(cfg, ora[e].get_state(0), pc.HISTORY)
         env.set_state(e, st)
         ora[e].set_state(0, st)
 
     def both(act, what):
-        og, rg, dg = sm.step(env, act, auto_reset=False)
+        og, rg, dg = pc.step(env, act, auto_reset=False)
         og, rg, dg = og.cpu().numpy(), rg.cpu().numpy(), dg.cpu().numpy()
         for e in piles:
             oc, rc, dc = ora[e].step(act[e:e + 1])
-            assert sm.same_f32(og[e], oc[0]), "%s: observations of environment %d" % (what, e)
-            assert sm.same_f64(rg[e], rc[0]) and dg[e] == dc[0], "%s: rewards / dones of environment %d" % (what, e)
-    for s, act in enumerate(sm.actions(cfg, E, A, 2, 6, idle=piles)):
+            assert pc.same_f32(og[e], oc[0]), "%s: observations of environment %d" % (what, e)
+            assert pc.same_f64(rg[e], rc[0]) and dg[e] == dc[0], "%s: rewards / dones of environment %d" % (what, e)
+    for s, act in enumerate(pc.actions(cfg, E, A, 2, 6, idle=piles)):
         both(act, "pile step %d" % s)
     for e in piles:
         assert ora[e].active_contacts(0) > 0, "environment %d holds no live contact when it is saved" % e
     blobs = env.get_exact(piles)
-    for act in sm.actions(cfg, E, A, 3, 21):   # the detour: the piles are driven too
-        sm.step(env, act, auto_reset=False)
+    for act in pc.actions(cfg, E, A, 3, 21):   # the detour: the piles are driven too
+        pc.step(env, act, auto_reset=False)
     assert not _eq(env.get_exact(piles), blobs)
     assert env.set_exact(piles, blobs).cpu().tolist() == [0, 0]
-    for s, act in enumerate(sm.actions(cfg, E, A, 8, 8, idle=piles)):
+    for s, act in enumerate(pc.actions(cfg, E, A, 8, 8, idle=piles)):
         both(act, "step %d after the restore" % s)
     for e in piles:
         assert ora[e].overflow() == 0
-        assert env.get_state(e).elapsed == ora[e].get_state(0).elapsed == (sm.HISTORY + 2 + 8) * sm.sub(cfg)[0]
-    assert env.get_state(2).elapsed == (sm.HISTORY + 2 + 3 + 8) * sm.sub(cfg)[0]
+        assert env.get_state(e).elapsed == ora[e].get_state(0).elapsed == (pc.HISTORY + 2 + 8) * pc.sub(cfg)[0]
+    assert env.get_state(2).elapsed == (pc.HISTORY + 2 + 3 + 8) * pc.sub(cfg)[0]
     assert env.error_flags_per_env().cpu().tolist() == [0] * E
     env.close()
 
@@ -178,7 +178,7 @@ def test_exact_fork(cfg):
     after = env.get_exact()
     for e in (0, 1, 2, 4):
         assert _eq(after[e], before[e]), "environment %d changed" % e
-    one = sm.make(cfg, 1, episodes="per_env")
+    one = pc.make(cfg, 1, episodes="per_env")
     assert one.exact_size == env.exact_size
     assert one.set_exact([0], after[2:3]).cpu().tolist() == [0]
     assert _eq(one.get_exact(), after[2:3])
@@ -211,8 +211,8 @@ def test_refusals(cfg):
     assert env.error_flags_per_env().cpu().tolist() == [0, 0, _capi.ERR_BAD_BLOB, 0, 0]
     env.reset_envs([2])
     assert env.error_flags_per_env().cpu().tolist() == [0] * E
-    if sm.driving(cfg):   # a RoboCup blob, cut to this handle's blob size: another configuration's tag
-        rc = sm.make("robocup5", 1, episodes="per_env")
+    if pc.driving(cfg):   # a RoboCup blob, cut to this handle's blob size: another configuration's tag
+        rc = pc.make("robocup5", 1, episodes="per_env")
         rc.reset_flat()
         foreign = rc.get_exact()
         cut = torch.zeros((1, env.exact_size), dtype=torch.uint8, device="cuda")
@@ -241,7 +241,7 @@ def test_a_captured_restore_reads_ids_and_blobs_at_replay():
     import torch
     cfg, E = "driving10", 5
     env, twin = _situation(cfg, E), _situation(cfg, E)
-    assert sm.ckpt_diff(env, twin) == ""
+    assert pc.ckpt_diff(env, twin) == ""
     saved = env.get_exact().clone()
     size = env.exact_size
     ids = torch.tensor([0, 2, 4], dtype=torch.int32, device="cuda")
@@ -251,10 +251,10 @@ def test_a_captured_restore_reads_ids_and_blobs_at_replay():
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         status = env.set_exact(ids, blobs)
-    acts = sm.actions(cfg, E, env.n_agents, 3, 13, idle=sm.pile_envs(cfg, E))
+    acts = pc.actions(cfg, E, env.n_agents, 3, 13, idle=pc.pile_envs(cfg, E))
     for a in acts[:2]:
-        sm.step(env, a, auto_reset=False)
-        sm.step(twin, a, auto_reset=False)
+        pc.step(env, a, auto_reset=False)
+        pc.step(twin, a, auto_reset=False)
     mid = env.get_exact().clone()
     ids.copy_(torch.tensor([0, -1, 4], dtype=torch.int32, device="cuda"))
     blobs.copy_(saved[[4, 2, 0]])   # new contents: 0 <- 4's blob, 4 <- 0's
@@ -265,7 +265,7 @@ def test_a_captured_restore_reads_ids_and_blobs_at_replay():
     for e in (1, 2, 3):
         assert _eq(now[e], mid[e]), "environment %d was touched" % e
     assert twin.set_exact([0, 4], saved[[4, 0]]).cpu().tolist() == [0, 0]
-    assert sm.ckpt_diff(env, twin) == ""
+    assert pc.ckpt_diff(env, twin) == ""
     # a step and the restore behind it, in one graph
     static_a = torch.zeros((E, env.n_agents, env.action_dim), dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
@@ -283,9 +283,9 @@ def test_a_captured_restore_reads_ids_and_blobs_at_replay():
     assert _eq(now[1], saved[1]) and _eq(now[3], saved[3])
     for e in (0, 2, 4):
         assert not _eq(now[e], before[e]), "environment %d was not stepped" % e
-    sm.step(twin, acts[2], auto_reset=False)
+    pc.step(twin, acts[2], auto_reset=False)
     assert twin.set_exact([1, 3], saved[[1, 3]]).cpu().tolist() == [0, 0]
-    assert sm.ckpt_diff(env, twin) == ""
+    assert pc.ckpt_diff(env, twin) == ""
     assert sm.same_outputs(sm.outputs(env), sm.outputs(twin)) == ""
     assert env.error_flags() == 0 and twin.error_flags() == 0
     env.close()

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-import test_oracle_golden_contacts as tc
+import golden_common as tc
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")

@@ -8,7 +8,7 @@ import pytest
 
 import kat_worlds as kw
 import oracle_lib as ol
-import test_kat_general as tk
+import kat_scenes_common as tk
 
 pytestmark = pytest.mark.gpu
 

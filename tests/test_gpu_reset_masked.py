@@ -8,152 +8,18 @@ Configurations: those of tests/test_gpu_state_batch.py plus robocup5_random (ran
 rc_reset_masked_kernel).  dynenv_reset is the same kernels with no mask; tests/test_gpu_state_digests.py pins what they write.  Shapes: E = 1, E = 5 with the listed set {3, 0, 4}, E = 70 with every third environment plus 63 and 64 (both
 sides of a 64 boundary).  "Pile" environments: capacity_scenes.drv_full_coupled / rc_chain written into environments 0 and 1 of the
 configurations that have the ten agents the scenes need, and stepped twice: they hold live contacts when they are reset."""
-import warnings
-
 import numpy as np
 import pytest
 
-import capacity_scenes as cs
 import oracle_lib as ol
+from per_env_common import (CASES, HISTORY, NAMES, PILE_CFGS, SENTINEL, SHAPES, actions as _actions, bits32 as _i32, bits64 as _i64,
+                            ckpt as _ckpt, ckpt_diff as _ckpt_diff, driving as _driving, env_oracle as _oracle, make as _make,
+                            pile_envs as _pile_envs, same_f32 as _same_f32, same_f64 as _same_f64, select, situation as _situation,
+                            staggered as _staggered, step as _step, sub as _sub, write_pile as _write_pile)
 
 pytestmark = pytest.mark.gpu
 
-RC_RANDOM = ol.ROBOCUP_DEFAULT_FLAGS | ol.FLAG_RANDOM_INIT | ol.FLAG_DETERMINISTIC_TURN
-# name: (oracle env_type, players, action highs, Partial + Realistic 3?, flags)
-CFGS = {
-    "driving10": (1, 10, [3, 3], False, 0),
-    "driving2": (1, 2, [3, 3], False, 0),
-    "robocup5": (0, 5, [5, 3, 3, 7], False, ol.ROBOCUP_DEFAULT_FLAGS),
-    "robocup1": (0, 1, [5, 3, 3, 7], False, ol.ROBOCUP_DEFAULT_FLAGS),
-    "driving_partial": (1, 10, [3, 3], True, 0),
-    "robocup_partial": (0, 5, [5, 3, 3, 7], True, ol.ROBOCUP_DEFAULT_FLAGS),
-    "robocup5_random": (0, 5, [5, 3, 3, 7], False, RC_RANDOM),
-}
-PILE_CFGS = [c for c in CFGS if CFGS[c][1] * (1 if CFGS[c][0] == 1 else 2) == 10]
-# name: (E, the listed set M)
-SHAPES = {"E1": (1, [0]), "E5": (5, [3, 0, 4]), "E70": (70, sorted(set(range(0, 70, 3)) | {63, 64}))}
-HISTORY = 40
-SEED = 31
-SENTINEL = 0x5EA71E55   # the int32 pattern obs is pre-filled with where no byte of it may change
-
-
-def _driving(cfg):
-    return CFGS[cfg][0] == 1
-
-
-def _sub(cfg):   # `elapsed` per step, and the episode's length in it
-    return (10, 6000) if _driving(cfg) else (50, 12000)
-
-
-def _make(cfg, E, seed=SEED, **kw):
-    from dynenv_amd import BatchedDynEnv, DynEnvType, NoiseType, ObservationType
-    oet, n, hi, partial, flags = CFGS[cfg]
-    if partial:
-        kw.update(observationType=ObservationType.PARTIAL, noiseType=NoiseType.REALISTIC, noiseMagnitude=3)
-    return BatchedDynEnv(DynEnvType.DRIVE if oet == 1 else DynEnvType.ROBO_CUP, E, n, seed=seed, flags=flags, **kw)
-
-
-def _oracle(cfg, e, seed=SEED):
-    """environment e of a batch, as an oracle of its own"""
-    oet, n, hi, partial, flags = CFGS[cfg]
-    kw = dict(obs_type=1, noise_type=1, noise_magnitude=3.0) if partial else {}
-    return ol.OracleEnv(env_type=oet, num_envs=1, n_players=n, seed=seed, env_id_offset=e, flags=flags, **kw)
-
-
-def _pile_envs(cfg, E):
-    return list(range(min(2, E))) if cfg in PILE_CFGS else []
-
-
-def _idle(cfg, a, envs):
-    """the environments that hold a pile take no action"""
-    for e in envs:
-        if _driving(cfg):
-            a[e] = 1
-        else:
-            a[e] = 0
-            a[e, :, 3] = 3
-    return a
-
-
-def _actions(cfg, E, A, steps, seed, idle=()):
-    rng = np.random.default_rng(seed)
-    return [_idle(cfg, np.stack([rng.integers(0, h, (E, A)) for h in CFGS[cfg][2]], -1).astype(np.int32), idle) for _ in range(steps)]
-
-
-def _step(env, a, **kw):
-    import torch
-    return env.step_flat(torch.tensor(a, device="cuda"), **kw)
-
-
-def _write_pile(cfg, st, step):
-    (cs.drv_full_coupled if _driving(cfg) else cs.rc_chain)(st)
-    st.elapsed = step * _sub(cfg)[0]
-    return st
-
-
-def _situation(cfg, E, **kw):
-    """a handle HISTORY + 2 steps into its first episode whose pile environments hold live contacts (the same for the same arguments)"""
-    env = _make(cfg, E, **kw)
-    env.reset_flat()
-    piles = _pile_envs(cfg, E)
-    blank = {e: env.get_state(e) for e in piles}
-    for a in _actions(cfg, E, env.n_agents, HISTORY, 5):
-        _step(env, a, auto_reset=False)
-    for e in piles:
-        env.set_state(e, _write_pile(cfg, blank[e], HISTORY))
-    for a in _actions(cfg, E, env.n_agents, 2, 6, idle=piles):
-        _step(env, a, auto_reset=False)
-    return env
-
-
-def _i32(t):
-    return t.cpu().numpy().view(np.int32)
-
-
-def _i64(t):
-    return t.cpu().numpy().view(np.int64)
-
-
-def _same_f32(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.int32), np.ascontiguousarray(b).view(np.int32))
-
-
-def _same_f64(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.int64), np.ascontiguousarray(b).view(np.int64))
-
-
-# Driving's checkpointed arrays in allocation order (csrc/driving_tu.hip: init), as (fields, slots per environment, bytes per element);
-# envi is the sixth: EI_COUNT = 19 ints an environment, EI_DEFER_OBS the last of them (csrc/driving_dev.h)
-DRV_NB, DRV_EI_COUNT, DRV_EI_DEFER_OBS, CKPT_HEADER = 32, 19, 18, 80
-DRV_ARRAYS = (("body", 9, DRV_NB, 8), ("carx", 6, 16, 8), ("flags", 1, DRV_NB, 4), ("aux", 1, DRV_NB, 4), ("obst", 2, 20, 8),
-              ("envi", 1, DRV_EI_COUNT, 4), ("epr", 2, 16, 8), ("s_pair", 1, cs.DRV_NS, 4), ("s_meta", 1, cs.DRV_NS, 4),
-              ("s_hash", 2, cs.DRV_NS, 4), ("s_imp", 4, cs.DRV_NS, 8), ("lastcand", 1, 64, 4))
-
-
-def _ckpt(env):
-    """checkpoint() - every device array of the handle that is simulation state - as uint8.  For Driving PARTIAL handles one word of it
-    is not state and is left out: envi[EI_DEFER_OBS] says how many of the agents' Partial observations the STEP launch got done before
-    its forecast end and how many it left to the deferred launch.  It is scheduling scratch that lives in a checkpointed row, depends
-    on timing once an environment is on the contact path - the piles are - and is neither read nor written by either reset.  Every
-    other configuration is compared whole."""
-    from dynenv_amd import ObservationType
-    c = env.checkpoint().copy()
-    if int(env.env_type) == 1 and env.observationType == ObservationType.PARTIAL:
-        E = env.num_envs
-        size = {name: f * n * b * E for name, f, n, b in DRV_ARRAYS}
-        assert c.size == CKPT_HEADER + sum(size.values()), "the checkpoint's layout changed: find envi again"
-        off = CKPT_HEADER + sum(size[name] for name, _, _, _ in DRV_ARRAYS[:5])
-        c[off:off + size["envi"]].view(np.int32).reshape(E, DRV_EI_COUNT)[:, DRV_EI_DEFER_OBS] = 0
-    return c
-
-
-def _ckpt_diff(a, b):
-    ca, cb = _ckpt(a), _ckpt(b)
-    diff = np.nonzero(ca != cb)[0]
-    return "" if diff.size == 0 else "checkpoints differ in %d bytes, first at offset %d of %d" % (diff.size, diff[0], ca.size)
-
-
-CASES = [(c, s) for c in CFGS for s in SHAPES]
+CFGS = select(*NAMES)
 
 
 # ------------------------------------------------------------------------------------------------ 1
@@ -342,25 +208,6 @@ def test_staggered_soak_against_per_env_oracles(cfg, oracle_built):
 
 
 # ------------------------------------------------------------------------------------------------ 6
-def _staggered(cfg, E, **kw):
-    """a per_env handle whose environment e ends after 1 + e % 4 steps: blobs from step HISTORY with `elapsed` edited, written with ONE
-    set_states that needs no episode_step and warns about nothing.  -> (handle, the blobs as uint8 [E, state_size])"""
-    from dynenv_amd import _capi
-    env = _make(cfg, E, episodes="per_env", **kw)
-    env.reset_flat()
-    for a in _actions(cfg, E, env.n_agents, HISTORY, 5):
-        _step(env, a, auto_reset=False)
-    blobs = env.get_states().cpu().numpy()
-    view = _capi.blobs_as_states(blobs, env.env_type)
-    sub, end = _sub(cfg)
-    for e in range(E):
-        view["elapsed"][e] = end - (1 + e % 4) * sub
-    with warnings.catch_warnings():
-        warnings.simplefilter("error")
-        assert env.set_states(None, blobs).cpu().tolist() == [0] * E
-    return env, blobs
-
-
 @pytest.mark.parametrize("cfg,E", [("driving10", 8), ("robocup5", 6)])
 def test_natural_ends_per_env(cfg, E, oracle_built):
     """6. episodes="per_env": step_flat(auto_reset=True) returns the step's dones with the finished environments' rows of obs already

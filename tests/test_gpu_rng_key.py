@@ -18,9 +18,9 @@ import pytest
 
 import capacity_scenes as cs
 import oracle_lib as ol
+import per_env_common as pc
 import rng_key_common as rk
-import test_gpu_reset_masked as rm
-from test_gpu_parity import _resting_chain_scene
+from capacity_scenes import resting_chain_scene as _resting_chain_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -37,11 +37,7 @@ def gpu(oracle_built):
 
 
 def _make(cfg, num_envs=E, seed=42, off=0, **kw):
-    from dynenv_amd import BatchedDynEnv, DynEnvType, NoiseType, ObservationType
-    oet, n, hi, partial, flags, _ = rk.CFGS[cfg]
-    if partial:
-        kw.update(observationType=ObservationType.PARTIAL, noiseType=NoiseType.REALISTIC, noiseMagnitude=3)
-    return BatchedDynEnv(DynEnvType.DRIVE if oet == 1 else DynEnvType.ROBO_CUP, num_envs, n, seed=seed, env_id_offset=off, flags=flags, **kw)
+    return pc.make(cfg, num_envs, seed, off, **kw)
 
 
 def _t(a):
@@ -170,7 +166,7 @@ def test_reset_then_steps_at_every_key(key, cfg):
 
 
 # ------------------------------------------------------------------------------------------------ 3
-DRV_ENVI_OFFSET_ARRAYS = 5   # rm.DRV_ARRAYS: envi is the sixth checkpointed array
+DRV_ENVI_OFFSET_ARRAYS = 5   # pc.DRV_ARRAYS: envi is the sixth checkpointed array
 
 
 def _defer_obs(env):
@@ -178,10 +174,10 @@ def _defer_obs(env):
     launch left to drv_partial_obs_deferred_kernel (0: all of them, A: none)"""
     c = env.checkpoint()
     n = env.num_envs
-    size = {name: f * k * b * n for name, f, k, b in rm.DRV_ARRAYS}
-    assert c.size == rm.CKPT_HEADER + sum(size.values()), "the checkpoint's layout changed: find envi again"
-    off = rm.CKPT_HEADER + sum(size[name] for name, _, _, _ in rm.DRV_ARRAYS[:DRV_ENVI_OFFSET_ARRAYS])
-    return c[off:off + size["envi"]].view(np.int32).reshape(n, rm.DRV_EI_COUNT)[:, rm.DRV_EI_DEFER_OBS].copy()
+    size = {name: f * k * b * n for name, f, k, b in pc.DRV_ARRAYS}
+    assert c.size == pc.CKPT_HEADER + sum(size.values()), "the checkpoint's layout changed: find envi again"
+    off = pc.CKPT_HEADER + sum(size[name] for name, _, _, _ in pc.DRV_ARRAYS[:DRV_ENVI_OFFSET_ARRAYS])
+    return c[off:off + size["envi"]].view(np.int32).reshape(n, pc.DRV_EI_COUNT)[:, pc.DRV_EI_DEFER_OBS].copy()
 
 
 @pytest.mark.parametrize("key", ["K2", "K3"])
@@ -276,19 +272,19 @@ def test_shard_invariance_at_the_largest_global_ids(cfg):
 @pytest.mark.parametrize("cfg", ["drv10", "drvp", "rc5r", "rcp"])
 def test_reseed_then_reset_is_a_fresh_handle(cfg):
     """6a. created with s1, seed(s2), reset = created with s2, reset = the oracle of s2: observations, counts, blobs, and the two
-    handles' checkpoints byte for byte (rm._ckpt: whole, but for Driving Partial's scheduling word EI_DEFER_OBS)"""
+    handles' checkpoints byte for byte (pc.ckpt: whole, but for Driving Partial's scheduling word EI_DEFER_OBS)"""
     a, b, ora = _make(cfg, seed=S1, off=5), _make(cfg, seed=S2, off=5), rk.oracle(cfg, E, S2, 5)
     assert a.seed(S2) == [S2] * E
     oa, ob, oc = a.reset_flat().cpu().numpy(), b.reset_flat().cpu().numpy(), ora.reset()
     assert np.array_equal(rk.bits32(oa), rk.bits32(ob)) and np.array_equal(rk.bits32(oa), rk.bits32(oc))
     assert np.array_equal(a.counts().cpu().numpy(), ora.counts())
     assert rk.blob_diff(_blobs(a), rk.oracle_blobs(ora, cfg), cfg) == ""
-    assert rm._ckpt_diff(a, b) == ""
+    assert pc.ckpt_diff(a, b) == ""
     for s, act in enumerate(rk.actions(cfg, E, 3, 37)):
         got = _step(a, act)
         _same_step(got, _step(b, act), "re-seeded against fresh, step %d" % s)
         _same_step(got, ora.step(act), "re-seeded against the oracle, step %d" % s)
-    assert rm._ckpt_diff(a, b) == ""
+    assert pc.ckpt_diff(a, b) == ""
     for x in (a, b):
         assert x.error_flags() == 0
         x.close()
@@ -304,13 +300,13 @@ def test_reseed_mid_episode_changes_the_draws_and_no_state(cfg):
     for s, a in enumerate(acts[:4]):
         _same_step(_step(env, a), ora.step(a), "%s under s1, step %d" % (cfg, s))
     before = _blobs(env)
-    ck = rm._ckpt(env)
+    ck = pc.ckpt(env)
     assert env.seed(S2) == [S2] * E
     ora.seed(S2)
     assert np.array_equal(_blobs(env), before) and rk.blob_diff(rk.oracle_blobs(ora, cfg), before, cfg) == ""
-    after = rm._ckpt(env)
-    assert np.array_equal(after[rm.CKPT_HEADER:], ck[rm.CKPT_HEADER:]), "seed() changed a device array"
-    assert not np.array_equal(after[:rm.CKPT_HEADER], ck[:rm.CKPT_HEADER]), "a checkpoint taken after seed() carries the new seed"
+    after = pc.ckpt(env)
+    assert np.array_equal(after[pc.CKPT_HEADER:], ck[pc.CKPT_HEADER:]), "seed() changed a device array"
+    assert not np.array_equal(after[:pc.CKPT_HEADER], ck[:pc.CKPT_HEADER]), "a checkpoint taken after seed() carries the new seed"
     for s, a in enumerate(acts[4:]):
         _same_step(_step(env, a), ora.step(a), "%s under s2, step %d" % (cfg, 4 + s))
     assert rk.blob_diff(_blobs(env), rk.oracle_blobs(ora, cfg), cfg) == ""
@@ -327,7 +323,7 @@ def test_reseed_through_env_method_is_the_same_call():
     assert a.seed(S2) == [S2] * E and b.env_method("set_random_seed", S2) == [S2] * E
     oa, ob, oc = (x.reset_flat().cpu().numpy() for x in (a, b, c))
     assert np.array_equal(rk.bits32(oa), rk.bits32(ob)) and np.array_equal(rk.bits32(oa), rk.bits32(oc))
-    assert rm._ckpt_diff(a, b) == "" and rm._ckpt_diff(a, c) == ""
+    assert pc.ckpt_diff(a, b) == "" and pc.ckpt_diff(a, c) == ""
     for x in (a, b, c):
         x.close()
 
@@ -354,7 +350,7 @@ def test_restore_brings_back_the_seed_of_the_checkpoint(cfg):
     a.restore(ck)
     for s, act in enumerate(acts[6:]):
         _same_step(_step(a, act), _step(twin, act), "after the restore, step %d" % s)
-    assert rm._ckpt_diff(a, twin) == ""
+    assert pc.ckpt_diff(a, twin) == ""
     for x in (a, twin, detour):
         assert x.error_flags() == 0
         x.close()
@@ -429,9 +425,9 @@ def test_captured_step_with_auto_reset_keeps_its_seed_and_says_so():
     seed, like the eager twin's"""
     import torch
     cfg = "driving10"
-    eager, _ = rm._staggered(cfg, E, seed=S1)
-    graphed, _ = rm._staggered(cfg, E, seed=S1)
-    other_ckpt = _other_checkpoint(lambda s: rm._make(cfg, E, seed=s))
+    eager, _ = pc.staggered(cfg, E, seed=S1)
+    graphed, _ = pc.staggered(cfg, E, seed=S1)
+    other_ckpt = _other_checkpoint(lambda s: pc.make(cfg, E, seed=s))
     static_a = torch.zeros((E, eager.n_agents, eager.action_dim), dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
@@ -439,7 +435,7 @@ def test_captured_step_with_auto_reset_keeps_its_seed_and_says_so():
         graphed.step_flat(static_a, auto_reset=True)
     _refuses_another_seed(graphed, other_ckpt)
     n_done = 0
-    for r, a in enumerate(rm._actions(cfg, E, eager.n_agents, 6, 13)):
+    for r, a in enumerate(pc.actions(cfg, E, eager.n_agents, 6, 13)):
         static_a.copy_(_t(a))
         g.replay()
         eager.step_flat(static_a.clone(), auto_reset=True)
@@ -473,6 +469,6 @@ def test_captured_masked_reset_alone_freezes_the_seed_too():
         eager.reset_envs(listed)
         assert torch.equal(eager.obs.view(torch.int32), graphed.obs.view(torch.int32)), r
         assert torch.equal(eager.get_states(), graphed.get_states()), r
-    assert rm._ckpt_diff(eager, graphed) == ""
+    assert pc.ckpt_diff(eager, graphed) == ""
     eager.close()
     graphed.close()

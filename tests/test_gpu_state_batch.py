@@ -9,77 +9,21 @@ block of the per-environment kernels; the random resets give the environments di
 import numpy as np
 import pytest
 
+from per_env_common import (DONOR_SEED, HISTORY, NAMES, SEED, STATE_CASES as CASES, STATE_SHAPES as SHAPES, actions as _actions,
+                            donor_blobs as _donor_blobs, listed_ids as _ids, make as _make, oracle, select, started as _started, step)
+
 pytestmark = pytest.mark.gpu
 
-# name: (oracle env_type, players, action highs, Partial + Realistic?)
-CFGS = {
-    "driving10": (1, 10, [3, 3], False),
-    "driving2": (1, 2, [3, 3], False),
-    "robocup5": (0, 5, [5, 3, 3, 7], False),
-    "robocup1": (0, 1, [5, 3, 3, 7], False),
-    "driving_partial": (1, 10, [3, 3], True),
-    "robocup_partial": (0, 5, [5, 3, 3, 7], True),
-}
-# name: (E, listed environments; None = all of them, in order)
-SHAPES = {"E1": (1, [0]), "E5_subset": (5, [3, 0, 4]), "E70_all": (70, None)}
-HISTORY = 40   # steps every handle runs before anything is read or written: mid-episode, contacts cached, pedestrians under way
-SEED, DONOR_SEED = 31, 977
-
-
-def _make(cfg, E, seed):
-    from dynenv_amd import BatchedDynEnv, DynEnvType, NoiseType, ObservationType
-    import oracle_lib as ol
-    oet, n, hi, partial = CFGS[cfg]
-    kw = dict(observationType=ObservationType.PARTIAL, noiseType=NoiseType.REALISTIC, noiseMagnitude=3) if partial else {}
-    flags = ol.ROBOCUP_DEFAULT_FLAGS if oet == 0 else 0
-    return BatchedDynEnv(DynEnvType.DRIVE if oet == 1 else DynEnvType.ROBO_CUP, E, n, seed=seed, flags=flags, **kw)
+CFGS = select(*NAMES[:6])   # (robocup5_random is the masked reset's)
 
 
 def _make_oracle(cfg, E, seed):
-    import oracle_lib as ol
-    oet, n, hi, partial = CFGS[cfg]
-    kw = dict(obs_type=1, noise_type=1, noise_magnitude=3.0) if partial else {}
-    flags = ol.ROBOCUP_DEFAULT_FLAGS if oet == 0 else 0
-    return ol.OracleEnv(env_type=oet, num_envs=E, n_players=n, seed=seed, flags=flags, threads=8, **kw)
-
-
-def _draw(rng, cfg, E, A):
-    return np.stack([rng.integers(0, h, (E, A)) for h in CFGS[cfg][2]], -1).astype(np.int32)
-
-
-def _actions(cfg, E, A, steps, seed):
-    rng = np.random.default_rng(seed)
-    return [_draw(rng, cfg, E, A) for _ in range(steps)]
+    return oracle(cfg, E, seed, threads=8)
 
 
 def _run(env, acts):
-    import torch
     for a in acts:
-        env.step_flat(torch.tensor(a, device="cuda"), auto_reset=False)
-
-
-def _started(cfg, E, seed, act_seed=5):
-    """a handle HISTORY steps into its first episode (the same history for the same arguments)"""
-    env = _make(cfg, E, seed)
-    env.reset_flat()
-    _run(env, _actions(cfg, E, env.n_agents, HISTORY, act_seed))
-    return env
-
-
-def _donor_blobs(cfg, E, ids):
-    """mid-episode states of a third run, read one by one with get_state: (ctypes structs, uint8 [n, state_size]); blob k
-    comes from environment (3 k + 1) % E of the donor, so that a batched write that ignored its index list would not pass"""
-    donor = _started(cfg, E, DONOR_SEED, act_seed=9)
-    sts = [donor.get_state((3 * k + 1) % E) for k in range(len(ids))]
-    donor.close()
-    return sts, np.stack([np.frombuffer(bytes(s), np.uint8) for s in sts])
-
-
-def _ids(E, listed):
-    return list(range(E)) if listed is None else list(listed)
-
-
-CASES = [(c, s) for c in CFGS for s in SHAPES]
+        step(env, a, auto_reset=False)
 
 
 @pytest.mark.parametrize("cfg,shape", CASES)

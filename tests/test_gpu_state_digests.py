@@ -2,8 +2,8 @@
 
 The library has one implementation of each; the file was recorded with the library that still had two (a reset with one thread per
 environment, a host path that moved an environment row by row through hipMemcpy) and holds what THOSE produced.  Every entry is
-recomputed by the code that wrote it (tests/golden/gen_state_digests.py: reset_flat() twice on _situation, get_state(e) of every
-environment and the set_state loop on _started, at the shapes of tests/test_gpu_reset_masked.py and tests/test_gpu_state_batch.py) and
+recomputed by the code that wrote it (tests/golden/gen_state_digests.py: reset_flat() twice on per_env_common.situation, get_state(e) of every
+environment and the set_state loop on per_env_common.started, at the shapes of tests/test_gpu_reset_masked.py and tests/test_gpu_state_batch.py) and
 compared.  checkpoint().size is recorded too: the staging area of dynenv_get_state / dynenv_set_state is not part of a checkpoint."""
 import json
 import os

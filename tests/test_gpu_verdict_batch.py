@@ -50,7 +50,7 @@ import pytest
 import oracle_lib as ol
 from capacity_scenes import CAR_HX, CAR_HY, S2, _dead_ped, _park, _turn
 from kat_scenes_r4 import CY, _place_crashed_car
-from test_gpu_parity import _assert_state_equal
+from parity_common import _assert_state_equal
 
 SEED = 33
 STEPS = 12

@@ -9,19 +9,16 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_common import ROOT, built_capi, header_without_comments
 
 
 @pytest.fixture(scope="module")
 def capi():
-    from dynenv_amd import _capi, build
-    build.build()
-    return _capi
+    return built_capi()
 
 
 def _declared_functions():
-    txt = open(os.path.join(ROOT, "include", "dynenv.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = header_without_comments(collapse=False)
     names = re.findall(r"^\s*(?:const\s+)?(?:int|void|size_t|char\s*\*|const char\s*\*)\s*\*?\s*(dynenv_\w+)\s*\(", txt, flags=re.M)
     return sorted(set(names))
 
@@ -34,6 +31,28 @@ def test_library_exports_every_declared_symbol(capi):
         assert hasattr(lib, n), "libdynenv_hip.so does not export %s declared in include/dynenv.h" % n
     assert set(names) <= set(capi.EXPORTS) | {"dynenv_abi_version", "dynenv_last_error"}
     assert lib.dynenv_abi_version() == capi.DYNENV_ABI_VERSION == 3
+
+
+def test_binding_table_follows_the_header_prototype_by_prototype(capi):
+    """every function include/dynenv.h declares has a line in the binding's one signature table, with as many argument types as the
+    prototype has parameters and the return type the header names (load() sets exactly the table's types: a missing line would load
+    and truncate pointers)"""
+    protos = re.findall(r"(const char ?\*|size_t|int64_t|int|void) ?(dynenv_\w+) ?\(([^()]*)\) ?;", header_without_comments())
+    names = [name for _, name, _ in protos]
+    assert set(_declared_functions()) <= set(names) and len(set(names)) == len(names)
+    assert set(names) == set(capi.SIGNATURES), "the table binds what the header declares, no more"
+    restypes = {"int": C.c_int, "size_t": C.c_size_t, "void": None, "int64_t": C.c_int64}
+    for ret, name, params in protos:
+        assert name in capi.SIGNATURES, "no signature for %s" % name
+        restype, argtypes = capi.SIGNATURES[name]
+        n_params = 0 if params.strip() == "void" else params.count(",") + 1
+        assert len(argtypes) == n_params, "%s: %d argument types for %d parameters" % (name, len(argtypes), n_params)
+        assert restype is restypes.get(ret, C.c_char_p), "%s returns %s" % (name, ret)
+    lib = capi.load()
+    assert capi.EXPORTS == list(capi.SIGNATURES)
+    for name, (restype, argtypes) in capi.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and fn.argtypes == argtypes, name
 
 
 def test_struct_sizes_match_the_header(capi, tmp_path):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+from golden_common import _state_from_npz
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 RTOL = 1e-11
@@ -151,31 +152,6 @@ def test_move_pedestrian_fsm(unit):
         e = mout[i]
         np.testing.assert_allclose([o.vx, o.vy], e[:2], rtol=RTOL, atol=ATOL, err_msg="trial %d" % i)
         assert [o.side, o.moving, o.crossing, o.begin_crossing] == [int(x) for x in e[2:6]], i
-
-
-def _state_from_npz(z, tag, which, key):
-    cf, ci = z["%s_%s_cars_f" % (tag, which)], z["%s_%s_cars_i" % (tag, which)]
-    pf, pi = z["%s_%s_peds_f" % (tag, which)], z["%s_%s_peds_i" % (tag, which)]
-    ob, sc = z["%s_%s_obst" % (tag, which)], z["%s_%s_scalars" % (tag, which)]
-    st = ol.DrivingState()
-    st.elapsed, st.all_finished = int(sc[0]), int(sc[1])
-    st.n_cars, st.n_peds, st.n_obst, st.episode = len(cf), len(pf), len(ob), int(key[2])
-    for i in range(len(cf)):
-        for n, v in zip(ol.CAR_F, cf[i]):
-            setattr(st.cars[i], n, float(v))
-        for n, v in zip(ol.CAR_I, ci[i]):
-            setattr(st.cars[i], n, int(v))
-    for i in range(len(pf)):
-        for n, v in zip(ol.PED_F, pf[i]):
-            setattr(st.peds[i], n, float(v))
-        for n, v in zip(ol.PED_I, pi[i]):
-            setattr(st.peds[i], n, int(v))
-    for i in range(len(ob)):
-        st.obst_x[i], st.obst_y[i] = float(ob[i][0]), float(ob[i][1])
-    er, epr = z["%s_%s_episode_r" % (tag, which)], z["%s_%s_episode_pos_r" % (tag, which)]
-    for i in range(len(er)):
-        st.episode_r[i], st.episode_pos_r[i] = float(er[i]), float(epr[i])
-    return st
 
 
 @pytest.mark.parametrize("tag", ["a", "b", "c"])

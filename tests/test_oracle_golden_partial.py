@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from test_oracle_golden import _state_from_npz  # noqa: F401  (same blob helpers)
+from golden_common import _state_from_npz  # noqa: F401  (same blob helpers)
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 

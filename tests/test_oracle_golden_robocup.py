@@ -8,53 +8,14 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+from golden_common import _check, _to_state
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-RT, AT = 1e-11, 1e-10
 
 
 @pytest.fixture(scope="module")
 def z(oracle_built):
     return np.load(os.path.join(G, "robocup_unit.npz"))
-
-
-def _to_state(rf, ri, sc, fl, episode):
-    st = ol.RoboCupState()
-    n = int(sc[1])
-    st.elapsed, st.n_robots, st.ball_owned, st.n_last_kicked = int(sc[0]), n, int(sc[2]), int(sc[3])
-    for i in range(4):
-        st.last_kicked[i] = int(sc[4 + i])
-    st.goals[0], st.goals[1], st.closest[0], st.closest[1] = int(sc[8]), int(sc[9]), int(sc[10]), int(sc[11])
-    st.n_def[0], st.n_def[1] = int(sc[12]), int(sc[13])
-    for i in range(10):
-        st.defenders[0][i] = int(sc[14 + i])
-        st.defenders[1][i] = int(sc[24 + i])
-    st.episode = episode
-    st.ball_free_cntr, st.grace_period, st.penal_times[0], st.penal_times[1] = fl[0], fl[1], fl[2], fl[3]
-    st.bpx, st.bpy, st.bvx, st.bvy, st.bw, st.bprevx, st.bprevy = fl[4:11]
-    for i in range(n):
-        for k, v in zip(ol.ROBOT_F, rf[i]):
-            setattr(st.robots[i], k, float(v))
-        for k, v in zip(ol.ROBOT_I, ri[i]):
-            setattr(st.robots[i], k, int(v))
-    return st
-
-
-def _check(st, rf, ri, sc, fl, msg, skip_def_order=False):
-    n = int(sc[1])
-    got_f = np.array([[getattr(st.robots[i], k) for k in ol.ROBOT_F] for i in range(n)])
-    got_i = np.array([[getattr(st.robots[i], k) for k in ol.ROBOT_I] for i in range(n)])
-    np.testing.assert_allclose(got_f, rf[:n], rtol=RT, atol=AT, err_msg=msg + " robot floats")
-    np.testing.assert_array_equal(got_i, ri[:n], err_msg=msg + " robot ints")
-    assert [st.elapsed, st.ball_owned, st.n_last_kicked] == [int(sc[0]), int(sc[2]), int(sc[3])], msg
-    assert list(st.last_kicked)[:st.n_last_kicked] == [int(x) for x in sc[4:4 + int(sc[3])]], msg + " lastKicked"
-    assert [st.goals[0], st.goals[1], st.closest[0], st.closest[1]] == [int(x) for x in sc[8:12]], msg + " goals/closest"
-    assert [st.n_def[0], st.n_def[1]] == [int(sc[12]), int(sc[13])], msg + " defenders"
-    assert list(st.defenders[0])[:st.n_def[0]] == [int(x) for x in sc[14:14 + st.n_def[0]]], msg
-    assert list(st.defenders[1])[:st.n_def[1]] == [int(x) for x in sc[24:24 + st.n_def[1]]], msg
-    got_fl = [st.ball_free_cntr, st.grace_period, st.penal_times[0], st.penal_times[1], st.bpx, st.bpy, st.bvx, st.bvy,
-              st.bw, st.bprevx, st.bprevy]
-    np.testing.assert_allclose(got_fl, fl, rtol=RT, atol=AT, err_msg=msg + " env floats")
 
 
 def _run(z, tag, call, flags=0):

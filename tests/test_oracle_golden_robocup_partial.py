@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from test_oracle_golden_robocup import _to_state
+from golden_common import _to_state
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 

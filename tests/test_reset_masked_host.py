@@ -2,26 +2,20 @@
 the library exports it and the binding lists it; its arguments are checked before any device is looked for; and the helper that turns
 reset_envs' argument into the device mask (vec_env.reset_mask) does so on CPU tensors."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG = -1
+from host_common import ERR_ARG, built_capi, header_without_comments
 
 
 @pytest.fixture(scope="module")
 def capi():
-    from dynenv_amd import _capi, build
-    build.build()
-    return _capi
+    return built_capi()
 
 
 def test_header_declares_the_entry_point_and_the_library_exports_it(capi):
-    txt = open(os.path.join(ROOT, "include", "dynenv.h")).read()
-    h = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    h = header_without_comments()
     assert "int dynenv_reset_masked(dynenv_t* h, const uint8_t* mask_dev, float* obs_dev, void* stream);" in h
     assert "#define DYNENV_ABI_VERSION 3" in h, "an addition only: the ABI version stays"
     assert "dynenv_reset_masked" in capi.EXPORTS

@@ -2,30 +2,22 @@
 the three entry points and the binding lists them, and the numpy view of a state blob (`_capi.state_dtype`, `blobs_as_states`,
 `states_as_blobs`) is the C struct byte for byte - every field, pads included, in both directions."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_common import built_capi, header_without_comments
+
 NEW = ("dynenv_get_states", "dynenv_set_states", "dynenv_error_flags_env")
 
 
 @pytest.fixture(scope="module")
 def capi():
-    from dynenv_amd import _capi, build
-    build.build()
-    return _capi
-
-
-def _header():
-    txt = open(os.path.join(ROOT, "include", "dynenv.h")).read()
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    return built_capi()
 
 
 def test_header_declares_the_three_entry_points_and_the_binding_lists_them(capi):
-    h = _header()
+    h = header_without_comments()
     want = {
         "dynenv_get_states": "int dynenv_get_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, void* blobs_dev, void* stream);",
         "dynenv_set_states": "int dynenv_set_states(dynenv_t* h, const int32_t* env_idx_dev, int32_t n, const void* blobs_dev, "

@@ -4,28 +4,24 @@ names its caller in its errors and reset_envs' messages are what they were; and 
 is touched."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_ARG = -1
+from host_common import ERR_ARG, built_capi, comment_before, header_without_comments
+
 PROTOTYPE = """int dynenv_step_masked(dynenv_t* h, const uint8_t* mask_dev, const int32_t* actions_dev, const double* head_dev,
                        float* obs_dev, double* rewards_dev, uint8_t* dones_dev, void* stream);"""
 
 
 @pytest.fixture(scope="module")
 def capi():
-    from dynenv_amd import _capi, build
-    build.build()
-    return _capi
+    return built_capi()
 
 
 def test_header_declares_the_entry_point_and_the_library_exports_it(capi):
-    txt = open(os.path.join(ROOT, "include", "dynenv.h")).read()
-    h = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    h = header_without_comments()
     assert re.sub(r"\s+", " ", PROTOTYPE) in h
     assert "#define DYNENV_ABI_VERSION 3" in h, "an addition only: the ABI version stays"
     assert capi.DYNENV_ABI_VERSION == 3
@@ -35,7 +31,7 @@ def test_header_declares_the_entry_point_and_the_library_exports_it(capi):
     assert lib.dynenv_step_masked.argtypes == [C.c_void_p] * 8
     assert lib.dynenv_abi_version() == 3
     # its comment says what the issue asks of it
-    comment = re.sub(r"\s+", " ", txt[:txt.index("int dynenv_step_masked(")].rsplit("/*", 1)[1])
+    comment = comment_before("dynenv_step_masked")
     for phrase in ("LISTED", "UNLISTED", "not read", "no host synchronisation, no allocation, no host copy", "Capturable", "replay"):
         assert phrase in comment, phrase
 

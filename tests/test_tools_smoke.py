@@ -52,7 +52,7 @@ def test_pair_order_cost_tool_runs(oracle_built, capsys):
 def test_own_side_line_excusal_accepts_the_degenerate_row_and_nothing_else():
     """tools/reference_step_fuzz.py (Partial populations) excuses exactly one thing: a zero-length line at the robot's own position on one
     side only (a penalized robot on its side line).  A real extra line, or any other difference, stays a failure."""
-    import test_oracle_golden_contacts as tc
+    import golden_common as tc
     T, L = tc.RCP_TAIL, tc.RCP_OFF_LINE
     a = np.zeros(793, np.float32)
     a[L:L + 5] = [0.3, 0.6, -0.8, 1.0, 0.0]                    # one ordinary line on both sides

@@ -8,16 +8,11 @@ events around the C entry points on preallocated device buffers, a warm-up, and 
   a lookahead: get_exact of every environment + 5 steps + set_exact of every environment, against the same 5 steps alone (both from
   the same state with the same actions: the state is put back, untimed, in front of every timed call).
 Usage (GPU box): python tools/exact_state_time.py [--envs 4096] [--calls 20] [--repeats 3] [--out FILE]"""
-import argparse
-import ctypes as C
-import json
-import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from timing_common import CONFIGS, action_pool, base_parser, event_times, fmt, mid_episode, parse_positive, spread_ids, write_json
 
-CONFIGS = (("Driving Full, 10 cars", "DRIVE", 10, (3, 3)), ("RoboCup Full, 5 per team", "ROBO_CUP", 5, (5, 3, 3, 7)))
 CALLS = ("get_states", "get_exact", "set_states", "set_exact")
 SETS = ("all", "64", "7")
 VARIANTS = tuple("%s_%s" % (c, s) for s in SETS for c in CALLS)
@@ -26,47 +21,17 @@ LOOKAHEAD_STEPS = 5
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--calls", type=int, default=20, help="timed calls per variant and repeat")
-    ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--out", default=None, help="write the results as JSON to this file as well")
-    args = ap.parse_args(argv)
-    if args.envs < 1 or args.calls < 1 or args.repeats < 1:
-        ap.error("--envs, --calls and --repeats must be positive")
-    return args
+    return parse_positive(base_parser(__doc__), argv)
 
 
 def listed_sets(E):
     """name -> the environments listed: "all" = None (no index list: environments 0..E-1), "64" and "7" = that many distinct
     environments spread evenly over [0, E) (all of them where E is smaller)"""
-    spread = lambda k: sorted({(j * E) // min(k, E) for j in range(min(k, E))})
-    return {"all": None, "64": spread(64), "7": spread(7)}
+    return {"all": None, "64": spread_ids(E, 64), "7": spread_ids(E, 7)}
 
 
 def listed_count(E, listed):
     return E if listed is None else len(listed)
-
-
-def event_times(torch, f, calls, warmup=3, prepare=None):
-    """device microseconds of each of `calls` calls of f, every call between its own pair of events; `prepare` runs, untimed, in front
-    of every call"""
-    for _ in range(warmup):
-        if prepare:
-            prepare()
-        f()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        if prepare:
-            prepare()
-        e0.record()
-        f()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3)
-    return out
 
 
 def measure(name, type_name, players, hi, args, seed):
@@ -75,27 +40,23 @@ def measure(name, type_name, players, hi, args, seed):
     from dynenv_amd import BatchedDynEnv, DynEnvType, _capi
     E = args.envs
     env = BatchedDynEnv(getattr(DynEnvType, type_name), E, players, seed=seed, episodes="per_env")
-    A = env.n_agents
-    rng = np.random.default_rng(seed)
-    acts = [torch.tensor(np.stack([rng.integers(0, h, (E, A)) for h in hi], -1).astype(np.int32), device="cuda") for _ in range(16)]
-    env.reset_flat()
-    for s in range(30):  # mid-episode: pedestrians under way, contacts cached
-        env.step_flat(acts[s % len(acts)], auto_reset=False)
+    acts = action_pool(torch, np, hi, E, env.n_agents, seed)
+    mid_episode(env, acts)
     lib, h, stream = env._lib, env._h, env._stream()
-    obs, rew, don = (C.c_void_p(t.data_ptr()) for t in (env.obs, env.rewards, env.dones))
+    obs, rew, don = (_capi.ptr(t) for t in (env.obs, env.rewards, env.dones))
     sizes = {"states": env.state_size, "exact": env.exact_size}
     calls, keep = {}, []
     for sname, listed in listed_sets(E).items():
         n = listed_count(E, listed)
         ids = None if listed is None else torch.tensor(listed, dtype=torch.int32, device="cuda")
-        idp = C.c_void_p(ids.data_ptr()) if ids is not None else None
+        idp = _capi.ptr(ids)
         status = torch.zeros((n,), dtype=torch.int32, device="cuda")
         keep += [ids, status]
         for kind in ("states", "exact"):
             blobs = torch.zeros((n, sizes[kind]), dtype=torch.uint8, device="cuda")
             keep.append(blobs)
             get, put = getattr(lib, "dynenv_get_" + kind), getattr(lib, "dynenv_set_" + kind)
-            bp, sp = C.c_void_p(blobs.data_ptr()), C.c_void_p(status.data_ptr())
+            bp, sp = _capi.ptr(blobs), _capi.ptr(status)
             calls["get_%s_%s" % (kind, sname)] = (lambda get=get, idp=idp, n=n, bp=bp, kind=kind:
                                                   _capi.check(get(h, idp, n, bp, stream), "dynenv_get_" + kind))
             calls["set_%s_%s" % (kind, sname)] = (lambda put=put, idp=idp, n=n, bp=bp, sp=sp, kind=kind:
@@ -106,7 +67,7 @@ def measure(name, type_name, players, hi, args, seed):
     def steps():
         for _ in range(LOOKAHEAD_STEPS):
             nxt[0] += 1
-            _capi.check(lib.dynenv_step(h, C.c_void_p(acts[nxt[0] % len(acts)].data_ptr()), obs, rew, don, stream), "dynenv_step")
+            _capi.check(lib.dynenv_step(h, _capi.ptr(acts[nxt[0] % len(acts)]), obs, rew, don, stream), "dynenv_step")
 
     def lookahead():
         calls["get_exact_all"]()
@@ -127,7 +88,6 @@ def measure(name, type_name, players, hi, args, seed):
             times[k].append(statistics.median(event_times(torch, f, max(2, args.calls // LOOKAHEAD_STEPS), warmup=1, prepare=rewind)))
     assert env.error_flags() == 0
     env.close()
-    fmt = lambda v: "%8.1f us (%.1f .. %.1f over %d repeats)" % (statistics.median(v), min(v), max(v), len(v))
     print("== %s: %d environments, medians of %d calls; canonical blob %d bytes, exact blob %d bytes" % (name, E, args.calls, sizes["states"], sizes["exact"]))
     for sname, listed in listed_sets(E).items():
         for c in CALLS:
@@ -142,10 +102,7 @@ def measure(name, type_name, players, hi, args, seed):
 def main(argv=None):
     args = parse_args(argv)
     results = [measure(name, type_name, players, hi, args, 42) for name, type_name, players, hi in CONFIGS]
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-    return results
+    return write_json(results, args.out)
 
 
 if __name__ == "__main__":

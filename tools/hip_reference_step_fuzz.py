@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle_lib as ol  # noqa: E402  (state structs only: the oracle is not run)
-import test_oracle_golden_contacts as tc  # noqa: E402
+import golden_common as tc  # noqa: E402
 
 
 def main():

@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import kat_fuzz as kf  # noqa: E402
 import kat_worlds as kw  # noqa: E402
 import oracle_lib as ol  # noqa: E402
-import test_kat_general as tk  # noqa: E402
+import kat_scenes_common as tk  # noqa: E402
 
 
 def pct(x):

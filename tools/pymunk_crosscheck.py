@@ -172,7 +172,7 @@ def compare(tag, log, ora, rewards_ref, rewards_ora, substeps_per_step):
 # ------------------------------------------------------------------------------------------------ Driving
 def run_driving(gg, ol, n_players, seed, steps, bias, tag):
     import gen_golden_contacts as gc
-    from test_oracle_golden import _state_from_npz
+    from golden_states import _state_from_npz
     env, de, cut = gg.make_driving(n_players, seed)
     sid_of = gc.driving_sids(env)
     name_shapes(env.space, sid_of)
@@ -234,7 +234,7 @@ class Dice(object):
 def run_robocup(gg, ol, n, can_fall, steps, seed, forward, tag):
     import gen_golden_contacts as gc
     import gen_golden_robocup as gr
-    from test_oracle_golden_robocup import _to_state
+    from golden_states import _to_state
     env, rc_mod, cut = gr.make_env(n, seed, can_fall)
     sid_of = gc.robocup_sids(env)
     name_shapes(env.space, sid_of)

@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import gen_golden_contacts as gc  # noqa: E402
 import oracle_lib as ol  # noqa: E402
-import test_oracle_golden_contacts as tc  # noqa: E402
+import golden_common as tc  # noqa: E402
 
 
 def driving_env(n_players, seed, offset):

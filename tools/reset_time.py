@@ -11,57 +11,18 @@ every repeat (--repeats: the run-to-run spread):
       set_states from blobs of environments that really are at that phase - a donor runs one episode and keeps get_states() every
       10 steps - with `elapsed` edited to the environment's exact step.
 Usage (GPU box): python tools/reset_time.py [--envs 4096] [--calls 20] [--repeats 3] [--no-episode] [--out FILE]"""
-import argparse
-import ctypes as C
-import json
-import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from timing_common import CONFIGS, action_pool, base_parser, event_times, fmt, mid_episode, parse_positive, spread_ids, write_json
 
-CONFIGS = (("Driving Full, 10 cars", "DRIVE", 10, (3, 3)), ("RoboCup Full, 5 per team", "ROBO_CUP", 5, (5, 3, 3, 7)))
 SNAP_EVERY = 10
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--calls", type=int, default=20, help="timed calls per variant and repeat")
-    ap.add_argument("--repeats", type=int, default=3)
+    ap = base_parser(__doc__)
     ap.add_argument("--no-episode", action="store_true", help="skip (e), the two whole-episode runs per repeat")
-    ap.add_argument("--out", default=None, help="write the results as JSON to this file as well")
-    args = ap.parse_args(argv)
-    if args.envs < 1 or args.calls < 1 or args.repeats < 1:
-        ap.error("--envs, --calls and --repeats must be positive")
-    return args
-
-
-def spread_ids(E, n):
-    """n environment ids spread evenly over [0, E)"""
-    n = max(0, min(n, E))
-    return sorted(set((k * E) // n for k in range(n))) if n else []
-
-
-def event_times(torch, f, calls, warmup=3):
-    """device microseconds of each of `calls` calls of f, every call between its own pair of events"""
-    for _ in range(warmup):
-        f()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        f()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3)
-    return out
-
-
-def action_pool(torch, np, hi, E, A, seed, n=16):
-    rng = np.random.default_rng(seed)
-    return [torch.tensor(np.stack([rng.integers(0, h, (E, A)) for h in hi], -1).astype(np.int32), device="cuda") for _ in range(n)]
+    return parse_positive(ap, argv)
 
 
 def mean_step_us(torch, env, acts, steps, auto_reset):
@@ -103,10 +64,8 @@ def measure(name, type_name, players, hi, args, seed):
     env = make()
     A = env.n_agents
     acts = action_pool(torch, np, hi, E, A, seed)
-    env.reset_flat()
-    for s in range(30):  # mid-episode: pedestrians under way, contacts cached
-        env.step_flat(acts[s % len(acts)], auto_reset=False)
-    lib, h, stream, obs = env._lib, env._h, env._stream(), C.c_void_p(env.obs.data_ptr())
+    mid_episode(env, acts)
+    lib, h, stream, obs = env._lib, env._h, env._stream(), _capi.ptr(env.obs)
     n_small = max(1, round(E / 600))
     masks = {}
     for key, ids in (("all", list(range(E))), ("none", []), ("few", spread_ids(E, n_small)), ("64", spread_ids(E, 64))):
@@ -116,7 +75,7 @@ def measure(name, type_name, players, hi, args, seed):
         masks[key] = m
     variants = [("reset", lambda: _capi.check(lib.dynenv_reset(h, obs, stream), "dynenv_reset"))]
     for key in ("all", "none", "few", "64"):
-        ptr = C.c_void_p(masks[key].data_ptr())
+        ptr = _capi.ptr(masks[key])
         variants.append(("masked_" + key, lambda ptr=ptr: _capi.check(lib.dynenv_reset_masked(h, ptr, obs, stream), "dynenv_reset_masked")))
     steps = env.steps_per_episode
     sub = env._substeps()
@@ -143,7 +102,6 @@ def measure(name, type_name, players, hi, args, seed):
         b.close()
     assert env.error_flags() == 0
     env.close()
-    fmt = lambda v: "%8.1f us (%.1f .. %.1f over %d repeats)" % (statistics.median(v), min(v), max(v), len(v))
     step_us = statistics.median(lock) if lock else None
     share = lambda v: "" if step_us is None else "  = %.2f %% of a step" % (100.0 * statistics.median(v) / step_us)
     print("== %s: %d environments, medians of %d calls" % (name, E, args.calls))
@@ -164,10 +122,7 @@ def measure(name, type_name, players, hi, args, seed):
 def main(argv=None):
     args = parse_args(argv)
     results = [measure(name, type_name, players, hi, args, 42) for name, type_name, players, hi in CONFIGS]
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-    return results
+    return write_json(results, args.out)
 
 
 if __name__ == "__main__":

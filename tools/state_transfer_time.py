@@ -7,34 +7,15 @@ preallocated buffers, median (min .. max) of --calls calls after a warm-up, next
 n x state_size bytes timed the same way in the same run.  "Rate" is blob bytes per second (n x state_size / time) for the kernels and
 for the copy alike.  --repeats repeats the whole measurement on fresh handles: the run-to-run spread.
 Usage (GPU box): python tools/state_transfer_time.py [--envs 4096] [--calls 20] [--repeats 3] [--out FILE]"""
-import argparse
-import ctypes as C
-import json
-import os
 import statistics
 import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-from dynenv_amd import BatchedDynEnv, DynEnvType, _capi  # noqa: E402
+from timing_common import action_pool, base_parser, event_times, mid_episode, parse_positive, write_json
 
-
-def event_times(f, calls, warmup=5):
-    """device microseconds of each of `calls` calls of f, every call between its own pair of events"""
-    for _ in range(warmup):
-        f()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        f()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3)
-    return out
+import numpy as np
+import torch
+from dynenv_amd import BatchedDynEnv, DynEnvType, _capi
 
 
 def summary(us):
@@ -43,11 +24,7 @@ def summary(us):
 
 def measure(name, env_type, players, hi, E, calls, seed):
     env = BatchedDynEnv(env_type, E, players, seed=seed)
-    env.reset_flat()
-    rng = np.random.default_rng(seed)
-    for _ in range(30):  # mid-episode: pedestrians under way, contacts cached
-        a = np.stack([rng.integers(0, h, (E, env.n_agents)) for h in hi], -1).astype(np.int32)
-        env.step_flat(torch.tensor(a, device="cuda"), auto_reset=False)
+    mid_episode(env, action_pool(torch, np, hi, E, env.n_agents, seed, n=30))   # (30 steps, each with actions of its own)
     torch.cuda.synchronize()
     size, lib, h = env.state_size, env._lib, env._h
     nbytes = E * size
@@ -63,19 +40,19 @@ def measure(name, env_type, players, hi, E, calls, seed):
     other = torch.empty_like(blobs)
     status = torch.empty((E,), dtype=torch.int32, device="cuda")
     stream = env._stream()
-    get = lambda: _capi.check(lib.dynenv_get_states(h, None, E, C.c_void_p(blobs.data_ptr()), stream), "dynenv_get_states")
-    put = lambda: _capi.check(lib.dynenv_set_states(h, None, E, C.c_void_p(blobs.data_ptr()), C.c_void_p(status.data_ptr()), stream),
+    get = lambda: _capi.check(lib.dynenv_get_states(h, None, E, _capi.ptr(blobs), stream), "dynenv_get_states")
+    put = lambda: _capi.check(lib.dynenv_set_states(h, None, E, _capi.ptr(blobs), _capi.ptr(status), stream),
                               "dynenv_set_states")
-    g = summary(event_times(get, calls))
+    g = summary(event_times(torch, get, calls, warmup=5))
     host = np.stack([np.frombuffer(bytes(s), np.uint8) for s in sts])
     assert np.array_equal(blobs.cpu().numpy(), host), "the batched read must be the loop's bytes"
-    s = summary(event_times(put, calls))
+    s = summary(event_times(torch, put, calls, warmup=5))
     assert int(status.abs().sum()) == 0 and env.error_flags() == 0
-    c = summary(event_times(lambda: other.copy_(blobs), calls))
+    c = summary(event_times(torch, lambda: other.copy_(blobs), calls, warmup=5))
     # (the permuted list: the same work through an index list)
     perm = torch.randperm(E, device="cuda").to(torch.int32)
-    gp = summary(event_times(lambda: _capi.check(lib.dynenv_get_states(h, C.c_void_p(perm.data_ptr()), E, C.c_void_p(blobs.data_ptr()), stream),
-                                                 "dynenv_get_states"), calls))
+    gp = summary(event_times(torch, lambda: _capi.check(lib.dynenv_get_states(h, _capi.ptr(perm), E, _capi.ptr(blobs), stream),
+                                                 "dynenv_get_states"), calls, warmup=5))
     env.close()
     rate = lambda t: nbytes / (t["median_us"] * 1e-6) / 1e9
     res = dict(config=name, envs=E, state_size=size, blob_bytes=nbytes, get_state_loop_s=t_get_loop, set_state_loop_s=t_set_loop,
@@ -92,21 +69,14 @@ def measure(name, env_type, players, hi, E, calls, seed):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--out", default=None, help="write the results as JSON to this file as well")
-    args = ap.parse_args()
+    args = parse_positive(base_parser(__doc__, calls_help="timed calls of every batched call"))
     results = []
     for r in range(args.repeats):
         print("---- repeat %d of %d" % (r + 1, args.repeats))
         results.append(measure("Driving, 10 cars", DynEnvType.DRIVE, 10, [3, 3], args.envs, args.calls, 42 + r))
         results.append(measure("RoboCup, 5 per team", DynEnvType.ROBO_CUP, 5, [5, 3, 3, 7], args.envs, args.calls, 42 + r))
         sys.stdout.flush()
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
+    write_json(results, args.out)
 
 
 if __name__ == "__main__":

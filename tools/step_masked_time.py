@@ -11,30 +11,18 @@ repeat (--repeats: the run-to-run spread).  Every variant's calls start from the
       (the median of three launches: a launch lasts as long as its slowest environment) and the slowest groups that make up a tenth
       of the batch are the ones left out.
 Usage (GPU box): python tools/step_masked_time.py [--envs 4096] [--calls 20] [--repeats 3] [--groups 64] [--out FILE]"""
-import argparse
-import ctypes as C
-import json
-import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from timing_common import CONFIGS, action_pool, base_parser, event_times, fmt, mid_episode, parse_positive, write_json
 
-CONFIGS = (("Driving Full, 10 cars", "DRIVE", 10, (3, 3)), ("RoboCup Full, 5 per team", "ROBO_CUP", 5, (5, 3, 3, 7)))
 VARIANTS = ("step", "masked_all", "masked_none", "masked_half", "masked_fast")
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--calls", type=int, default=20, help="timed calls per variant and repeat")
-    ap.add_argument("--repeats", type=int, default=3)
+    ap = base_parser(__doc__)
     ap.add_argument("--groups", type=int, default=64, help="groups of consecutive environments timed alone to find the slowest tenth")
-    ap.add_argument("--out", default=None, help="write the results as JSON to this file as well")
-    args = ap.parse_args(argv)
-    if args.envs < 1 or args.calls < 1 or args.repeats < 1 or args.groups < 1:
-        ap.error("--envs, --calls, --repeats and --groups must be positive")
-    return args
+    return parse_positive(ap, argv, also=("groups",))
 
 
 def group_bounds(E, groups):
@@ -61,45 +49,25 @@ def mask_bytes(E, listed):
     return m
 
 
-def event_times(torch, f, calls, warmup=3):
-    """device microseconds of each of `calls` calls of f, every call between its own pair of events"""
-    for _ in range(warmup):
-        f()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        f()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3)
-    return out
-
-
 def measure(name, type_name, players, hi, args, seed):
     import numpy as np
     import torch
     from dynenv_amd import BatchedDynEnv, DynEnvType, _capi
     E = args.envs
     env = BatchedDynEnv(getattr(DynEnvType, type_name), E, players, seed=seed, episodes="per_env")
-    A = env.n_agents
-    rng = np.random.default_rng(seed)
-    acts = [torch.tensor(np.stack([rng.integers(0, h, (E, A)) for h in hi], -1).astype(np.int32), device="cuda") for _ in range(16)]
-    env.reset_flat()
-    for s in range(30):  # mid-episode: pedestrians under way, contacts cached
-        env.step_flat(acts[s % len(acts)], auto_reset=False)
+    acts = action_pool(torch, np, hi, E, env.n_agents, seed)
+    mid_episode(env, acts)
     start = env.checkpoint()
     lib, h, stream = env._lib, env._h, env._stream()
-    obs, rew, don = (C.c_void_p(t.data_ptr()) for t in (env.obs, env.rewards, env.dones))
+    obs, rew, don = (_capi.ptr(t) for t in (env.obs, env.rewards, env.dones))
     nxt = [0]
 
     def action():
         nxt[0] += 1
-        return C.c_void_p(acts[nxt[0] % len(acts)].data_ptr())
+        return _capi.ptr(acts[nxt[0] % len(acts)])
 
     def masked(m):
-        ptr = C.c_void_p(m.data_ptr())
+        ptr = _capi.ptr(m)
         return lambda: _capi.check(lib.dynenv_step_masked(h, ptr, action(), None, obs, rew, don, stream), "dynenv_step_masked")
 
     def tensor(listed):
@@ -127,7 +95,6 @@ def measure(name, type_name, players, hi, args, seed):
             times[k].append(statistics.median(event_times(torch, calls[k], args.calls)))
     assert env.error_flags() == 0
     env.close()
-    fmt = lambda v: "%8.1f us (%.1f .. %.1f over %d repeats)" % (statistics.median(v), min(v), max(v), len(v))
     print("== %s: %d environments, medians of %d calls" % (name, E, args.calls))
     print("(a) dynenv_step                                %s" % fmt(times["step"]))
     print("(b) dynenv_step_masked, all listed             %s" % fmt(times["masked_all"]))
@@ -143,10 +110,7 @@ def measure(name, type_name, players, hi, args, seed):
 def main(argv=None):
     args = parse_args(argv)
     results = [measure(name, type_name, players, hi, args, 42) for name, type_name, players, hi in CONFIGS]
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-    return results
+    return write_json(results, args.out)
 
 
 if __name__ == "__main__":
