@@ -114,6 +114,8 @@ SIGNATURES = {
     "dynenv_arrange_gather": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, vp, i32, C.POINTER(vp), C.POINTER(vp), vp, vp]),
     "dynenv_arrange_scatter": (C.c_int, [vp, vp, i64, i32, vp, vp]),
     "dynenv_arrange_pad": (C.c_int, [C.POINTER(vp), vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "dynenv_arrange_pad_backward": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp), vp]),
+    "dynenv_arrange_scatter_backward": (C.c_int, [vp, vp, i64, i32, vp, vp]),
     "dynenv_checkpoint_size": (sz, [vp]),
     "dynenv_checkpoint_save": (C.c_int, [vp, vp, sz]),
     "dynenv_checkpoint_load": (C.c_int, [vp, vp, sz]),

@@ -7,6 +7,10 @@ The reference's input layer does, per forward pass, in triple-nested Python over
     outs, masks = arranger.rearrange_outputs(outs, counts, device)
 Here the same three calls exist with the same results, but `x` is the dense device tensor and all index work runs in the
 HIP kernels of `csrc/arranger_kernels.hip` through the C ABI (`dynenv_arrange_*`, include/dynenv.h).  No CPU fallback.
+
+Like the reference's (out[range] -> torch.cat -> F.pad -> torch.stack, models.py:250-274), `rearrange_outputs` is differentiable:
+the embedding blocks train through it (a torch.autograd.Function over `dynenv_arrange_pad_backward` /
+`dynenv_arrange_scatter_backward`).  `GpuInputLayer` is the three calls as one nn.Module.
 """
 import ctypes as C
 import os
@@ -40,13 +44,10 @@ class GpuInOutArranger(object):
         self.E, self.A, self.nTime, self.D = int(nEnvs), int(nAgents), int(nTime), int(obs_dim)
         self.nPlayers = self.E * self.A
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
-        TP = self.nTime * self.nPlayers
-        i32 = dict(dtype=torch.int32, device=self.device)
-        self._counts = torch.empty((self.nObjectTypes, self.nTime, self.nPlayers), **i32)
-        self._obj_counts = torch.empty((self.nTime, self.nPlayers), **i32)
-        self._base = torch.empty((self.nObjectTypes, self.nTime, self.nPlayers), **i32)
+        self._counts = self._obj_counts = self._base = None   # the latest rearrange_inputs call's plan (each call allocates its own)
+        self.last_backward = None                             # "fused" | "rows": the route the latest backward took
         n = int(self._lib.dynenv_arrange_scratch_ints(self.E, self.nTime, self.A, self.nObjectTypes))
-        self._scratch = torch.empty((n + 2,), **i32)
+        self._scratch = torch.empty((n + 2,), dtype=torch.int32, device=self.device)
         self.feats = [int(t.feat) for t in types]
 
     def _stream(self):
@@ -54,15 +55,22 @@ class GpuInOutArranger(object):
 
     def rearrange_inputs(self, obs, count_env=None):
         """obs: dense float32 device tensor [E, T, A, D]; count_env: int32 [E, 2] from BatchedDynEnv.counts() when a type
-        counts per environment.  Returns (inputs, (counts, maxCount, objCounts, slots)) like models.py:219-250:
-        inputs[i] float32 [N_i, feat_i] in (time, player, object) order; counts int32 [type, T, P]; objCounts [T, P]."""
+        counts per environment.  Returns (inputs, countArr) like models.py:219-250: inputs[i] float32 [N_i, feat_i] in (time, player,
+        object) order; countArr = (counts int32 [type, T, P], maxCount, objCounts [T, P], slots, mask) with `countArr.base` (see
+        ArrangePlan).  Every call's plan lives in buffers of its own: a countArr stays valid - for rearrange_outputs and for the
+        backward of what it returned - after any number of later calls (a trainer runs backward once at the end of a rollout)."""
         torch = self._torch
         assert obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous()
         assert tuple(obs.shape) == (self.E, self.nTime, self.A, self.D), (tuple(obs.shape), (self.E, self.nTime, self.A, self.D))
+        i32 = dict(dtype=torch.int32, device=self.device)
+        counts = torch.empty((self.nObjectTypes, self.nTime, self.nPlayers), **i32)
+        obj_counts = torch.empty((self.nTime, self.nPlayers), **i32)
+        base = torch.empty((self.nObjectTypes, self.nTime, self.nPlayers), **i32)
+        self._counts, self._obj_counts, self._base = counts, obj_counts, base   # (the latest plan)
         plan = _capi.ArrPlan()
         _capi.check(self._lib.dynenv_arrange_plan(_capi.ptr(obs), self.E, self.nTime, self.A, self.D, self.types,
-                                                  self.nObjectTypes, _capi.ptr(count_env), _capi.ptr(self._counts),
-                                                  _capi.ptr(self._obj_counts), _capi.ptr(self._base), _capi.ptr(self._scratch),
+                                                  self.nObjectTypes, _capi.ptr(count_env), _capi.ptr(counts),
+                                                  _capi.ptr(obj_counts), _capi.ptr(base), _capi.ptr(self._scratch),
                                                   C.byref(plan), self._stream()), "dynenv_arrange_plan")
         max_count = int(plan.max_count)
         inputs = [torch.empty((int(plan.total[i]), self.feats[i]), dtype=torch.float32, device=self.device)
@@ -73,16 +81,31 @@ class GpuInOutArranger(object):
         in_ptrs = (vp * self.nObjectTypes)(*[t.data_ptr() if t.numel() else None for t in inputs])
         sl_ptrs = (vp * self.nObjectTypes)(*[t.data_ptr() if t.numel() else None for t in slots])
         _capi.check(self._lib.dynenv_arrange_gather(_capi.ptr(obs), self.E, self.nTime, self.A, self.D, self.types,
-                                                    self.nObjectTypes, _capi.ptr(self._counts), _capi.ptr(self._base), max_count,
+                                                    self.nObjectTypes, _capi.ptr(counts), _capi.ptr(base), max_count,
                                                     in_ptrs, sl_ptrs, _capi.ptr(mask) if max_count else vp(0), self._stream()),
                     "dynenv_arrange_gather")
-        return inputs, (self._counts, max_count, self._obj_counts, slots, mask)
+        return inputs, ArrangePlan(counts, max_count, obj_counts, slots, mask, base)
+
+    def _plan_of(self, countArr):
+        """(counts, base, max_count, slots) of a countArr.  A plain tuple (rebuilt by the caller, no `.base`) gets its bases from
+        its own counts - the exclusive prefix in (time, player) order - never from whichever call came last."""
+        torch = self._torch
+        counts, max_count, _, slots, _ = countArr
+        base = getattr(countArr, "base", None)
+        if base is None:
+            flat = counts.reshape(self.nObjectTypes, -1)
+            base = (torch.cumsum(flat, 1) - flat).to(torch.int32).reshape(counts.shape).contiguous()
+        return counts, base, int(max_count), slots
 
     def rearrange_outputs(self, outs, countArr, device=None):
         """outs[i]: float32 [N_i, F] embeddings of inputs[i] (or None).  Returns (padded [T, maxCount, P, F],
-        masks = list over time of bool [P, maxCount]) like models.py:252-274."""
+        masks = list over time of bool [P, maxCount]) like models.py:252-274, and differentiable like it: when an outs[i]
+        requires grad, `padded` carries a grad_fn whose backward (csrc/arranger_kernels.hip, K5' / K4') hands every embedding
+        row the upstream gradient's row at its slot.  The masks are not differentiable outputs."""
         torch = self._torch
-        _, max_count, _, slots, mask = countArr
+        mask = countArr[4]
+        plan = self._plan_of(countArr)
+        slots = plan[3]
         if len(outs) != self.nObjectTypes:
             raise ValueError("rearrange_outputs: %d outputs for %d object types" % (len(outs), self.nObjectTypes))
         # a type without any object has out = None in the reference (:262); its counts are all zero, so it shifts nothing.
@@ -92,6 +115,18 @@ class GpuInOutArranger(object):
             if o is None and int(slots[i].shape[0]):
                 raise ValueError("rearrange_outputs: outs[%d] is None but object type %d has %d objects"
                                  % (i, i, int(slots[i].shape[0])))
+        if torch.is_grad_enabled() and any(o is not None and o.requires_grad for o in outs):
+            # float32 inside the Function; another dtype is cast out here, where torch differentiates the cast
+            outs = [o if o is None or o.dtype == torch.float32 else o.float() for o in outs]
+            padded = _arrange_function().apply(self, plan, *outs)
+        else:  # nothing to differentiate: the same launches as ever, no grad_fn
+            padded = self._pad(outs, *plan)
+        masks = [mask[t].bool() for t in range(self.nTime)]
+        return padded, masks
+
+    def _pad(self, outs, counts, base, max_count, slots):
+        """the forward of rearrange_outputs: one pass over the padded tensor, or zero fill + one scatter per type"""
+        torch = self._torch
         F = next(int(o.shape[1]) for o in outs if o is not None)
         ok = F % 4 == 0 and all(o is None or (o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and
                                               o.shape[1] == F and o.data_ptr() % 16 == 0) for o in outs)
@@ -103,7 +138,7 @@ class GpuInOutArranger(object):
             padded = torch.empty((self.nTime, max_count, self.nPlayers, F), dtype=torch.float32, device=self.device)
             vp = C.c_void_p
             ptrs = (vp * self.nObjectTypes)(*[o.data_ptr() if (o is not None and o.shape[0]) else None for o in outs])
-            _capi.check(self._lib.dynenv_arrange_pad(ptrs, _capi.ptr(self._counts), _capi.ptr(self._base), self.nObjectTypes,
+            _capi.check(self._lib.dynenv_arrange_pad(ptrs, _capi.ptr(counts), _capi.ptr(base), self.nObjectTypes,
                                                      self.nTime, self.nPlayers, max_count, F, _capi.ptr(padded),
                                                      self._stream()), "dynenv_arrange_pad")
         else:  # odd widths: zero fill + one scatter per type
@@ -114,5 +149,112 @@ class GpuInOutArranger(object):
                 out = out.contiguous().float()
                 _capi.check(self._lib.dynenv_arrange_scatter(_capi.ptr(out), _capi.ptr(slots[i]), int(out.shape[0]), F,
                                                              _capi.ptr(padded), self._stream()), "dynenv_arrange_scatter")
-        masks = [mask[t].bool() for t in range(self.nTime)]
-        return padded, masks
+        return padded
+
+    def _unpad(self, grad, rows, F, wanted, counts, base, max_count, slots):
+        """the backward of _pad: grad [T, maxCount, P, F] -> per type float32 [N_i, F] (None where rows[i] is None or the gradient
+        is not wanted).  One fused pass when F % 4 == 0 and every buffer is 16-byte aligned, whichever forward ran (its cost goes
+        with the objects, not with the padding); else one row gather per type.  self.last_backward names the route taken."""
+        torch = self._torch
+        g = grad.contiguous()   # (an attention layer often hands back a permuted view)
+        if g.dtype != torch.float32:
+            g = g.float()
+        assert tuple(g.shape) == (self.nTime, max_count, self.nPlayers, F), tuple(g.shape)
+        # every row is written: no zero fill
+        grads = [torch.empty((n, F), dtype=torch.float32, device=g.device) if (n is not None and w) else None
+                 for n, w in zip(rows, wanted)]
+        live = [ge is not None and ge.shape[0] > 0 for ge in grads]
+        self.last_backward = None
+        if max_count == 0 or not any(live):
+            return grads
+        vp = C.c_void_p
+        if F % 4 == 0 and g.data_ptr() % 16 == 0 and all(ge.data_ptr() % 16 == 0 for ge, l in zip(grads, live) if l):
+            ptrs = (vp * self.nObjectTypes)(*[ge.data_ptr() if l else None for ge, l in zip(grads, live)])
+            _capi.check(self._lib.dynenv_arrange_pad_backward(_capi.ptr(g), _capi.ptr(counts), _capi.ptr(base), self.nObjectTypes,
+                                                              self.nTime, self.nPlayers, max_count, F, ptrs, self._stream()),
+                        "dynenv_arrange_pad_backward")
+            self.last_backward = "fused"
+        else:
+            for i, ge in enumerate(grads):
+                if live[i]:
+                    _capi.check(self._lib.dynenv_arrange_scatter_backward(_capi.ptr(g), _capi.ptr(slots[i]), int(ge.shape[0]), F,
+                                                                          _capi.ptr(ge), self._stream()),
+                                "dynenv_arrange_scatter_backward")
+            self.last_backward = "rows"
+        return grads
+
+
+class ArrangePlan(tuple):
+    """The countArr of GpuInOutArranger.rearrange_inputs: the five entries (counts, maxCount, objCounts, slots, mask) - the
+    reference's three (models.py:248) in its order, then the two the kernels add - and, as the attribute `.base`, the int32
+    [type, T, P] start of every (time, player)'s objects inside inputs[i].  An attribute, not a sixth entry: callers unpack five."""
+
+    def __new__(cls, counts, max_count, obj_counts, slots, mask, base):
+        self = tuple.__new__(cls, (counts, max_count, obj_counts, slots, mask))
+        self.base = base
+        return self
+
+
+# torch is imported on first use (the package itself imports without it): the autograd Function and the nn.Module are built then.
+_lazy = {}
+
+
+def _arrange_function():
+    if "fn" not in _lazy:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class ArrangeOutputs(torch.autograd.Function):
+            """padded = arranger._pad(outs, plan); d padded / d outs[i] = arranger._unpad.  The plan is the forward call's own."""
+
+            @staticmethod
+            def forward(ctx, arr, plan, *outs):
+                ctx.arr, ctx.plan = arr, plan
+                ctx.rows = [None if o is None else int(o.shape[0]) for o in outs]
+                ctx.F = next(int(o.shape[1]) for o in outs if o is not None)
+                return arr._pad(outs, *plan)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad):
+                grads = ctx.arr._unpad(grad, ctx.rows, ctx.F, ctx.needs_input_grad[2:], *ctx.plan)
+                return (None, None) + tuple(grads)
+
+        _lazy["fn"] = ArrangeOutputs
+    return _lazy["fn"]
+
+
+def _input_layer_class():
+    if "layer" not in _lazy:
+        import torch
+
+        class GpuInputLayer(torch.nn.Module):
+            """The reference's InputLayer (models.py:278-307) over the dense observation tensor: rearrange_inputs -> one embedding
+            block per object type -> rearrange_outputs, differentiable down to the blocks' parameters.
+
+            GpuInputLayer(blocks, types, nEnvs, nAgents, nTime, obs_dim): `blocks` is the caller's own nn.ModuleList, one module per
+            object type of `types` (groups_for(env)[...]), each mapping [N, feat_i] -> [N, F]; the embedding network is the trainer's.
+            forward(obs, count_env=None) -> (padded [T, maxCount, E*A, F], masks).  A type without objects in this call does not run
+            its block and contributes None, as EmbedBlock returns for an empty input (:112-116): its parameters get no gradient."""
+
+            def __init__(self, blocks, types, nEnvs, nAgents, nTime, obs_dim):
+                super().__init__()
+                if len(blocks) != len(types):
+                    raise ValueError("GpuInputLayer: %d blocks for %d object types" % (len(blocks), len(types)))
+                self.blocks = blocks if isinstance(blocks, torch.nn.ModuleList) else torch.nn.ModuleList(blocks)
+                self.arranger = GpuInOutArranger(types, nEnvs, nAgents, nTime, obs_dim)
+
+            def forward(self, obs, count_env=None):
+                inputs, countArr = self.arranger.rearrange_inputs(obs, count_env)
+                outs = [block(x) if x.shape[0] else None for block, x in zip(self.blocks, inputs)]
+                return self.arranger.rearrange_outputs(outs, countArr)
+
+        GpuInputLayer.__qualname__ = "GpuInputLayer"
+        _lazy["layer"] = GpuInputLayer
+    return _lazy["layer"]
+
+
+def __getattr__(name):
+    if name == "GpuInputLayer":
+        return _input_layer_class()
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -369,6 +369,35 @@ int dynenv_arrange_pad(const float* const* emb_dev, const int32_t* counts_dev, c
   return launched();
 }
 
+// the backward of the two calls above.  Argument errors come before a device is looked for (as in dynenv_reset_masked): they are
+// the same with and without a GPU.
+int dynenv_arrange_pad_backward(const float* grad_padded_dev, const int32_t* counts_dev, const int32_t* base_dev, int32_t n_types,
+                                int32_t T, int32_t P, int32_t max_count, int32_t F, float* const* grad_emb_dev, void* stream) {
+  if (!grad_padded_dev || !counts_dev || !base_dev || !grad_emb_dev) return fail(DYNENV_ERR_ARG, "null argument");
+  if (n_types < 1 || n_types > DYNENV_ARR_MAX_TYPES || T < 1 || P < 1 || max_count < 0 || F < 4 || (F & 3)) return fail(DYNENV_ERR_ARG, "arranger: bad shape (F must be a multiple of 4)");
+  const long long perRow = (long long)P * (F / 4);
+  if (perRow > 0x7fffffffLL || T > 65535) return fail(DYNENV_ERR_ARG, "arranger: padded tensor too large for one launch");
+  if (int rc = have_device()) return rc;
+  if (max_count == 0) return DYNENV_OK;
+  float* g[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < n_types; ++i) g[i] = grad_emb_dev[i];
+  hipLaunchKernelGGL(arr_unpad_cols_kernel, dim3((unsigned)((perRow + ARR_BLOCK - 1) / ARR_BLOCK), (unsigned)T), dim3(ARR_BLOCK), 0, (hipStream_t)stream,
+                     reinterpret_cast<const float4*>(grad_padded_dev), counts_dev, base_dev, n_types, T, P, max_count, F / 4, g[0], g[1], g[2], g[3]);
+  return launched();
+}
+
+int dynenv_arrange_scatter_backward(const float* grad_padded_dev, const int32_t* slot_dev, int64_t N, int32_t F, float* grad_emb_dev, void* stream) {
+  if (N < 0 || F < 1) return fail(DYNENV_ERR_ARG, "bad argument");
+  if (N > 0 && (!grad_padded_dev || !slot_dev || !grad_emb_dev)) return fail(DYNENV_ERR_ARG, "null argument");
+  const long long nBlocks = (N > 0x7fffffffffffffffLL / F) ? -1 : ((long long)N * F + ARR_BLOCK - 1) / ARR_BLOCK;
+  if (nBlocks < 0 || nBlocks > 0x7fffffffLL) return fail(DYNENV_ERR_ARG, "arranger: too many rows for one launch");
+  if (int rc = have_device()) return rc;
+  if (N == 0) return DYNENV_OK;
+  hipLaunchKernelGGL(arr_unscatter_kernel, dim3((unsigned)nBlocks), dim3(ARR_BLOCK), 0, (hipStream_t)stream,
+                     grad_padded_dev, slot_dev, (long long)N, F, grad_emb_dev);
+  return launched();
+}
+
 int dynenv_obs_pack(const float* obs_dev, int64_t n_env_time, int32_t A, int32_t D, int32_t split, float* packed_dev, void* stream) {
   if (int rc = have_device()) return rc;
   if (!obs_dev || !packed_dev || n_env_time < 0 || A < 1 || D < 1 || split < 0 || split > D) return fail(DYNENV_ERR_ARG, "bad argument");

@@ -422,6 +422,26 @@ int dynenv_arrange_scatter(const float* emb_dev, const int32_t* slot_dev, int64_
  * float32 [N_i][F] (NULL for a type without objects); F must be a multiple of 4 and the buffers 16-byte aligned. */
 int dynenv_arrange_pad(const float* const* emb_dev, const int32_t* counts_dev, const int32_t* base_dev, int32_t n_types,
                        int32_t T, int32_t P, int32_t max_count, int32_t F, float* padded_dev, void* stream);
+/* Backward of phase 3.  The reference's rearrange_outputs (models.py:250-274) is out[range] -> torch.cat -> F.pad ->
+ * torch.stack, so autograd's derivative of catAndPad (:147-166) hands every embedding row the upstream gradient's row at
+ * that object's slot: nothing is summed, no row is used twice, padding slots have no gradient.
+ * Fused (preferred), the mirror of dynenv_arrange_pad: grad_emb_dev[i][base[i][t][p] + k][:] = grad_padded_dev[t][j][p][:]
+ * for k < counts[i][t][p], j running over the player's slots in type order.  grad_padded_dev is float32
+ * [T][max_count][P][F], contiguous; grad_emb_dev[i] is float32 [N_i][F], every row of which is written exactly once (no
+ * pre-zeroing), or NULL: no gradient wanted for type i, its slots are stepped over and not read.  F must be a multiple of
+ * 4 and all buffers 16-byte aligned.
+ * Errors, DYNENV_ERR_ARG, all reported before a device is looked for: a NULL grad_padded_dev, counts_dev, base_dev or
+ * grad_emb_dev; n_types outside 1..DYNENV_ARR_MAX_TYPES; T < 1, P < 1, max_count < 0; F < 4 or F & 3; P * F / 4 >= 2^31 or
+ * T > 65535 (the launch limits of dynenv_arrange_pad).  max_count == 0 launches nothing and returns DYNENV_OK. */
+int dynenv_arrange_pad_backward(const float* grad_padded_dev, const int32_t* counts_dev, const int32_t* base_dev,
+                                int32_t n_types, int32_t T, int32_t P, int32_t max_count, int32_t F,
+                                float* const* grad_emb_dev, void* stream);
+/* Backward of dynenv_arrange_scatter, one type per call, any F and any alignment:
+ * grad_emb_dev[n][:] = grad_padded_dev[slot_dev[n]][:] for the N embeddings of the type (slot_dev as dynenv_arrange_gather
+ * wrote it).  Errors, DYNENV_ERR_ARG, before a device is looked for: N < 0, F < 1, a NULL pointer with N > 0, N * F beyond
+ * one launch (2^31 blocks of 256).  N == 0 launches nothing and returns DYNENV_OK. */
+int dynenv_arrange_scatter_backward(const float* grad_padded_dev, const int32_t* slot_dev, int64_t N, int32_t F,
+                                    float* grad_emb_dev, void* stream);
 
 
 /* Device self-test of the deterministic math header: evaluates sincos/atan2/sqrt/div on n host-provided doubles and

@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Throughput of the GPU arranger on real observations at BASELINE sizes: one JSON line per config with
 the HBM roofline of the gather kernel and the numpy oracle (a restatement of the reference's InOutArranger) timed on a
-bounded sample.  Usage (GPU box):  python tools/bench_arranger.py [--envs 4096] [--feat 128]"""
+bounded sample.  Usage (GPU box):  python tools/bench_arranger.py [--envs 4096] [--feat 128] [--backward]
+
+--backward adds, from the same run and on the same plan: the backward of rearrange_outputs (GpuInOutArranger._unpad: the fused HIP
+kernel), the torch composition a user would write without it (per type G.reshape(-1, F).index_select(0, slot_i)) and the forward,
+each as the median over --reps of HIP-event timings of --inner back-to-back calls, the three taking turns inside every repetition;
+algorithmic bytes of the backward are 2 * n_obj * F * 4 (every gradient row read once and written once) plus counts and bases."""
 import argparse
 import json
 import os
@@ -14,11 +19,59 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+def backward_leg(torch, arr, outs, countArr, padded, args, plan_bytes):
+    """medians (ms) of the fused backward, the torch composition and the forward on one plan, and what they move"""
+    import statistics
+    F = args.feat
+    plan = arr._plan_of(countArr)
+    slots = plan[3]
+    rows = [int(o.shape[0]) for o in outs]
+    wanted = [True] * len(outs)
+    G = torch.randn(tuple(padded.shape), device=padded.device)
+    legs = {
+        "backward": lambda: arr._unpad(G, rows, F, wanted, *plan),
+        "torch_index_select": lambda: [G.reshape(-1, F).index_select(0, s) for s, n in zip(slots, rows) if n],
+        "forward": lambda: arr.rearrange_outputs(outs, countArr),
+    }
+    got = legs["backward"]()
+    ref = legs["torch_index_select"]()
+    assert arr.last_backward == "fused", "the fused kernel is what is measured (F % 4 == 0)"
+    assert all(torch.equal(a, b) for a, b in zip([g for g, n in zip(got, rows) if n], ref)), "backward != torch composition"
+    for fn in legs.values():   # warm-up of every shape
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in legs}
+    for _ in range(args.reps):
+        for k, fn in legs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _i in range(args.inner):
+                fn()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) / args.inner)
+    n_obj = sum(rows)
+    b_bwd = 2 * n_obj * F * 4 + plan_bytes                      # gradient rows read + written, counts and bases read
+    b_sel = 2 * n_obj * F * 4 + n_obj * 4                       # the same rows, one slot per row
+    b_fwd = n_obj * F * 4 + padded.numel() * 4 + plan_bytes     # embeddings read, every padded element written
+    out = {"reps": args.reps, "inner": args.inner, "occupancy": n_obj / (padded.numel() // F)}
+    for k, b in (("backward", b_bwd), ("torch_index_select", b_sel), ("forward", b_fwd)):
+        t = sorted(times[k])
+        med = statistics.median(t)
+        out[k] = {"median_ms": med, "min_ms": t[0], "p90_ms": t[int(0.9 * (len(t) - 1))], "alg_bytes": b,
+                  "achieved": b / (med * 1e-3) / 1e9, "unit": "GB/s"}
+    out["speedup_over_torch"] = out["torch_index_select"]["median_ms"] / out["backward"]["median_ms"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--feat", type=int, default=128, help="embedding width F of rearrange_outputs")
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--backward", action="store_true", help="also time the backward of rearrange_outputs against the torch composition")
+    ap.add_argument("--inner", type=int, default=10, help="--backward: calls between two events (keeps the queue full)")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -74,6 +127,7 @@ def main():
         oa.rearrange_outputs(o_outs, o_cnt)
         cpu_s = time.perf_counter() - t0
         agent_rows = E * env.n_agents * env.n_time_steps
+        bwd = backward_leg(torch, arr, outs, countArr, padded, args, TP * len(types) * 8) if args.backward else None
         print(json.dumps({
             "metric": "arranged agent-observations/s", "config": cfg, "envs": E, "players": E * env.n_agents,
             "time_steps": env.n_time_steps, "objects": n_obj, "max_count": countArr[1], "embed_width": args.feat,
@@ -85,6 +139,7 @@ def main():
             "cpu_baseline": {"kind": "port", "cores": 1, "value": Es * env.n_agents * env.n_time_steps / cpu_s,
                              "unit": "agent-observations/s",
                              "sample": "oracle/arranger.py (numpy restatement of InOutArranger) on the first %d envs, %.2f s" % (Es, cpu_s)},
+            **({"backward": bwd} if bwd is not None else {}),
         }))
         env.close()
 
