@@ -33,17 +33,22 @@ CFGS = {name: c for long, short, c in _TABLE for name in (long, short) if name} 
 NAMES = tuple(long for long, _, _ in _TABLE if long)   # the configurations of the masked reset, the masked step and the exact transfer
 
 
+def cfg_of(cfg):
+    """a configuration's record: `cfg` is a name of the table or - for a test module that has configurations of its own - the record"""
+    return cfg if isinstance(cfg, Cfg) else CFGS[cfg]
+
+
 def select(*names):
     """name -> record of the listed configurations, in that order: the table a test module parametrizes over"""
     return {n: CFGS[n] for n in names}
 
 
 def driving(cfg):
-    return CFGS[cfg].env_type == 1
+    return cfg_of(cfg).env_type == 1
 
 
 def agents(cfg):
-    return CFGS[cfg].players * (1 if driving(cfg) else 2)
+    return cfg_of(cfg).players * (1 if driving(cfg) else 2)
 
 
 def sub(cfg):   # `elapsed` per step, and the episode's length in it
@@ -62,7 +67,7 @@ SENTINEL = 0x5EA71E55   # the int32 pattern obs is pre-filled with where no byte
 # ------------------------------------------------------------------------------------------------ handles, oracles, actions
 def make(cfg, E, seed=SEED, off=0, **kw):
     from dynenv_amd import BatchedDynEnv, DynEnvType, NoiseType, ObservationType
-    c = CFGS[cfg]
+    c = cfg_of(cfg)
     if c.partial:
         kw.update(observationType=ObservationType.PARTIAL, noiseType=NoiseType.REALISTIC, noiseMagnitude=3)
     return BatchedDynEnv(DynEnvType.DRIVE if c.env_type == 1 else DynEnvType.ROBO_CUP, E, c.players, seed=seed, env_id_offset=off, flags=c.flags, **kw)
@@ -70,7 +75,7 @@ def make(cfg, E, seed=SEED, off=0, **kw):
 
 def oracle(cfg, E, seed=SEED, off=0, **kw):
     """the oracle of a batch of E environments (kw: threads)"""
-    c = CFGS[cfg]
+    c = cfg_of(cfg)
     if c.partial:
         kw.update(obs_type=1, noise_type=1, noise_magnitude=3.0)
     return ol.OracleEnv(env_type=c.env_type, num_envs=E, n_players=c.players, seed=seed, env_id_offset=off, flags=c.flags, **kw)
@@ -99,7 +104,7 @@ def _idle(cfg, a, envs):
 def actions(cfg, E, A, steps, seed, idle=()):
     """[steps] of int32 [E, A, K], uniformly random in the action space; the environments in `idle` take no action"""
     rng = np.random.default_rng(seed)
-    return [_idle(cfg, np.stack([rng.integers(0, h, (E, A)) for h in CFGS[cfg].highs], -1).astype(np.int32), idle) for _ in range(steps)]
+    return [_idle(cfg, np.stack([rng.integers(0, h, (E, A)) for h in cfg_of(cfg).highs], -1).astype(np.int32), idle) for _ in range(steps)]
 
 
 def step(env, a, **kw):
