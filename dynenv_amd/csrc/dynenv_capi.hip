@@ -28,6 +28,14 @@ int have_device(int* ndev, const char* msg) {
   return DYNENV_OK;
 }
 
+// dynenv_reset / dynenv_step / dynenv_full_obs: the Driving Full writer stores float4 where the row layout allows it, so an observation
+// buffer is 16-byte aligned (NULL, where NULL is allowed, passes).  An argument check like the NULL checks: before a device is looked
+// for, before the handle is dereferenced, nothing launched.
+static int obs_aligned(const float* p, const char* name) {
+  if ((uintptr_t)p % 16) return fail(DYNENV_ERR_ARG, std::string(name) + " must be 16-byte aligned (the observation writers store float4)");
+  return DYNENV_OK;
+}
+
 extern "C" {
 
 int dynenv_abi_version(void) { return DYNENV_ABI_VERSION; }
@@ -93,12 +101,14 @@ int dynenv_seed(dynenv_t* h, uint64_t seed) {
 
 int dynenv_reset(dynenv_t* h, float* obs_dev, void* stream) {
   if (!h) return fail(DYNENV_ERR_ARG, "null handle");
+  if (int rc = obs_aligned(obs_dev, "obs_dev")) return rc;
   ON_DEVICE(h);
   return h->reset_masked(nullptr, obs_dev, (hipStream_t)stream);
 }
 
 int dynenv_reset_masked(dynenv_t* h, const uint8_t* mask_dev, float* obs_dev, void* stream) {
   if (!h || !mask_dev) return fail(DYNENV_ERR_ARG, "null argument");
+  if (int rc = obs_aligned(obs_dev, "obs_dev")) return rc;
   ON_DEVICE(h);
   return h->reset_masked(mask_dev, obs_dev, (hipStream_t)stream);
 }
@@ -106,6 +116,7 @@ int dynenv_reset_masked(dynenv_t* h, const uint8_t* mask_dev, float* obs_dev, vo
 int dynenv_full_obs_dim(const dynenv_t* h) { return h ? h->full_dim : fail(DYNENV_ERR_ARG, "null handle"); }
 int dynenv_full_obs(dynenv_t* h, float* full_dev, void* stream) {
   if (!h || !full_dev) return fail(DYNENV_ERR_ARG, "null argument");
+  if (int rc = obs_aligned(full_dev, "full_dev")) return rc;
   ON_DEVICE(h);
   return h->full_obs(full_dev, (hipStream_t)stream);
 }
@@ -121,6 +132,7 @@ int dynenv_global_state(dynenv_t* h, float* state_dev, void* stream) {
 static int step_any(dynenv_t* h, const uint8_t* mask_dev, const int32_t* actions_dev, const double* head_dev, float* obs_dev, double* rewards_dev,
                     uint8_t* dones_dev, void* stream) {
   if (!h || !actions_dev || !rewards_dev || !dones_dev) return fail(DYNENV_ERR_ARG, "null argument");
+  if (int rc = obs_aligned(obs_dev, "obs_dev")) return rc;
   if (head_dev && !(h->cfg.flags & DYNENV_FLAG_ALLOW_HEAD_TURN))  // (RoboCup's switch: a Driving handle has no flags, dynenv_create)
     return fail(DYNENV_ERR_ARG, "the continuous head channel exists for RoboCup with DYNENV_FLAG_ALLOW_HEAD_TURN only");
   ON_DEVICE(h);

@@ -166,7 +166,10 @@ int dynenv_layout(const dynenv_t* h, dynenv_layout_t* out);
 int dynenv_seed(dynenv_t* h, uint64_t seed);
 
 /* (Re)build every environment's scene and write the first observation(s): obs_dev float32 [E, T, A, obs_dim].  The launches of
- * dynenv_reset_masked without a mask. */
+ * dynenv_reset_masked without a mask.
+ * Alignment: obs_dev must be 16-byte aligned here, in dynenv_reset_masked and in every step call (the observation writers store
+ * float4 where the row layout allows it); a non-NULL obs_dev that is not returns DYNENV_ERR_ARG before a device is looked for, and
+ * nothing is launched.  The other buffers of these calls need their element's natural alignment only. */
 int dynenv_reset(dynenv_t* h, float* obs_dev, void* stream);
 
 /* Reset exactly the environments e with mask_dev[e] != 0 (uint8 [E]; the dones_dev of the step before it is a valid mask).
@@ -188,6 +191,8 @@ int dynenv_reset_masked(dynenv_t* h, const uint8_t* mask_dev, float* obs_dev, vo
  * Does NOT auto-reset: the host mirror calls dynenv_reset after a terminal step (SubprocVecEnv semantics).
  * obs_dev may be NULL (no observation written) except for RoboCup with Partial observations, whose rewards contain the
  * observation reward of processSeens (RoboCupEnvironment.py:497-524) and come out of the same pass: DYNENV_ERR_ARG then.
+ * Alignment: a non-NULL obs_dev must be 16-byte aligned (dynenv_step, dynenv_step_head, dynenv_step_masked alike), else
+ * DYNENV_ERR_ARG: checked with the other arguments, before a device is looked for; no state changes and nothing is launched.
  * May be captured into a hipGraph (stream capture) and replayed: per-step scheduling counters move to the device on the first
  * captured call, for the rest of the handle's life (INTEGRATION.md "Scheduling, checkpoints and graphs"). */
 int dynenv_step(dynenv_t* h, const int32_t* actions_dev, float* obs_dev, double* rewards_dev, uint8_t* dones_dev,
@@ -197,7 +202,8 @@ int dynenv_step(dynenv_t* h, const int32_t* actions_dev, float* obs_dev, double*
  * [E, A, dynenv_full_obs_dim(h)] in the Full layout (Driving: self 9 | cars (A-1) x 7 | obstacles 20 x 4 | pedestrians 20 x 2 |
  * lanes 8 x 5; RoboCup: ball 4 | self 8 | robots (A-1) x 6).  This is what the reference puts into info['Full State'] /
  * info['Recon States'] after every step in every observation mode (getFullState, DrivingEnvironment.py:306-307,
- * RoboCupEnvironment.py:511-512) and what a caller needs after dynenv_set_state / dynenv_checkpoint_load. */
+ * RoboCupEnvironment.py:511-512) and what a caller needs after dynenv_set_state / dynenv_checkpoint_load.
+ * Alignment: full_dev must be 16-byte aligned, as obs_dev in dynenv_reset; DYNENV_ERR_ARG otherwise, nothing launched. */
 int dynenv_full_obs_dim(const dynenv_t* h);
 int dynenv_full_obs(dynenv_t* h, float* full_dev, void* stream);
 
