@@ -138,6 +138,9 @@ SIGNATURES = {
     "dynenv_exact_size": (sz, [vp]),
     "dynenv_get_exact": (C.c_int, [vp, vp, i32, vp, vp]),
     "dynenv_set_exact": (C.c_int, [vp, vp, i32, vp, vp, vp]),
+    "dynenv_arrange_fixed_gather": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, C.POINTER(i32), i32, vp, vp, C.POINTER(vp), vp, vp, vp]),
+    "dynenv_arrange_fixed_pad": (C.c_int, [C.POINTER(vp), vp, C.POINTER(i32), i32, i32, i32, i32, i32, vp, vp]),
+    "dynenv_arrange_fixed_pad_backward": (C.c_int, [vp, vp, C.POINTER(i32), i32, i32, i32, i32, i32, C.POINTER(vp), vp]),
 }
 EXPORTS = list(SIGNATURES)
 

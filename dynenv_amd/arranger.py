@@ -11,6 +11,10 @@ HIP kernels of `csrc/arranger_kernels.hip` through the C ABI (`dynenv_arrange_*`
 Like the reference's (out[range] -> torch.cat -> F.pad -> torch.stack, models.py:250-274), `rearrange_outputs` is differentiable:
 the embedding blocks train through it (a torch.autograd.Function over `dynenv_arrange_pad_backward` /
 `dynenv_arrange_scatter_backward`).  `GpuInputLayer` is the three calls as one nn.Module.
+
+Two modes.  The default pads to the largest object count of each batch, as the reference does, and so has to wait for the device to
+learn the shapes.  `fixed=...` works at capacities the caller fixes once (`dynenv_arrange_fixed_*`, csrc/arranger_fixed_kernels.hip):
+the same layout in the leading slots, zeros behind, no host round trip, capturable into a graph.
 """
 import ctypes as C
 import os
@@ -31,7 +35,14 @@ class GpuInOutArranger(object):
     """Same role and call sequence as the reference's InOutArranger(nObjectTypes, nPlayers, nTime) (models.py:208-216);
     `nPlayers` is E*A as in InputLayer (:283).  `types` describes where each object type lives in an observation row."""
 
-    def __init__(self, types, nEnvs, nAgents, nTime, obs_dim, device=None):
+    def __init__(self, types, nEnvs, nAgents, nTime, obs_dim, device=None, fixed=None):
+        """fixed=None: the reference's shapes - every call pads to the largest object count of ITS batch, which the host has to wait
+        for (dynenv_arrange_plan synchronises).  fixed=True or fixed=dict(max_count=M, rows=[...]): the fixed-shape mode
+        (dynenv_arrange_fixed_*): inputs[i] always has rows[i] rows per (time, player) - rows past the count are zero - and the
+        padded tensor always M slots; True means rows = the types' capacities and M = their sum.  Nothing is copied to the host
+        and nothing waited for, so the calls can be captured into a graph.  Objects beyond rows[i] or M are dropped, earlier types
+        winning, and counted per type in the persistent int32 tensor `self.dropped` (added to by every call; nothing here reads or
+        zeroes it)."""
         import torch
         if not torch.cuda.is_available():
             raise _capi.DynEnvError("dynenv_amd needs an MI355X (HIP device); there is no CPU fallback")
@@ -49,6 +60,16 @@ class GpuInOutArranger(object):
         n = int(self._lib.dynenv_arrange_scratch_ints(self.E, self.nTime, self.A, self.nObjectTypes))
         self._scratch = torch.empty((n + 2,), dtype=torch.int32, device=self.device)
         self.feats = [int(t.feat) for t in types]
+        self.fixed = fixed is not None and fixed is not False
+        if self.fixed:
+            caps = [int(t.cap) for t in types]
+            rows, max_count = (caps, sum(caps)) if fixed is True else (list(fixed["rows"]), fixed["max_count"])
+            self.rows, self.max_count = [int(r) for r in rows], int(max_count)
+            if len(self.rows) != self.nObjectTypes or any(not 0 <= r <= c for r, c in zip(self.rows, caps)) or self.max_count < 0:
+                raise ValueError("fixed: rows[i] in 0..cap_i for each of the %d object types (caps %s) and max_count >= 0, got %r"
+                                 % (self.nObjectTypes, caps, fixed))
+            self._rows_c = (C.c_int32 * self.nObjectTypes)(*self.rows)
+            self.dropped = torch.zeros((self.nObjectTypes,), dtype=torch.int32, device=self.device)
 
     def _stream(self):
         return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
@@ -58,13 +79,16 @@ class GpuInOutArranger(object):
         counts per environment.  Returns (inputs, countArr) like models.py:219-250: inputs[i] float32 [N_i, feat_i] in (time, player,
         object) order; countArr = (counts int32 [type, T, P], maxCount, objCounts [T, P], slots, mask) with `countArr.base` (see
         ArrangePlan).  Every call's plan lives in buffers of its own: a countArr stays valid - for rearrange_outputs and for the
-        backward of what it returned - after any number of later calls (a trainer runs backward once at the end of a rollout)."""
+        backward of what it returned - after any number of later calls (a trainer runs backward once at the end of a rollout).
+        In the fixed-shape mode: _rearrange_inputs_fixed."""
         torch = self._torch
         assert obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous()
         assert tuple(obs.shape) == (self.E, self.nTime, self.A, self.D), (tuple(obs.shape), (self.E, self.nTime, self.A, self.D))
         i32 = dict(dtype=torch.int32, device=self.device)
         counts = torch.empty((self.nObjectTypes, self.nTime, self.nPlayers), **i32)
         obj_counts = torch.empty((self.nTime, self.nPlayers), **i32)
+        if self.fixed:
+            return self._rearrange_inputs_fixed(obs, count_env, counts, obj_counts)
         base = torch.empty((self.nObjectTypes, self.nTime, self.nPlayers), **i32)
         self._counts, self._obj_counts, self._base = counts, obj_counts, base   # (the latest plan)
         plan = _capi.ArrPlan()
@@ -86,6 +110,84 @@ class GpuInOutArranger(object):
                     "dynenv_arrange_gather")
         return inputs, ArrangePlan(counts, max_count, obj_counts, slots, mask, base)
 
+    def _rearrange_inputs_fixed(self, obs, count_env, counts, obj_counts):
+        """rearrange_inputs of the fixed-shape mode: inputs[i] float32 [T*P*rows[i], feat_i] - rows[i] rows per (time, player), those past
+        the kept count zero - and a countArr of the same five entries: maxCount is the Python int M, `slots` holds None per type
+        (a row's slot is arithmetic here) and `.base` is None.  Two launches; nothing is read back."""
+        torch = self._torch
+        TP = self.nTime * self.nPlayers
+        inputs = [torch.empty((TP * r, f), dtype=torch.float32, device=self.device) for r, f in zip(self.rows, self.feats)]
+        mask = torch.empty((self.nTime, self.nPlayers, self.max_count), dtype=torch.uint8, device=self.device)
+        vp = C.c_void_p
+        in_ptrs = (vp * self.nObjectTypes)(*[t.data_ptr() if t.numel() else None for t in inputs])
+        _capi.check(self._lib.dynenv_arrange_fixed_gather(_capi.ptr(obs), self.E, self.nTime, self.A, self.D, self.types,
+                                                          self.nObjectTypes, _capi.ptr(count_env), self._rows_c, self.max_count,
+                                                          _capi.ptr(counts), _capi.ptr(obj_counts), in_ptrs,
+                                                          _capi.ptr(mask) if self.max_count else vp(0), _capi.ptr(self.dropped),
+                                                          self._stream()), "dynenv_arrange_fixed_gather")
+        return inputs, ArrangePlan(counts, self.max_count, obj_counts, [None] * self.nObjectTypes, mask, None)
+
+    def _rearrange_outputs_fixed(self, outs, countArr):
+        """rearrange_outputs of the fixed-shape mode: outs[i] float32 [T*P*rows[i], F] (None exactly where rows[i] == 0)"""
+        torch = self._torch
+        counts, max_count, _, _, mask = countArr
+        if len(outs) != self.nObjectTypes:
+            raise ValueError("rearrange_outputs: %d outputs for %d object types" % (len(outs), self.nObjectTypes))
+        if int(max_count) != self.max_count or tuple(counts.shape) != (self.nObjectTypes, self.nTime, self.nPlayers):
+            raise ValueError("rearrange_outputs: the countArr is not one of this fixed-shape arranger's")
+        TP = self.nTime * self.nPlayers
+        F = next((int(o.shape[1]) for o in outs if o is not None), None)
+        if F is None:
+            raise ValueError("rearrange_outputs: every output is None (fixed-shape mode with rows all zero)")
+        for i, o in enumerate(outs):
+            if o is None and self.rows[i]:
+                raise ValueError("rearrange_outputs: outs[%d] is None but object type %d has rows[%d] = %d" % (i, i, i, self.rows[i]))
+            if o is not None and tuple(o.shape) != (TP * self.rows[i], F):
+                raise ValueError("rearrange_outputs: outs[%d] is %s, not %s" % (i, tuple(o.shape), (TP * self.rows[i], F)))
+        # float32 and contiguous inside the Function; torch differentiates a cast or a copy made out here
+        outs = [o if o is None else (o if o.dtype == torch.float32 else o.float()).contiguous() for o in outs]
+        if F % 4 or any(o is not None and o.data_ptr() % 16 for o in outs):
+            raise _capi.DynEnvError("the fixed-shape arranger needs an embedding width that is a multiple of 4 (got %d) and 16-byte aligned "
+                                    "embeddings; it has no per-type scatter fallback: use the default mode (fixed=None)" % F)
+        if torch.is_grad_enabled() and any(o is not None and o.requires_grad for o in outs):
+            padded = _arrange_fixed_function().apply(self, counts, *outs)
+        else:
+            padded = self._pad_fixed(outs, counts, F)
+        return padded, [mask[t].bool() for t in range(self.nTime)]
+
+    def _type_ptrs(self, tensors):
+        return (C.c_void_p * self.nObjectTypes)(*[t.data_ptr() if (t is not None and t.numel()) else None for t in tensors])
+
+    def _pad_fixed(self, outs, counts, F):
+        """one launch: every element of the padded tensor [T, M, P, F] is written"""
+        padded = self._torch.empty((self.nTime, self.max_count, self.nPlayers, F), dtype=self._torch.float32, device=self.device)
+        if self.max_count == 0:   # (an empty tensor has no address to hand over, and the call would launch nothing)
+            return padded
+        _capi.check(self._lib.dynenv_arrange_fixed_pad(self._type_ptrs(outs), _capi.ptr(counts), self._rows_c, self.nObjectTypes,
+                                                       self.nTime, self.nPlayers, self.max_count, F, _capi.ptr(padded), self._stream()),
+                    "dynenv_arrange_fixed_pad")
+        return padded
+
+    def _unpad_fixed(self, grad, counts, F, wanted):
+        """the backward of _pad_fixed, one launch: per type float32 [T*P*rows[i], F], zero in the rows past the kept count; None where
+        rows[i] == 0 or the gradient is not wanted"""
+        torch = self._torch
+        g = grad.contiguous()   # (an attention layer often hands back a permuted view)
+        if g.dtype != torch.float32:
+            g = g.float()
+        if g.data_ptr() % 16:
+            g = g.clone()
+        assert tuple(g.shape) == (self.nTime, self.max_count, self.nPlayers, F), tuple(g.shape)
+        TP = self.nTime * self.nPlayers
+        make = torch.zeros if self.max_count == 0 else torch.empty   # (M == 0: nothing is launched and every gradient row is zero)
+        grads = [make((TP * r, F), dtype=torch.float32, device=g.device) if (r and w) else None for r, w in zip(self.rows, wanted)]
+        if self.max_count and any(ge is not None for ge in grads):
+            _capi.check(self._lib.dynenv_arrange_fixed_pad_backward(_capi.ptr(g), _capi.ptr(counts), self._rows_c, self.nObjectTypes,
+                                                                    self.nTime, self.nPlayers, self.max_count, F,
+                                                                    self._type_ptrs(grads), self._stream()),
+                        "dynenv_arrange_fixed_pad_backward")
+        return grads
+
     def _plan_of(self, countArr):
         """(counts, base, max_count, slots) of a countArr.  A plain tuple (rebuilt by the caller, no `.base`) gets its bases from
         its own counts - the exclusive prefix in (time, player) order - never from whichever call came last."""
@@ -103,6 +205,8 @@ class GpuInOutArranger(object):
         requires grad, `padded` carries a grad_fn whose backward (csrc/arranger_kernels.hip, K5' / K4') hands every embedding
         row the upstream gradient's row at its slot.  The masks are not differentiable outputs."""
         torch = self._torch
+        if self.fixed:
+            return self._rearrange_outputs_fixed(outs, countArr)
         mask = countArr[4]
         plan = self._plan_of(countArr)
         slots = plan[3]
@@ -224,6 +328,29 @@ def _arrange_function():
     return _lazy["fn"]
 
 
+def _arrange_fixed_function():
+    if "fixed_fn" not in _lazy:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class ArrangeOutputsFixed(torch.autograd.Function):
+            """padded = arranger._pad_fixed(outs, counts); d padded / d outs[i] = arranger._unpad_fixed.  The counts are the forward call's own."""
+
+            @staticmethod
+            def forward(ctx, arr, counts, *outs):
+                ctx.arr, ctx.counts = arr, counts
+                ctx.F = next(int(o.shape[1]) for o in outs if o is not None)
+                return arr._pad_fixed(outs, counts, ctx.F)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad):
+                return (None, None) + tuple(ctx.arr._unpad_fixed(grad, ctx.counts, ctx.F, ctx.needs_input_grad[2:]))
+
+        _lazy["fixed_fn"] = ArrangeOutputsFixed
+    return _lazy["fixed_fn"]
+
+
 def _input_layer_class():
     if "layer" not in _lazy:
         import torch
@@ -235,14 +362,22 @@ def _input_layer_class():
             GpuInputLayer(blocks, types, nEnvs, nAgents, nTime, obs_dim): `blocks` is the caller's own nn.ModuleList, one module per
             object type of `types` (groups_for(env)[...]), each mapping [N, feat_i] -> [N, F]; the embedding network is the trainer's.
             forward(obs, count_env=None) -> (padded [T, maxCount, E*A, F], masks).  A type without objects in this call does not run
-            its block and contributes None, as EmbedBlock returns for an empty input (:112-116): its parameters get no gradient."""
+            its block and contributes None, as EmbedBlock returns for an empty input (:112-116): its parameters get no gradient.
 
-            def __init__(self, blocks, types, nEnvs, nAgents, nTime, obs_dim):
+            fixed=True / fixed=dict(max_count=M, rows=[...]) (GpuInOutArranger): the fixed-shape mode - padded is [T, M, E*A, F] whatever
+            the batch holds, no call waits for the device, and the whole forward can be captured into a graph.  Every block then runs on
+            every call, on rows[i] rows per (time, player), because x.shape[0] is no longer decided by the batch; only a type with
+            rows[i] == 0 contributes None.  CAVEAT: the blocks also see the all-zero rows behind each player's objects (their output is
+            discarded and their gradient is zero), so they must be ROW-WISE - Linear, LayerNorm, activations, as the reference's
+            EmbedBlock; a block that mixes rows (BatchNorm in training mode, attention across rows) would let the zero rows leak into
+            the real ones."""
+
+            def __init__(self, blocks, types, nEnvs, nAgents, nTime, obs_dim, fixed=None):
                 super().__init__()
                 if len(blocks) != len(types):
                     raise ValueError("GpuInputLayer: %d blocks for %d object types" % (len(blocks), len(types)))
                 self.blocks = blocks if isinstance(blocks, torch.nn.ModuleList) else torch.nn.ModuleList(blocks)
-                self.arranger = GpuInOutArranger(types, nEnvs, nAgents, nTime, obs_dim)
+                self.arranger = GpuInOutArranger(types, nEnvs, nAgents, nTime, obs_dim, fixed=fixed)
 
             def forward(self, obs, count_env=None):
                 inputs, countArr = self.arranger.rearrange_inputs(obs, count_env)

@@ -15,6 +15,18 @@
 // the kernels of env_rows_kernels.hip, which this unit includes last (behind everything the step launches run)
 extern "C" __global__ void env_rows_save_kernel(EnvRowTable T, const int* __restrict__ idx, unsigned char* __restrict__ blobs);
 extern "C" __global__ void env_rows_load_kernel(EnvRowTable T, const int* __restrict__ idx, const unsigned char* __restrict__ blobs, int* __restrict__ status);
+// ... and those of arranger_fixed_kernels.hip, with the two structs they take by value
+struct ArrFixed { ArrTypes ty; int rows[DYNENV_ARR_MAX_TYPES]; int maxCount; };
+struct ArrFixedRows { int rows[DYNENV_ARR_MAX_TYPES]; };
+extern "C" __global__ void arrf_plan_kernel(const float* __restrict__ obs, int E, int T, int A, int D, ArrFixed fx, const int32_t* __restrict__ count_env, int jSpan,
+                                            int32_t* __restrict__ counts, int32_t* __restrict__ obj_counts, uint8_t* __restrict__ mask, int32_t* __restrict__ dropped);
+extern "C" __global__ void arrf_gather_kernel(const float* __restrict__ obs, int E, int T, int A, int D, ArrFixed fx, const int32_t* __restrict__ count_env,
+                                              float* in0, float* in1, float* in2, float* in3);
+extern "C" __global__ void arrf_pad_cols_kernel(const float* __restrict__ e0, const float* __restrict__ e1, const float* __restrict__ e2, const float* __restrict__ e3,
+                                                const int32_t* __restrict__ counts, ArrFixedRows rw, int nTypes, int T, int P, int maxCount, int F4,
+                                                float4* __restrict__ padded);
+extern "C" __global__ void arrf_unpad_cols_kernel(const float4* __restrict__ grad, const int32_t* __restrict__ counts, ArrFixedRows rw, int nTypes, int T, int P,
+                                                  int maxCount, int F4, float* __restrict__ g0, float* __restrict__ g1, float* __restrict__ g2, float* __restrict__ g3);
 
 static thread_local std::string g_err;
 int fail(int code, const std::string& msg) {
@@ -410,6 +422,85 @@ int dynenv_arrange_scatter_backward(const float* grad_padded_dev, const int32_t*
   return launched();
 }
 
+// ---- the arranger at fixed capacities (arranger_fixed_kernels.hip): launches only - nothing synchronised, allocated or copied to the
+// host, so every call may be captured.  Argument errors come before a device is looked for.
+int dynenv_arrange_fixed_gather(const float* obs_dev, int32_t E, int32_t T, int32_t A, int32_t D, const dynenv_arr_type_t* types,
+                                int32_t n_types, const int32_t* count_env_dev, const int32_t* rows, int32_t max_count, int32_t* counts_dev,
+                                int32_t* obj_counts_dev, float* const* inputs_dev, uint8_t* mask_dev, int32_t* dropped_dev, void* stream) {
+  if (!obs_dev || !rows || !counts_dev || !obj_counts_dev) return fail(DYNENV_ERR_ARG, "null argument");
+  if (E < 1 || T < 1 || A < 1 || D < 1 || (int64_t)E * T * A > (int64_t)1 << 30) return fail(DYNENV_ERR_ARG, "arranger: bad shape");
+  if (max_count < 0) return fail(DYNENV_ERR_ARG, "arranger: max_count < 0");
+  ArrFixed fx;
+  if (int rc = arr_types(types, n_types, D, fx.ty)) return rc;
+  const long long TP = (long long)E * T * A;
+  long long gatherBlocks = 0;
+  float* in[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < DYNENV_ARR_MAX_TYPES; ++i) fx.rows[i] = 0;
+  for (int i = 0; i < n_types; ++i) {
+    if (types[i].count_mode == DYNENV_ARR_COUNT_ENV && !count_env_dev) return fail(DYNENV_ERR_ARG, "arranger: count_env_dev missing");
+    if (rows[i] < 0 || rows[i] > types[i].cap) return fail(DYNENV_ERR_ARG, "arranger: rows[i] outside 0..cap");
+    fx.rows[i] = rows[i];
+    if (inputs_dev && rows[i] > 0) in[i] = inputs_dev[i];
+    const long long b = in[i] ? (TP * rows[i] * types[i].feat + ARR_BLOCK - 1) / ARR_BLOCK : 0;
+    gatherBlocks = b > gatherBlocks ? b : gatherBlocks;
+  }
+  fx.maxCount = max_count;
+  const int jSpan = max_count > 0 ? max_count : 1;
+  const long long planBlocks = (TP * jSpan + ARR_BLOCK - 1) / ARR_BLOCK;
+  if (planBlocks > 0x7fffffffLL || gatherBlocks > 0x7fffffffLL) return fail(DYNENV_ERR_ARG, "arranger: too many rows for one launch");
+  if (int rc = have_device()) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(arrf_plan_kernel, dim3((unsigned)planBlocks), dim3(ARR_BLOCK), 0, st, obs_dev, E, T, A, D, fx, count_env_dev, jSpan,
+                     counts_dev, obj_counts_dev, max_count > 0 ? mask_dev : (uint8_t*)nullptr, dropped_dev);
+  if (gatherBlocks > 0)
+    hipLaunchKernelGGL(arrf_gather_kernel, dim3((unsigned)gatherBlocks, (unsigned)n_types), dim3(ARR_BLOCK), 0, st, obs_dev, E, T, A, D, fx,
+                       count_env_dev, in[0], in[1], in[2], in[3]);
+  return launched();
+}
+
+// what the two pad calls share: shapes, launch limits, rows and the 16-byte alignment of the float buffers (NULL entries pass)
+static int arr_fixed_pad_args(const void* big, const void* const* per_type, const int32_t* counts_dev, const int32_t* rows, int32_t n_types,
+                              int32_t T, int32_t P, int32_t max_count, int32_t F, ArrFixedRows& rw) {
+  if (!big || !per_type || !counts_dev || !rows) return fail(DYNENV_ERR_ARG, "null argument");
+  if (n_types < 1 || n_types > DYNENV_ARR_MAX_TYPES || T < 1 || P < 1 || max_count < 0 || F < 4 || (F & 3)) return fail(DYNENV_ERR_ARG, "arranger: bad shape (F must be a multiple of 4)");
+  if ((long long)P * (F / 4) > 0x7fffffffLL || T > 65535 || (int64_t)T * P > (int64_t)1 << 30) return fail(DYNENV_ERR_ARG, "arranger: padded tensor too large for one launch");
+  if ((uintptr_t)big % 16) return fail(DYNENV_ERR_ARG, "arranger: buffers must be 16-byte aligned");
+  for (int i = 0; i < DYNENV_ARR_MAX_TYPES; ++i) {
+    rw.rows[i] = i < n_types ? rows[i] : 0;
+    if (rw.rows[i] < 0) return fail(DYNENV_ERR_ARG, "arranger: rows[i] < 0");
+    if (i < n_types && (uintptr_t)per_type[i] % 16) return fail(DYNENV_ERR_ARG, "arranger: buffers must be 16-byte aligned");
+  }
+  return DYNENV_OK;
+}
+
+int dynenv_arrange_fixed_pad(const float* const* emb_dev, const int32_t* counts_dev, const int32_t* rows, int32_t n_types, int32_t T,
+                             int32_t P, int32_t max_count, int32_t F, float* padded_dev, void* stream) {
+  ArrFixedRows rw;
+  if (int rc = arr_fixed_pad_args(padded_dev, (const void* const*)emb_dev, counts_dev, rows, n_types, T, P, max_count, F, rw)) return rc;
+  if (int rc = have_device()) return rc;
+  if (max_count == 0) return DYNENV_OK;
+  const float* e[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < n_types; ++i) e[i] = emb_dev[i];
+  const long long perRow = (long long)P * (F / 4);
+  hipLaunchKernelGGL(arrf_pad_cols_kernel, dim3((unsigned)((perRow + ARR_BLOCK - 1) / ARR_BLOCK), (unsigned)T), dim3(ARR_BLOCK), 0, (hipStream_t)stream,
+                     e[0], e[1], e[2], e[3], counts_dev, rw, n_types, T, P, max_count, F / 4, reinterpret_cast<float4*>(padded_dev));
+  return launched();
+}
+
+int dynenv_arrange_fixed_pad_backward(const float* grad_padded_dev, const int32_t* counts_dev, const int32_t* rows, int32_t n_types, int32_t T,
+                                      int32_t P, int32_t max_count, int32_t F, float* const* grad_emb_dev, void* stream) {
+  ArrFixedRows rw;
+  if (int rc = arr_fixed_pad_args(grad_padded_dev, (const void* const*)grad_emb_dev, counts_dev, rows, n_types, T, P, max_count, F, rw)) return rc;
+  if (int rc = have_device()) return rc;
+  if (max_count == 0) return DYNENV_OK;
+  float* g[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < n_types; ++i) g[i] = grad_emb_dev[i];
+  const long long perRow = (long long)P * (F / 4);
+  hipLaunchKernelGGL(arrf_unpad_cols_kernel, dim3((unsigned)((perRow + ARR_BLOCK - 1) / ARR_BLOCK), (unsigned)T), dim3(ARR_BLOCK), 0, (hipStream_t)stream,
+                     reinterpret_cast<const float4*>(grad_padded_dev), counts_dev, rw, n_types, T, P, max_count, F / 4, g[0], g[1], g[2], g[3]);
+  return launched();
+}
+
 int dynenv_obs_pack(const float* obs_dev, int64_t n_env_time, int32_t A, int32_t D, int32_t split, float* packed_dev, void* stream) {
   if (int rc = have_device()) return rc;
   if (!obs_dev || !packed_dev || n_env_time < 0 || A < 1 || D < 1 || split < 0 || split > D) return fail(DYNENV_ERR_ARG, "bad argument");
@@ -556,3 +647,4 @@ int dynenv_checkpoint_load(dynenv_t* h, const void* buf_host, size_t nbytes) {
 // device code only, behind everything above: no kernel a step launches moves (rc_layout_pad, robocup_kernels.hip)
 #include "robocup_reset.hip"
 #include "env_rows_kernels.hip"
+#include "arranger_fixed_kernels.hip"

@@ -449,6 +449,52 @@ int dynenv_arrange_pad_backward(const float* grad_padded_dev, const int32_t* cou
 int dynenv_arrange_scatter_backward(const float* grad_padded_dev, const int32_t* slot_dev, int64_t N, int32_t F,
                                     float* grad_emb_dev, void* stream);
 
+/* ---- the arranger at FIXED capacities: the same layout with every shape chosen by the caller, so that nothing is copied to the
+ * host and nothing waited for.  All three calls are launches only, ordered on `stream`: no synchronisation, no allocation, no
+ * host copy.  They may be captured into a hipGraph: pointers and sizes (rows, max_count, the types) are frozen into the graph,
+ * buffer contents are read at replay.  The caller chooses rows[i] in 0..types[i].cap, the rows of type i kept per (time, player)
+ * (a HOST array [n_types]), and max_count = M >= 0, the slots of the padded tensor.  With c_i(t,p) = clamp(count, 0, cap_i), the
+ * count of the calls above, the KEPT count is k_i(t,p) = min(c_i, rows[i], M - sum_{i'<i} k_i'): earlier types win.  Rows beyond
+ * a capacity are dropped and reported, never silently (as error bit 3): sum_{t,p}(c_i - k_i) is ADDED to dropped_dev[i].
+ * tp = t*P + p.  Whenever nothing is dropped (rows[i] >= c_i everywhere, M >= the batch's maxCount) the kept rows, the leading
+ * maxCount slots of the padded tensor and of the mask, and the kept rows of the gradients are bit for bit those of
+ * dynenv_arrange_plan / _gather / _pad / _pad_backward; behind maxCount the padded tensor is zero and the mask 1.
+ *
+ * dynenv_arrange_fixed_gather (rearrange_inputs, models.py:219-250; the mask: createMask :166-180), at most two launches:
+ *   counts_dev int32 [n_types][T][P] = k_i;  obj_counts_dev int32 [T][P] = sum_i k_i;
+ *   inputs_dev[i] float32 [T][P][rows[i]][feat_i] (the array or an entry may be NULL): row r < k_i holds the object's features,
+ *     row r >= k_i holds +0.0 exactly - the unused capacity of an observation row is never read;
+ *   mask_dev uint8 [T][P][M] (may be NULL): 1 where j >= obj_counts[t][p];
+ *   dropped_dev int32 [n_types] (may be NULL): sticky, added to with atomics; the caller zeroes it.
+ *   max_count == 0 still writes the counts (all zero), dropped and the zeroed inputs.
+ *   Errors, DYNENV_ERR_ARG, before a device is looked for: a NULL obs_dev, types, rows, counts_dev or obj_counts_dev; n_types
+ *   outside 1..DYNENV_ARR_MAX_TYPES; a type outside the observation row; rows[i] outside 0..cap_i; max_count < 0; count_env_dev
+ *   NULL with a DYNENV_ARR_COUNT_ENV type; E, T, A or D < 1; more than 2^31 blocks of 256 threads in a launch. */
+int dynenv_arrange_fixed_gather(const float* obs_dev, int32_t E, int32_t T, int32_t A, int32_t D,
+                                const dynenv_arr_type_t* types, int32_t n_types, const int32_t* count_env_dev,
+                                const int32_t* rows /* host [n_types] */, int32_t max_count, int32_t* counts_dev,
+                                int32_t* obj_counts_dev, float* const* inputs_dev, uint8_t* mask_dev, int32_t* dropped_dev,
+                                void* stream);
+/* dynenv_arrange_fixed_pad (rearrange_outputs, models.py:252-274, catAndPad :147-180), one launch: padded_dev float32
+ * [T][M][P][F]; slot j = sum_{i'<i} k_i' + r with r < k_i gets emb_dev[i][tp*rows[i] + r][:], emb_dev[i] being float32
+ * [T*P*rows[i]][F]; a NULL emb_dev[i] writes zeros in its slots; slots j >= obj_counts get +0.0.  EVERY element is written: no
+ * pre-zeroing.  counts_dev is what dynenv_arrange_fixed_gather wrote (k_i); it is clamped to 0..rows[i] and to the slots left,
+ * so reads and writes stay in bounds whatever it holds.
+ * Errors, DYNENV_ERR_ARG, before a device is looked for: a NULL emb_dev, counts_dev, rows or padded_dev; n_types outside
+ * 1..DYNENV_ARR_MAX_TYPES; rows[i] < 0; T < 1, P < 1, max_count < 0; F < 4 or F & 3; padded_dev or an emb_dev[i] not 16-byte
+ * aligned; T > 65535, P * F / 4 >= 2^31 or T * P > 2^30.  max_count == 0 launches nothing and returns DYNENV_OK. */
+int dynenv_arrange_fixed_pad(const float* const* emb_dev, const int32_t* counts_dev, const int32_t* rows, int32_t n_types,
+                             int32_t T, int32_t P, int32_t max_count, int32_t F, float* padded_dev, void* stream);
+/* Backward of dynenv_arrange_fixed_pad (autograd's derivative of catAndPad, models.py:147-180, as dynenv_arrange_pad_backward),
+ * one launch: grad_emb_dev[i][tp*rows[i] + r][:] = grad_padded_dev[t][j][p][:] for r < k_i and +0.0 for r >= k_i - the
+ * embedding block ran on the zero rows too and their output was discarded, so their gradient is zero.  Every row of every
+ * non-NULL grad_emb_dev[i] (float32 [T*P*rows[i]][F]) is written exactly once; a NULL entry (no gradient wanted) is stepped
+ * over unread; padding slots of grad_padded_dev are never read.  Errors and max_count == 0 as dynenv_arrange_fixed_pad (with
+ * max_count == 0 nothing is written: every gradient row is zero and the caller's to fill). */
+int dynenv_arrange_fixed_pad_backward(const float* grad_padded_dev, const int32_t* counts_dev, const int32_t* rows,
+                                      int32_t n_types, int32_t T, int32_t P, int32_t max_count, int32_t F,
+                                      float* const* grad_emb_dev, void* stream);
+
 
 /* Device self-test of the deterministic math header: evaluates sincos/atan2/sqrt/div on n host-provided doubles and
  * returns the raw results so tests can compare them bit-for-bit with the host evaluation. out: [n,5]. */
