@@ -141,6 +141,7 @@ SIGNATURES = {
     "dynenv_arrange_fixed_gather": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, C.POINTER(i32), i32, vp, vp, C.POINTER(vp), vp, vp, vp]),
     "dynenv_arrange_fixed_pad": (C.c_int, [C.POINTER(vp), vp, C.POINTER(i32), i32, i32, i32, i32, i32, vp, vp]),
     "dynenv_arrange_fixed_pad_backward": (C.c_int, [vp, vp, C.POINTER(i32), i32, i32, i32, i32, i32, C.POINTER(vp), vp]),
+    "dynenv_math_probe": (C.c_int, [i32, vp, i32, vp, i32]),
 }
 EXPORTS = list(SIGNATURES)
 

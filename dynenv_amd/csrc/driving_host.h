@@ -36,3 +36,5 @@ static_assert(PV_LIM_CARS <= PV_CAP_CARS && PV_LIM_OBST <= PV_CAP_OBST && PV_LIM
 // the Driving handle (driving_tu.hip holds its host code next to the kernels); dynenv_create configures and initialises it
 struct dynenv;
 __attribute__((visibility("hidden"))) dynenv* drv_new_handle();
+// dynenv_math_probe's launch in the Driving unit (this unit's -Os copies of the math routines): n rows, device buffers, the null stream
+__attribute__((visibility("hidden"))) int drv_math_probe_launch(const double* in_dev, int n, double* out_dev);

@@ -365,3 +365,13 @@ extern "C" int dynenv_math_selftest(const double* x, const double* y, int32_t n,
   hipFree(dx); hipFree(dy); hipFree(dout);
   return DYNENV_OK;
 }
+
+// dynenv_math_probe, this unit's half: every routine of include/dynenv_math.h as compiled HERE (-Os, this unit's own copies of the
+// out-of-line wrappers of dev_common.h).  The row is include/dynenv_math_probe.h's, shared with the dynenv_capi.hip unit and the oracle.
+// Behind everything else in the unit: no other kernel moves.
+#include "dynenv_math_probe.h"
+extern "C" __global__ void __launch_bounds__(64) drv_math_probe_kernel(const double* in, int n, double* out) { dm_probe_wave(in, n, out); }
+int drv_math_probe_launch(const double* in_dev, int n, double* out_dev) {
+  hipLaunchKernelGGL(drv_math_probe_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, in_dev, n, out_dev);
+  return launched();
+}

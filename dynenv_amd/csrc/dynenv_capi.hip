@@ -11,6 +11,7 @@
 #include "arranger_kernels.hip"
 #include "dynenv_host.h"
 #include "robocup_host.hip"
+#include "dynenv_math_probe.h"   /* (inline device code and two sizes: nothing is emitted here) */
 
 // the kernels of env_rows_kernels.hip, which this unit includes last (behind everything the step launches run)
 extern "C" __global__ void env_rows_save_kernel(EnvRowTable T, const int* __restrict__ idx, unsigned char* __restrict__ blobs);
@@ -27,6 +28,8 @@ extern "C" __global__ void arrf_pad_cols_kernel(const float* __restrict__ e0, co
                                                 float4* __restrict__ padded);
 extern "C" __global__ void arrf_unpad_cols_kernel(const float4* __restrict__ grad, const int32_t* __restrict__ counts, ArrFixedRows rw, int nTypes, int T, int P,
                                                   int maxCount, int F4, float* __restrict__ g0, float* __restrict__ g1, float* __restrict__ g2, float* __restrict__ g3);
+// ... and this unit's math probe (include/dynenv_math_probe.h), the last kernel of the unit
+extern "C" __global__ void rc_math_probe_kernel(const double* in, int n, double* out);
 
 static thread_local std::string g_err;
 int fail(int code, const std::string& msg) {
@@ -642,9 +645,42 @@ int dynenv_checkpoint_load(dynenv_t* h, const void* buf_host, size_t nbytes) {
   return h->checkpoint_loaded();
 }
 
+// diagnostics: one row of every routine of include/dynenv_math.h per input row (include/dynenv_math_probe.h), computed by the kernel of
+// the unit asked for - this one (-O3) or the Driving unit (-Os): each carries its own compiled copy of the header and of dev_common.h's
+// out-of-line wrappers.  Host buffers on both sides, the null stream, everything freed on every way out.
+int dynenv_math_probe(int32_t unit, const double* in_host, int32_t n, double* out_host, int32_t device_id) {
+  if (!in_host || !out_host) return fail(DYNENV_ERR_ARG, "null argument");
+  if (n < 0) return fail(DYNENV_ERR_ARG, "negative row count");
+  if (unit != DYNENV_MATH_UNIT_ROBOCUP && unit != DYNENV_MATH_UNIT_DRIVING) return fail(DYNENV_ERR_ARG, "unknown unit");
+  if (n == 0) return DYNENV_OK;
+  int ndev = 0;
+  if (int rc = have_device(&ndev, "no HIP device visible")) return rc;
+  if (device_id < 0 || device_id >= ndev) return fail(DYNENV_ERR_ARG, "device_id out of range");
+  DeviceGuard guard_(device_id);
+  if (!guard_.ok) return fail(DYNENV_ERR_HIP, "hipSetDevice failed");
+  struct Bufs {
+    double *in = nullptr, *out = nullptr;
+    ~Bufs() { (void)hipFree(in); (void)hipFree(out); }
+  } d;
+  const size_t inBytes = sizeof(double) * DM_PROBE_NIN * (size_t)n, outBytes = sizeof(double) * DM_PROBE_NOUT * (size_t)n;
+  HIP_OK(hipMalloc((void**)&d.in, inBytes));
+  HIP_OK(hipMalloc((void**)&d.out, outBytes));
+  HIP_OK(hipMemcpy(d.in, in_host, inBytes, hipMemcpyHostToDevice));
+  if (unit == DYNENV_MATH_UNIT_DRIVING) {
+    if (int rc = drv_math_probe_launch(d.in, n, d.out)) return rc;
+  } else {
+    hipLaunchKernelGGL(rc_math_probe_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, (const double*)d.in, (int)n, d.out);
+    if (int rc = launched()) return rc;
+  }
+  HIP_OK(hipMemcpy(out_host, d.out, outBytes, hipMemcpyDeviceToHost));  // (waits for the kernel: the null stream)
+  return DYNENV_OK;
+}
+
 }  // extern "C"
 
 // device code only, behind everything above: no kernel a step launches moves (rc_layout_pad, robocup_kernels.hip)
 #include "robocup_reset.hip"
 #include "env_rows_kernels.hip"
 #include "arranger_fixed_kernels.hip"
+// this unit's math probe: every routine of include/dynenv_math.h as compiled here (-O3), the row of include/dynenv_math_probe.h
+extern "C" __global__ void __launch_bounds__(64) rc_math_probe_kernel(const double* in, int n, double* out) { dm_probe_wave(in, n, out); }

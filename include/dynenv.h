@@ -500,6 +500,16 @@ int dynenv_arrange_fixed_pad_backward(const float* grad_padded_dev, const int32_
  * returns the raw results so tests can compare them bit-for-bit with the host evaluation. out: [n,5]. */
 int dynenv_math_selftest(const double* x_host, const double* y_host, int32_t n, double* out_host, int32_t device_id);
 
+/* Device probe of the deterministic math header, routine by routine and build by build.  The library is two translation units with
+ * their own optimisation level and their own compiled copy of include/dynenv_math.h: `unit` names the one whose kernel runs.
+ * in_host: [n, 4] doubles (a, b, c, d); out_host: [n, 29] doubles, the columns of include/dynenv_math_probe.h (DM_PROBE_NIN,
+ * DM_PROBE_NOUT) - every sincos and atan2 variant of the kernels, atan, sqrt, /, rint, fma, the solver's fused forms, powi, Philox,
+ * dm_unit, dm_randint.  Host buffers on both sides, one synchronous call, like dynenv_math_selftest.  NULL buffers, n < 0 or an unknown
+ * unit are DYNENV_ERR_ARG before a device is looked for; n == 0 is DYNENV_OK; no visible device is DYNENV_ERR_NO_DEVICE. */
+#define DYNENV_MATH_UNIT_ROBOCUP 0 /* the unit of the C ABI, the RoboCup and the arranger kernels */
+#define DYNENV_MATH_UNIT_DRIVING 1 /* the unit of the Driving kernels */
+int dynenv_math_probe(int32_t unit, const double* in_host, int32_t n, double* out_host, int32_t device_id);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,7 +43,7 @@ DM_FN double dm_clamp(double x, double lo, double hi) { return dm_min(dm_max(x, 
 
 DM_FN double dm_sqrt(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_sqrt(x); /* f64 sqrt is correctly rounded on gfx950 (checked by tests -m gpu) */
+  return __builtin_sqrt(x); /* f64 sqrt is correctly rounded on gfx950, denormals included (tests/test_gpu_detmath.py: whole double range, both builds) */
 #else
   return __builtin_sqrt(x);
 #endif

@@ -13,6 +13,7 @@
 #include "robocup_partial.h"
 #include "dynenv.h"
 #include "dynenv_math.h"
+#include "dynenv_math_probe.h"
 
 typedef struct oracle {
   dynenv_cfg_t cfg;
@@ -257,6 +258,12 @@ void oracle_math(const double* x, const double* y, int n, double* out) {
 void oracle_math_f(const double* x, int n, double* out) { /* dm_sincos_f: out[2 i] = sin, out[2 i + 1] = cos */
   int i;
   for (i = 0; i < n; ++i) dm_sincos_f(x[i], &out[2 * i], &out[2 * i + 1]);
+}
+/* the host side of dynenv_math_probe (include/dynenv_math_probe.h): in [n, DM_PROBE_NIN] -> out [n, DM_PROBE_NOUT].  The columns of the
+ * device-only variants hold what those claim to be: dm_atan2 for dev_atan2_t, dm_sincos_f for dev_sincos_v. */
+void oracle_math_probe(const double* in, int n, double* out) {
+  int i;
+  for (i = 0; i < n; ++i) dm_probe_row(in + (size_t)i * DM_PROBE_NIN, out + (size_t)i * DM_PROBE_NOUT, 0);
 }
 void oracle_philox(uint32_t k0, uint32_t k1, const uint32_t* ctr, uint32_t* out) {
   dm_u32x4 r = dm_philox(k0, k1, ctr[0], ctr[1], ctr[2], ctr[3]);

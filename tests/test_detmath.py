@@ -4,7 +4,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import detmath_common as dc
 import oracle_lib as ol
+from detmath_common import _fdlibm_atan2, _fdlibm_atan_pos, _fma  # noqa: F401  (the references live in tests/detmath_common.py)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -79,71 +81,12 @@ def test_philox4x32_10_known_answers():
         assert tuple(int(v) for v in o) == exp
 
 
-def _fma(a, b, c):
-    """a * b + c with one rounding, elementwise: exact rational arithmetic, then Fraction -> float (correctly rounded)"""
-    from fractions import Fraction
-
-    def one(x, y, z):
-        if not (np.isfinite(x) and np.isfinite(y) and np.isfinite(z)):
-            return x * y + z
-        r = Fraction(float(x)) * Fraction(float(y)) + Fraction(float(z))
-        if r == 0:
-            return x * y + z  # the sign of a zero result follows the IEEE rule of the unfused expression here
-        try:
-            return float(r)
-        except OverflowError:
-            return np.inf if r > 0 else -np.inf
-    a, b, c = np.broadcast_arrays(np.asarray(a, float), np.asarray(b, float), np.asarray(c, float))
-    return np.array([one(x, y, z) for x, y, z in zip(a.ravel(), b.ravel(), c.ravel())]).reshape(a.shape)
-
-
-def _fdlibm_atan_pos(ax):
-    """fdlibm __atan for ax >= 0 in its branching form (one arm per range), the polynomial's and the last range's multiply-adds
-    fused as include/dynenv_math.h fuses them; evaluated with numpy (IEEE double) and an exact fma"""
-    hi_t = np.array([4.63647609000806093515e-01, 7.85398163397448278999e-01, 9.82793723247329054082e-01, 1.57079632679489655800e+00])
-    lo_t = np.array([2.26987774529616870924e-17, 3.06161699786838301793e-17, 1.39033110312309984516e-17, 6.12323399573676603587e-17])
-    aT = [3.33333333333329318027e-01, -1.99999999998764832476e-01, 1.42857142725034663711e-01, -1.11111104054623557880e-01,
-          9.09088713343650656196e-02, -7.69187620504482999495e-02, 6.66107313738753120669e-02, -5.83357013379057348645e-02,
-          4.97687799461593236017e-02, -3.65315727442169155270e-02, 1.62858201153657823623e-02]
-    idx = np.where(ax < 0.4375, -1, np.where(ax < 0.6875, 0, np.where(ax < 1.1875, 1, np.where(ax < 2.4375, 2, 3))))
-    t = np.where(idx == -1, ax, np.where(idx == 0, (2.0 * ax - 1.0) / (2.0 + ax), np.where(idx == 1, (ax - 1.0) / (ax + 1.0),
-                 np.where(idx == 2, (ax - 1.5) / _fma(1.5, ax, 1.0), -1.0 / ax))))
-    z = t * t
-    w = z * z
-    s1 = z * _fma(w, _fma(w, _fma(w, _fma(w, _fma(w, aT[10], aT[8]), aT[6]), aT[4]), aT[2]), aT[0])
-    s2 = w * _fma(w, _fma(w, _fma(w, _fma(w, aT[9], aT[7]), aT[5]), aT[3]), aT[1])
-    hi, lo = hi_t[np.maximum(idx, 0)], lo_t[np.maximum(idx, 0)]
-    r = np.where(idx < 0, t - t * (s1 + s2), hi - (_fma(t, s1 + s2, -lo) - t))
-    r = np.where(ax < 3.7252902984619140625e-09, ax, r)
-    return np.where(ax >= 1.0e300, hi_t[3] + lo_t[3], r)
-
-
-def _fdlibm_atan2(y, x):
-    pi, pi_lo = 3.1415926535897931160e+00, 1.2246467991473531772e-16
-    aq = np.abs(y / x)
-    z = np.where(aq > 1.0e300, 1.5707963267948966, np.where((x < 0.0) & (aq < 1.0e-300), 0.0, _fdlibm_atan_pos(aq)))
-    sx, sy = np.signbit(x), np.signbit(y)
-    r = np.where(~sx, np.where(sy, -z, z), np.where(~sy, pi - (z - pi_lo), (z - pi_lo) - pi))
-    r = np.where(x == 0.0, np.where(sy, -1.5707963267948966, 1.5707963267948966), r)
-    return np.where(y == 0.0, np.where(sx, np.where(sy, -pi, pi), y), r)
-
-
 def test_atan2_is_the_branching_fdlibm_evaluation_bit_for_bit():
     """dm_atan2 selects numerator, denominator, hi and lo instead of branching over the five ranges (one division instead of
     five arms on a diverging wavefront); it must stay the same arithmetic: bit patterns against the branching form, over the
     simulators' ranges, the range boundaries +- a few ulp, extreme magnitudes, zeros and infinities.  (The first range's
     t - t s: the header computes 0 - (fma(t, s, -0) - t), and fma(t, s, -0) = t s rounded once = the product.)"""
-    rng = np.random.default_rng(5)
-    n = 4000
-    sp = np.array([0.0, -0.0, 1.0, -1.0, np.inf, -np.inf, 1e300, -1e300, 1e-300, -1e-300, 5e-324, -5e-324, 1e-310, 0.4375, 0.6875,
-                   1.1875, 2.4375, 3.7252902984619140625e-09, 2.0 ** -28, 1e308, 90.0, -90.0, 1e-9, 1e150, 1e-150])
-    gx, gy = np.meshgrid(sp, sp)
-    sgn = lambda: rng.choice([-1.0, 1.0], n)
-    bx = (rng.random(n) + 0.5) * sgn()
-    by = rng.choice([0.4375, 0.6875, 1.1875, 2.4375], n) * (1 + rng.integers(-3, 4, n) * 2.2e-16) * bx * sgn()
-    x = np.concatenate([gx.ravel(), (rng.random(n) - 0.5) * 2000.0, (rng.random(n) - 0.5) * 8.0, np.exp((rng.random(n) - 0.5) * 1400) * sgn(), rng.choice(sp, n), bx])
-    y = np.concatenate([gy.ravel(), (rng.random(n) - 0.5) * 2000.0, (rng.random(n) - 0.5) * 1e-3, np.exp((rng.random(n) - 0.5) * 1400) * sgn(), (rng.random(n) - 0.5) * 8.0, by])
-    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
+    x, y = dc.atan2_inputs(np.random.default_rng(5), 4000)
     out = np.zeros((len(x), 5))
     ol.lib().oracle_math(x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), len(x), out.ctypes.data_as(C.c_void_p))
     with np.errstate(all="ignore"):
@@ -151,3 +94,97 @@ def test_atan2_is_the_branching_fdlibm_evaluation_bit_for_bit():
     got = out[:, 2]
     same = (got.view(np.uint64) == ref.view(np.uint64)) | (np.isnan(got) & np.isnan(ref))
     assert same.all(), [(y[i], x[i], got[i], ref[i]) for i in np.flatnonzero(~same)[:5]]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The math probe (include/dynenv_math_probe.h) on the host: oracle_math_probe over the whole input table of tests/detmath_common.py,
+# every column against its independent reference.  tests/test_gpu_detmath.py then holds the device to the oracle AND to the same
+# references: what passes here makes the oracle a verified stand-in there.
+# ------------------------------------------------------------------------------------------------------------------------------------
+def test_probe_table_is_what_its_tags_promise():
+    """the header's sizes, and the properties of the input sets the other tests lean on"""
+    assert dc.header_sizes() == (dc.NIN, dc.NOUT)
+    tab = dc.table()
+    assert 3000 <= len(tab) <= 12000 and tab.inp.shape == (len(tab), 4)
+    a, b = tab.inp[:, 0], tab.inp[:, 1]
+    # sincos inside the contract: finite, |x| < 1e6; outside: nothing finite
+    for name in ("sincos.random", "sincos.quadrant", "sincos.tie", "sincos.tiny"):
+        assert (np.abs(a[tab.rows(name)]) < 1.0e6).all(), name
+    assert not np.isfinite(a[tab.rows("sincos.outside")]).any()
+    # the tie set: x * invpio2 within a few ulp of a half-integer, and some rows exactly on it
+    t = a[tab.rows("sincos.tie")] * dc.INVPIO2
+    frac = np.abs(t - np.floor(t) - 0.5)
+    assert (frac <= 8 * np.spacing(np.abs(t))).all() and (frac == 0.0).sum() >= 20
+    # the wavefront block: starts on a wavefront, and EVERY group of 64 rows holds the five ranges with both signs of x and of y
+    w0 = tab.start["atan2.wave"]
+    n = int(tab.rows("atan2.wave").sum())
+    assert w0 % 64 == 0 and n % 64 == 0 and n >= 64
+    for g in range(w0, w0 + n, 64):
+        x, y = a[g:g + 64], b[g:g + 64]
+        combos = set(zip(dc.atan_row(np.abs(y / x)).tolist(), (x < 0).tolist(), (y < 0).tolist()))
+        assert combos == {(r, sx, sy) for r in range(5) for sx in (False, True) for sy in (False, True)}, g
+    # the atan2 set holds the range bounds +- 3 ulp, denormals, infinities and signed zeros
+    x, y = a[tab.rows("atan2.host")], b[tab.rows("atan2.host")]
+    with np.errstate(all="ignore"):
+        q = np.abs(y / x)
+    for bound in dc.ATAN_BOUNDS:
+        assert (q == bound).any() and (q == np.nextafter(bound, 0.0)).any() and (q == np.nextafter(bound, 9.0)).any(), bound
+    assert np.isinf(x).any() and (np.abs(x) == 5e-324).any() and (np.signbit(x) & (x == 0)).any()
+    # rint's ties and the ends of the integers' range; the arithmetic sets reach the denormals and the infinities
+    r = a[tab.rows("rint")]
+    assert {0.5, 1.5, 2.5, -0.5, 2.0 ** 52 - 1, 2.0 ** 52 + 1, 2.0 ** 53, 0.49999999999999994, -0.49999999999999994} <= set(r.tolist())
+    ar = tab.inp[tab.rows("arith.log") | tab.rows("arith.edges")]
+    assert (np.abs(ar[np.isfinite(ar) & (ar != 0)]) < 2.2250738585072014e-308).any() and np.isinf(ar).any()
+    # the powi set: the five bases, exponents 0 and 4096 among them
+    pw = tab.inp[tab.rows("powi")]
+    assert set(pw[:, 0].tolist()) == set(dc.POWI_BASES) and {0.0, 1.0, 4096.0, 1074.0, 1075.0} <= set(pw[:, 1].tolist())
+
+
+def test_probe_exact_columns_match_their_references_bit_for_bit():
+    """/, sqrt, rint (numpy IEEE), fma and every dms_* (exact rational arithmetic, composed as the header composes them), dm_atan2 and
+    dm_atan (the branching fdlibm restatement), Philox, dm_unit and dm_randint (Python integers): bit patterns, over the whole table"""
+    tab, got, ref = dc.table(), dc.oracle_table(), dc.references()
+    assert set(ref) == set(range(dc.NOUT)) - set(dc.SINCOS_COLS) - {dc.COL["powi"]}
+    for col, want in sorted(ref.items()):
+        bad = dc.bit_mismatches(got[:, col], want, nan_equal=col not in dc.PACKED_COLS)
+        assert len(bad) == 0, dc.describe(tab.inp, tab.set_of, col, bad, got[:, col], want, "oracle_math_probe against the reference")
+    # the Random123 vectors sit in the table as they are published
+    p0 = tab.start["philox"]
+    for i, (_, _, exp) in enumerate(dc.PHILOX_KATS):
+        words = got[p0 + i, list(dc.PACKED_COLS)].view(np.uint64)
+        assert (int(words[0]) & dc.M32, int(words[0]) >> 32, int(words[1]) & dc.M32, int(words[1]) >> 32) == exp
+
+
+def test_probe_powi_within_the_bound_of_square_and_multiply():
+    """dm_powi against exact rational powers: relative error <= gamma(n - 1) = (n - 1) u / (1 - (n - 1) u), u = 2^-53 (n - 1 rounding
+    errors in all: tests/detmath_common.py derives the count), and the exact result for powers of two to the ends of the range"""
+    tab, got = dc.table(), dc.oracle_table()
+    assert float(dc.powi_bound(4096)) < 4096 * 2.0 ** -53 * (1 + 1e-12)
+    bad = dc.powi_failures(tab.inp, got[:, dc.COL["powi"]])
+    assert not bad, "\n".join("row %d (set %s): %s" % (i, tab.set_of(i), m) for i, m in bad[:5])
+    pw = tab.rows("powi")
+    assert (got[pw & (tab.inp[:, 0] == 1.0), dc.COL["powi"]] == 1.0).all()
+    assert (got[pw & (tab.inp[:, 1] == 0.0), dc.COL["powi"]] == 1.0).all()
+
+
+def test_probe_sincos_columns_on_the_host():
+    """sincos has no exact reference here: <= 2 ulp of libm over the ranges the environments use (NOT at the quadrant boundaries,
+    where the two-stage reduction loses relative accuracy by design), the out-of-line and the inline column the same function, NaN
+    outside the contract.  Everything else about these columns is the device test's: bit identity with this host evaluation."""
+    tab, got = dc.table(), dc.oracle_table()
+    r = tab.rows("sincos.random")
+    x = tab.inp[r, 0]
+    for k, f in ((0, np.sin), (1, np.cos), (4, np.sin), (5, np.cos)):
+        assert _ulps(got[r, k], f(x)).max() <= 2.0, dc.COLS[k]
+    assert _ulps(got[r, 4], got[r, 0]).max() <= 2.0 and _ulps(got[r, 5], got[r, 1]).max() <= 2.0
+    ok = dc.sincos_compared(tab.inp)
+    for k in (0, 1):
+        assert len(dc.bit_mismatches(got[ok, k], got[ok, k + 2], True)) == 0
+    out = tab.rows("sincos.outside")
+    assert out.sum() == 3 and np.isnan(got[out][:, list(dc.SINCOS_COLS)]).all()
+    inside = ok & np.isfinite(tab.inp[:, 0])
+    assert not np.isnan(got[inside][:, list(dc.SINCOS_COLS)]).any()
+    # exact values at the tiny end: sin x = x and cos x = 1 below 2^-28 (by value: the reduction turns sin(-0) into +0, on both sides)
+    tiny = tab.rows("sincos.tiny") & (np.abs(tab.inp[:, 0]) < 2.0 ** -28)
+    for k in (0, 4):
+        assert (got[tiny, k] == tab.inp[tiny, 0]).all() and (got[tiny, k + 1] == 1.0).all()
