@@ -5,6 +5,7 @@
 //   * owner of robot l (l < 10) for the joint solver: PivotJoint + RotaryLimitJoint of Robot.py:58-60
 //   * detector of collision pairs {l, 64+l, ...} of the 294 canonical pairs (5 rounds)
 //   * owner of contact-cache slot l (l < RC_NS)
+// In the general solve an arbiter's bias chain runs on lane slot + 16 and robot r's joints on lane RC_JOINT_LANE0 + r.
 // The order-dependent game logic (processAction / tick / isBallOutOfField and the collision callbacks with their
 // fall()/penalize() side effects) runs as a scalar program on lane 0 — it is strictly sequential in the reference.
 #pragma once
@@ -13,6 +14,7 @@
 #define RC_MAXR 10
 #define RC_NB 32
 #define RC_NS 16
+#define RC_JOINT_LANE0 32 /* the general solve's joint lanes start here, above the slot and bias lanes */
 #define RC_NPAIR_ROUNDS 5 /* ceil(294 / 64) */
 #define RC_BALL 20
 #define RC_POST 21

@@ -95,24 +95,10 @@ struct __align__(16) RcLds {
 static_assert(sizeof(RcLds) <= 10240, "16 one-wave workgroups per CU - one residency round of 4096 environments on 256 CUs - need <= 160 KB / 16 of LDS each");
 __shared__ RcLds g_R;
 
-// Grp<EPW>: the lanes that serve ONE environment and how they talk to each other.  EPW = 1, the only layout shipped: the whole
-// wave (cross-lane traffic through v_readlane with wave-uniform indices, masks in SGPRs).  (Round 2 measured two further
-// layouts through this interface - two environments per wave, one lane per robot - 4x less HBM traffic, 23 % slower; they are
-// in the repository's history, profiles/r02_robocup_variants_final.txt, and not in the product.)
-template <int EPW> struct Grp;
-template <> struct Grp<1> {
-  static constexpr int W = 64, JL0 = 32, OBS_BALL_LANE = 32;
-  DE_DEV static int lane() { return (int)threadIdx.x; }
-  DE_DEV static int id() { return 0; }
-  DE_DEV static RcLds& tile() { return g_R; }
-  DE_DEV static uint64_t ballot(bool p) { return __ballot(p); }
-  DE_DEV static uint64_t lt_mask() { return ::lanemask_lt(); }
-  DE_DEV static int bcast_i(int v, int src) { return ::bcast_i(v, src); }
-  DE_DEV static double bcast_d(double v, int src) { return ::bcast_d(v, src); }
-  DE_DEV static uint64_t uniform_u64(uint64_t v) { return ::uniform_u64(v); }
-  DE_DEV static int uniform_i(int v) { return ::uniform_i(v); }
-};
-#define RC_MY_PAIR(t) ((int)((((t) < 4 ? pairLo : (t) < 8 ? pairHi : pairTop) >> (16 * ((t)&3))) & 0xFFFFull))
+// One environment per wave is the only layout: the whole wave serves it, and its tile is g_R.
+// (The measured alternatives - two environments per wave, one lane per robot - are in profiles/r02_robocup_variants_final.txt.)
+static_assert(RC_NPAIR_ROUNDS <= 8, "a lane's pair codes are two words of four rounds each");
+#define RC_MY_PAIR(t) ((int)((((t) < 4 ? pairLo : pairHi) >> (16 * ((t)&3))) & 0xFFFFull))
 
 DE_DEV double rc_minv(int b) { return b == RC_BALL ? 1.0 / 10.0 : (b < RC_BALL ? 1.0 / ROBOT_MASS : 0.0); }
 DE_DEV double rc_iinv(int b) { return b == RC_BALL ? RC.ballIinv : (b < RC_BALL ? RC.footIinv : 0.0); }  // host-side 1.0 / inertia
@@ -231,10 +217,9 @@ DE_DEV void free_penalty_spot(const RcCtx& c, const RcLds& L, int r, V2& spot, d
   spot.y = lower ? RC_H - RC_SIDE : RC_SIDE;
 }
 
-template <int EPW>
 DE_OOL void rc_penalize(const RcCtx c_, int r) {  // :824-859
   const RcCtx c = rc_ctx_uniform(c_);
-  RcLds& L = Grp<EPW>::tile();
+  RcLds& L = g_R;
   const int teamIdx = robot_team(L, r) > 0 ? 0 : 1;
   int f = L.rflags[r];
   f |= RF_PENAL;
@@ -271,10 +256,9 @@ DE_DEV double shape_point_dist(const RcLds& L, int s, V2 p) {
   return dm_sqrt(vdot(d, d)) - FOOT_RADIUS;
 }
 
-template <int EPW>
 DE_OOL void rc_fall(const RcCtx c_, int r, int punish) {  // :735-791
   const RcCtx c = rc_ctx_uniform(c_);
-  RcLds& L = Grp<EPW>::tile();
+  RcLds& L = g_R;
   const V2 pos = robot_pos(L, r);
   if (punish) L.rrew[r] -= 2.0;
   for (int s = 0; s <= RC_BALL; ++s) {  // canonical slot order; goalposts are static (forces never integrated)
@@ -297,10 +281,9 @@ DE_OOL void rc_fall(const RcCtx c_, int r, int punish) {  // :735-791
   L.rflags[r] |= RF_FALLEN;
   L.fallc[r] += 1;
   L.fallT[r] = 4000.0;
-  if (L.fallc[r] > 2) rc_penalize<EPW>(c, r);
+  if (L.fallc[r] > 2) rc_penalize(c, r);
 }
 
-template <int EPW>
 DE_DEV void rc_process_action(const RcCtx& c, RcLds& L, int r, const int* action, const double* headAct) {  // :527-581
   const int move = action[0], turn = action[1], kick = action[2];
   double head = (double)action[3];  // a float with allowHeadTurn (Box(-3, 3), :339-342), an int otherwise: exact either way
@@ -315,7 +298,7 @@ DE_DEV void rc_process_action(const RcCtx& c, RcLds& L, int r, const int* action
   const bool canMove = !(f0 & (RF_PENAL | RF_KICK | RF_FALLEN));
   if (move > 0 && canMove) {
     const double rr = c.canFall ? dm_unit(u.v[0]) : 0.0;
-    if (rr > 0.999) { rc_fall<EPW>(c, r, 0); return; }
+    if (rr > 0.999) { rc_fall(c, r, 0); return; }
     if (!(L.rflags[r] & (RF_KICK | RF_PENAL | RF_FALLEN))) {  // Robot.step :103-119
       L.moveT[r] = 500.0;
       const int dir = move - 1;
@@ -335,7 +318,7 @@ DE_DEV void rc_process_action(const RcCtx& c, RcLds& L, int r, const int* action
   }
   if (turn > 0 && canMove) {
     const double rr = c.canFall ? dm_unit(u.v[1]) : 0.0;
-    if (rr > 0.999) { rc_fall<EPW>(c, r, 0); return; }
+    if (rr > 0.999) { rc_fall(c, r, 0); return; }
     if (!(L.rflags[r] & (RF_KICK | RF_PENAL | RF_FALLEN))) {  // Robot.turn :122-125
       L.moveT[r] = 500.0;
       L.w[2 * r] += (turn - 1) ? 20.0 : -20.0;
@@ -344,7 +327,7 @@ DE_DEV void rc_process_action(const RcCtx& c, RcLds& L, int r, const int* action
   if (head != 0.0) { L.headmov[r] = head * DM_PI / 720.0; L.moveT[r] = 500.0; }  // Robot.turnHead :136-138
   if (kick > 0 && move == 0 && turn == 0 && canMove) {
     const double rr = c.canFall ? dm_unit(u.v[2]) : 0.0;
-    if (rr > 0.99) { rc_fall<EPW>(c, r, 0); return; }
+    if (rr > 0.99) { rc_fall(c, r, 0); return; }
     int f = L.rflags[r];
     if (!(f & (RF_KICK | RF_PENAL | RF_FALLEN))) {  // Robot.kick :128-133
       const int foot = kick - 1;
@@ -359,7 +342,6 @@ DE_DEV void rc_process_action(const RcCtx& c, RcLds& L, int r, const int* action
 
 // The reference's tick, every branch: used by the sequential form (rc_game_serial).  The common substep runs the event-free
 // subset one robot per lane on registers (rc_game_logic_batched below).
-template <int EPW>
 DE_DEV void rc_tick(const RcCtx& c, RcLds& L, int r) {  // :862-1007
   const double time = RC_TIME;
   if (L.moveT[r] > 0.0) {
@@ -401,7 +383,7 @@ DE_DEV void rc_tick(const RcCtx& c, RcLds& L, int r) {  // :862-1007
     if (L.fallT[r] < 0.0) {
       const dm_u32x4 u = rc_rng(c, L, (uint32_t)r | (1u << 8));
       const double rr = dm_unit(u.v[0]);
-      if (rr > 0.9 && !(L.rflags[r] & RF_PENAL) && c.canFall) { rc_fall<EPW>(c, r, 0); return; }
+      if (rr > 0.9 && !(L.rflags[r] & RF_PENAL) && c.canFall) { rc_fall(c, r, 0); return; }
       L.rflags[r] &= ~RF_FALLEN;
       L.fallc[r] = 0;
     }
@@ -425,7 +407,7 @@ DE_DEV void rc_tick(const RcCtx& c, RcLds& L, int r) {  // :862-1007
     const bool isDef = (L.envi[RE_DEF0 + teamIdx] & bit) != 0;
     if (robX < penX && p.y > (RC_H / 2.0 - 110.0) && p.y < (RC_H / 2.0 + 110.0)) {
       if (!isDef) {
-        if (__popc(L.envi[RE_DEF0 + teamIdx]) >= 2) rc_penalize<EPW>(c, r);
+        if (__popc(L.envi[RE_DEF0 + teamIdx]) >= 2) rc_penalize(c, r);
         else L.envi[RE_DEF0 + teamIdx] |= bit;
       }
     } else if (isDef) {
@@ -433,7 +415,7 @@ DE_DEV void rc_tick(const RcCtx& c, RcLds& L, int r) {  // :862-1007
     }
   }
   const V2 pos = robot_pos(L, r);
-  if (pos.y < 0.0 || pos.x < 0.0 || pos.y > RC_H || pos.x > RC_W) rc_penalize<EPW>(c, r);
+  if (pos.y < 0.0 || pos.x < 0.0 || pos.y > RC_H || pos.x > RC_W) rc_penalize(c, r);
   if (pos.x != L.prevx[r] || pos.y != L.prevy[r]) {
     if ((r == L.envi[RE_CLOSE0] || r == L.envi[RE_CLOSE1]) && !(L.rflags[r] & RF_PENAL)) {
       const V2 ballPos = v2(L.px[RC_BALL], L.py[RC_BALL]);
@@ -481,7 +463,6 @@ __device__ unsigned long long g_rcprof4[4096 * 8];  // stages of the batched gam
 #else
 #define RC_PROF_G(...)
 #endif
-template <int EPW>
 DE_DEV bool rc_game_logic_batched(const RcCtx& c, RcLds& L, int lane, bool withTick) {
 RC_PROF_G(const unsigned long long G0 = __builtin_amdgcn_s_memtime(); unsigned long long G1 = G0, G2 = G0;)
   const int R = c.R, n = c.n;
@@ -525,7 +506,7 @@ RC_PROF_G(const unsigned long long G0 = __builtin_amdgcn_s_memtime(); unsigned l
       }
       if (rpos.y < 0.0 || rpos.x < 0.0 || rpos.y > RC_H || rpos.x > RC_W) ev = true;
     }
-    if (Grp<EPW>::ballot(ev) != 0ull) return false;
+    if (wave_ballot(ev) != 0ull) return false;
 RC_PROF_G(G1 = __builtin_amdgcn_s_memtime();)
     // ---- (2) the event-free tick (:862-1007) ----
     if (isRobot) {
@@ -642,7 +623,7 @@ RC_PROF_G(const unsigned long long G3 = __builtin_amdgcn_s_memtime();)
   {
     const bool t0 = lane < n, t1 = lane >= n && lane < 2 * n;
     const double m0 = rc_row_min(t0 ? q : INFINITY), m1 = rc_row_min(t1 ? q : INFINITY);
-    const uint64_t w0 = Grp<EPW>::ballot(t0 && q == m0 && q < INFINITY), w1 = Grp<EPW>::ballot(t1 && q == m1 && q < INFINITY);
+    const uint64_t w0 = wave_ballot(t0 && q == m0 && q < INFINITY), w1 = wave_ballot(t1 && q == m1 && q < INFINITY);
     best0 = w0 ? (int)__builtin_ctzll(w0) : 0;
     best1 = w1 ? (int)__builtin_ctzll(w1) - n : 0;
   }
@@ -679,22 +660,20 @@ RC_PROF_G(if (lane == 0 && c.genv < 4096u) { unsigned long long* d = g_rcprof4 +
 // The sequential form of the robots' game logic - for robot in agents: [processAction]; tick - for the first substep and for
 // substeps with a cross-robot event; out of line, called by lane 0 from the kernel.  (The ball's part follows in
 // rc_game_logic_batched, which the common substep then runs without its tick.)
-template <int EPW>
 DE_OOL void rc_game_serial(RcCtx c_, int it, const int* __restrict__ actions, const double* __restrict__ headAct) {
   const RcCtx c = rc_ctx_uniform(c_);
-  RcLds& L = Grp<EPW>::tile();
+  RcLds& L = g_R;
   for (int r = 0; r < c.R; ++r) {
     if (it == 0) {
       int act[4] = {actions[4 * r], actions[4 * r + 1], actions[4 * r + 2], actions[4 * r + 3]};
-      rc_process_action<EPW>(c, L, r, act, headAct);
+      rc_process_action(c, L, r, act, headAct);
     }
-    rc_tick<EPW>(c, L, r);
+    rc_tick(c, L, r);
   }
 }
 // ------------------------------------------------------------------------------------------------
 // collision callbacks (lane 0), RoboCupEnvironment.py:1010-1146
 // ------------------------------------------------------------------------------------------------
-template <int EPW>
 DE_DEV bool rc_cb_begin(const RcCtx& c, RcLds& L, int i, int j) {  // pair (i < j), returns "keep"
   if (j < RC_BALL) {  // robotPushingDet: shapes in collision order (a = lower slot)
     const int r1 = i >> 1, r2 = j >> 1;
@@ -713,7 +692,7 @@ DE_DEV bool rc_cb_begin(const RcCtx& c, RcLds& L, int i, int j) {  // pair (i < 
   if (j == RC_BALL) {  // ballCollision (foot i, ball)
     const int r = i >> 1;
     if (L.envi[RE_OWNED] != 0) {
-      if (robot_team(L, r) != L.envi[RE_OWNED] && !(L.rflags[r] & RF_PENAL) && c.canFall) rc_penalize<EPW>(c, r);
+      if (robot_team(L, r) != L.envi[RE_OWNED] && !(L.rflags[r] & RF_PENAL) && c.canFall) rc_penalize(c, r);
       else { L.envi[RE_OWNED] = 0; L.envd[RD_GRACE] = 0.0; L.envd[RD_FREECNT] = 0.0; }
     }
     push_last_kicked(L, r);
@@ -737,7 +716,6 @@ DE_DEV void rc_post_solve_dice(const RcCtx& c, const RcLds& L, int i, int j, dou
   const dm_u32x4 u = rc_rng(c, L, key | ((j < RC_BALL ? 2u : 3u) << 16));
   d0 = dm_unit(u.v[0]); d1 = dm_unit(u.v[1]);
 }
-template <int EPW>
 DE_DEV void rc_cb_post_solve(const RcCtx& c, RcLds& L, int i, int j, double dice0, double dice1) {
   if (!c.canFall) return;
   if (j < RC_BALL) {  // robotCollision :1039-1088
@@ -751,17 +729,17 @@ DE_DEV void rc_cb_post_solve(const RcCtx& c, RcLds& L, int i, int j, double dice
     L.touchc[r1] = t1; L.touchc[r2] = t2;
     const bool p1 = f1 & RF_PUSH, p2 = f2 & RF_PUSH;
     if (!(f1 & RF_FALLEN) && rc_dice_exceeds(dice0, p1 ? 0.99995 : 0.9999, p1 ? 5.0001e-5 : 1.0001e-4, t1)) {
-      rc_fall<EPW>(c, r1, p1 ? 1 : 0);
+      rc_fall(c, r1, p1 ? 1 : 0);
       L.touchc[r1] = 0;
     }
     if (!(f2 & RF_FALLEN) && rc_dice_exceeds(dice1, p2 ? 0.99995 : 0.9999, p2 ? 5.0001e-5 : 1.0001e-4, t2)) {
-      rc_fall<EPW>(c, r2, p2 ? 1 : 0);
+      rc_fall(c, r2, p2 ? 1 : 0);
       L.touchc[r2] = 0;
     }
     if (p1 != p2) {  // (the pushing bits are not touched by a fall; the fallen bits are: read them again)
       const bool diffTeam = robot_team(L, r1) != robot_team(L, r2);
-      if (p1 && (L.rflags[r2] & RF_FALLEN) && diffTeam) { rc_penalize<EPW>(c, r1); L.touchc[r1] = 0; }
-      else if (p2 && (L.rflags[r1] & RF_FALLEN) && diffTeam) { rc_penalize<EPW>(c, r2); L.touchc[r2] = 0; }
+      if (p1 && (L.rflags[r2] & RF_FALLEN) && diffTeam) { rc_penalize(c, r1); L.touchc[r1] = 0; }
+      else if (p2 && (L.rflags[r1] & RF_FALLEN) && diffTeam) { rc_penalize(c, r2); L.touchc[r2] = 0; }
     }
   } else if (j > RC_BALL && i < RC_BALL) {  // goalpostCollision :1106-1125
     const int r = i >> 1;
@@ -770,7 +748,7 @@ DE_DEV void rc_cb_post_solve(const RcCtx& c, RcLds& L, int i, int j, double dice
     if (!(f & RF_TOUCH)) { L.rflags[r] = f | RF_TOUCH; t = 0; }
     t += 1;
     L.touchc[r] = t;
-    if (rc_dice_exceeds(dice0, 0.9998, 2.0001e-4, t)) rc_fall<EPW>(c, r, 1);
+    if (rc_dice_exceeds(dice0, 0.9998, 2.0001e-4, t)) rc_fall(c, r, 1);
   }
 }
 
@@ -944,16 +922,6 @@ DE_DEV void rbody_load(const RcLds& L, int idx, RBody& b) {  // (a goalpost's sl
   b.p = v2(L.px[idx], L.py[idx]); b.v = v2(L.vx[idx], L.vy[idx]); b.w = L.w[idx];
   b.vb = v2(L.vbx[idx], L.vby[idx]); b.wb = L.wb[idx]; b.minv = rc_minv(idx); b.iinv = rc_iinv(idx);
 }
-DE_DEV void rbody_load_vel(const RcLds& L, int idx, RBody& b) {
-  if (idx <= RC_BALL) {
-    b.v = v2(L.vx[idx], L.vy[idx]); b.w = L.w[idx]; b.vb = v2(L.vbx[idx], L.vby[idx]); b.wb = L.wb[idx];
-  }
-}
-DE_DEV void rbody_store_vel(RcLds& L, int idx, const RBody& b) {
-  if (idx <= RC_BALL) {
-    L.vx[idx] = b.v.x; L.vy[idx] = b.v.y; L.w[idx] = b.w; L.vbx[idx] = b.vb.x; L.vby[idx] = b.vb.y; L.wb[idx] = b.wb;
-  }
-}
 // The arbiter solver's arithmetic with its multiply-adds FUSED: the dms_* functions of include/dynenv_math.h, the same ones
 // oracle/cp_lite.c calls (k_scalar_body_f, relative_velocity_f, apply_impulse_f ...).  (vrotate_f / vdot_f: driving_kernels.hip)
 DE_DEV double rk_scalar_body(const RBody& b, V2 r, V2 n) { return dms_k_scalar(b.minv, b.iinv, r.x, r.y, n.x, n.y); }
@@ -965,10 +933,6 @@ DE_DEV V2 rrelative_velocity(const RBody& a, const RBody& b, V2 r1, V2 r2) {
 DE_DEV void rapply_impulse(RBody& b, V2 j, V2 r) {
   b.v = v2(dm_fma(j.x, b.minv, b.v.x), dm_fma(j.y, b.minv, b.v.y));
   b.w = dm_fma(b.iinv, dms_cross(r.x, r.y, j.x, j.y), b.w);
-}
-DE_DEV void rapply_bias_impulse(RBody& b, V2 j, V2 r) {
-  b.vb = v2(dm_fma(j.x, b.minv, b.vb.x), dm_fma(j.y, b.minv, b.vb.y));
-  b.wb = dm_fma(b.iinv, dms_cross(r.x, r.y, j.x, j.y), b.wb);
 }
 // arbiter material: e = e_a * e_b, u = u_a * u_b in narrowphase order (a = circle / lower slot)
 DE_DEV void pair_material(int i, int j, double& e, double& u) {
@@ -1133,9 +1097,8 @@ DE_DEV void joints_solve(const RcJoint& J, RcFeet& f, double& jx, double& jy, do
     if (CLEAN && __ballot(!(jx == jx0 && jy == jy0 && jr == jr0)) == 0ull) break;
   }
 }
-template <int EPW>
 DE_DEV void rc_joints_only_inl(int lane, int R) {
-  RcLds& L = Grp<EPW>::tile();
+  RcLds& L = g_R;
   if (lane < R) {
     const int la = 2 * lane, lb = 2 * lane + 1;
     RcJoint J;
@@ -1162,9 +1125,7 @@ DE_DEV void rc_joints_only_inl(int lane, int R) {
 }
 
 // out of line where it runs inside the general path's caller (its own small register allocation)
-DE_OOL void rc_joints_only_ool(int lane, int R) { rc_joints_only_inl<1>(lane, R); }
-template <int EPW>
-DE_DEV void rc_joints_only(int lane, int R) { rc_joints_only_ool(lane, R); }
+DE_OOL void rc_joints_only_ool(int lane, int R) { rc_joints_only_inl(lane, R); }
 
 #ifdef DRV_PROFILE
 #define RC_PROF(...) __VA_ARGS__
@@ -1179,19 +1140,16 @@ struct RcStepRet {
   int err;
 };
 
-template <int EPW>
-DE_DEV RcStepRet rc_physics_inl(RcCtx c, int lane, int cand, uint64_t pairLo, uint64_t pairHi, uint64_t pairTop, uint64_t occ) {
-  typedef Grp<EPW> G;
-  constexpr int W = G::W, NROUNDS = (RC_NPAIR_ROUNDS * 64) / W;
-  // SPLIT: the two impulse chains of an arbiter's contact - velocity (normal + tangent) and position correction (bias) -
+DE_DEV RcStepRet rc_physics_inl(RcCtx c, int lane, int cand, uint64_t pairLo, uint64_t pairHi, uint64_t occ) {
+  // The two impulse chains of an arbiter's contact - velocity (normal + tangent) and position correction (bias) -
   // read and write disjoint body fields (v, w against v_bias, w_bias) and run the same instruction sequence up to the
-  // impulse vector; a lone wave pays per instruction, not per lane, so the bias chain moves to lane slot + 16.
-  constexpr bool SPLIT = W == 64 && RC_NS == 16 && G::JL0 == 32;  // an arbiter's bias impulses on lane slot + 16 beside its velocity impulses
-  RcLds& L = G::tile();
+  // impulse vector; a lone wave pays per instruction, not per lane, so the bias chain runs on lane slot + 16 beside
+  // the velocity chain on lane slot.
+  RcLds& L = g_R;
   RcMailbox& M = L.u.mb;
   int err = 0;
   bool biasLane = false;
-  const bool anyContactWork = G::ballot(cand != 0) != 0ull || occ != 0ull;
+  const bool anyContactWork = wave_ballot(cand != 0) != 0ull || occ != 0ull;
 RC_PROF(const unsigned long long T0 = __builtin_amdgcn_s_memtime(); unsigned long long C0 = T0, C1 = T0, C2 = T0, C3 = T0, C4 = T0;)
   // --- contact detection / cache -------------------------------------------------------------------------
   bool touched = false, slotOcc = false, freeMe = false, active = false;
@@ -1199,7 +1157,7 @@ RC_PROF(const unsigned long long T0 = __builtin_amdgcn_s_memtime(); unsigned lon
   int arank = 0, nActive = 0;  // canonical order among the active arbiters (cached with the levels)
   int myLevel = 0, maxLevel = -1;
   double jn[2] = {0.0, 0.0}, jt[2] = {0.0, 0.0};
-  double nMass[2] = {0.0, 0.0}, tMass[2] = {0.0, 0.0}, bias[2] = {0.0, 0.0}, bounce[2] = {0.0, 0.0}, jBias[2] = {0.0, 0.0};
+  double nMass[2] = {0.0, 0.0}, tMass[2] = {0.0, 0.0}, bias[2] = {0.0, 0.0}, bounce[2] = {0.0, 0.0};
   double arb_e = 0.0, arb_u = 0.0;
   V2 n = v2(0.0, 0.0), r1[2], r2[2];
   r1[0] = r1[1] = r2[0] = r2[1] = v2(0.0, 0.0);
@@ -1211,16 +1169,16 @@ RC_PROF(const unsigned long long T0 = __builtin_amdgcn_s_memtime(); unsigned lon
     // within a launch: it stays valid while every lane's candidate mask is the one it was built from (lastCand / candN).
     unsigned short* cl = L.candList;
     int nCand = 0;
-    const int prevCand = (int)L.lastCand[lane], savedN = G::uniform_i(L.candN);
+    const int prevCand = (int)L.lastCand[lane], savedN = uniform_i(L.candN);
     int spair = lane < RC_NS ? L.s_pair[lane] : -1;  // the slots' pairs for the slot search (one load, then v_readlane per occupied slot)
     if (lane < RC_NS) M.flag[lane] = 0;
-    if (savedN >= 0 && G::ballot(prevCand != (cand & 0xFF)) == 0ull) nCand = savedN;  // same masks as when the list was built: it is still there
+    if (savedN >= 0 && wave_ballot(prevCand != (cand & 0xFF)) == 0ull) nCand = savedN;  // same masks as when the list was built: it is still there
     else {
     // (straight-line over the five rounds: five ballots, v_mbcnt, masked stores - no loop-carried wait, no branch per round)
 #pragma unroll
-    for (int t = 0; t < NROUNDS; ++t) {
+    for (int t = 0; t < RC_NPAIR_ROUNDS; ++t) {
       const bool cbit = (cand >> t) & 1;
-      const uint64_t m = G::ballot(cbit);
+      const uint64_t m = wave_ballot(cbit);
       if (cbit) {
         const int idx = nCand + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         if (idx < 128) cl[idx] = (unsigned short)RC_MY_PAIR(t); else err |= 1;  // overflow is reported through RE_ERR
@@ -1234,26 +1192,26 @@ RC_PROF(const unsigned long long T0 = __builtin_amdgcn_s_memtime(); unsigned lon
     __syncthreads();
 RC_PROF(C0 = __builtin_amdgcn_s_memtime();)
 #pragma unroll 1
-    for (int pass = 0; pass * W < nCand; ++pass) {
-      const int pr = pass * W + lane < nCand ? (int)cl[pass * W + lane] : 0xFFFF;
+    for (int pass = 0; pass * DE_WAVE < nCand; ++pass) {
+      const int pr = pass * DE_WAVE + lane < nCand ? (int)cl[pass * DE_WAVE + lane] : 0xFFFF;
       const bool isCand = pr != 0xFFFF;
       RcContacts ct;
       ct.count = 0; ct.degenerate = false;
       if (isCand) rc_narrowphase(L, pr >> 8, pr & 0xFF, ct);
       const bool touch = isCand && ct.count > 0;
-      if (G::ballot(touch) == 0ull) continue;
+      if (wave_ballot(touch) == 0ull) continue;
       if (ct.degenerate) err |= 16;  // (a degenerate pair always has contacts: the check sits behind the early continue)
       int slot = -1;
       for (uint64_t mm = occ; mm; mm &= mm - 1) {
         int sidx = __builtin_ctzll(mm);
-        if (G::bcast_i(spair, sidx) == pr) slot = sidx;
+        if (bcast_i(spair, sidx) == pr) slot = sidx;
       }
       if (!touch) slot = -1;
       const bool needNew = touch && slot < 0;
-      const uint64_t newMask = G::ballot(needNew);
+      const uint64_t newMask = wave_ballot(needNew);
       if (newMask) {
         const uint64_t slotBits = (1ull << RC_NS) - 1ull;
-        int rk = __popcll(newMask & G::lt_mask());
+        int rk = __popcll(newMask & lanemask_lt());
         uint64_t fm = (~occ) & slotBits;
         if (needNew) {
           for (int r = 0; r < rk; ++r) fm &= fm - 1;
@@ -1317,14 +1275,14 @@ RC_PROF(C1 = __builtin_amdgcn_s_memtime();)
       }
     }
 RC_PROF(C2 = __builtin_amdgcn_s_memtime();)
-    touchedMask = G::ballot(touched);
+    touchedMask = wave_ballot(touched);
     nTouched = __popcll(touchedMask);
     // (the rank - canonical order among the touched arbiters - is needed by the begin callbacks and by a level computation; a call
     //  without a first contact whose active set is the previous evaluation's needs neither)
-    if (G::ballot(touched && a_state == ARB_FIRST_) != 0ull) {
+    if (wave_ballot(touched && a_state == ARB_FIRST_) != 0ull) {
       for (uint64_t mm = touchedMask; mm; mm &= mm - 1) {
         int b = __builtin_ctzll(mm);
-        int pk = G::bcast_i(a_pair, b);
+        int pk = bcast_i(a_pair, b);
         rank += (pk < a_pair) ? 1 : 0;
       }
     }
@@ -1332,9 +1290,9 @@ RC_PROF(C2 = __builtin_amdgcn_s_memtime();)
     // a robot: ballCollision -> penalize), then the begin callback of first contacts (scalar, lane 0)
     // (no first contact among the touched arbiters - the usual case - means no begin callback, nothing moves a body in between,
     //  and every touched lane takes its r1 / r2 at once instead of one lane after the other with an LDS round trip each)
-    const bool anyFirst = G::ballot(touched && a_state == ARB_FIRST_) != 0ull;
+    const bool anyFirst = wave_ballot(touched && a_state == ARB_FIRST_) != 0ull;
     for (int k = 0; k < (anyFirst ? nTouched : (nTouched ? 1 : 0)); ++k) {
-      const uint64_t who = G::ballot(touched && rank == k);
+      const uint64_t who = wave_ballot(touched && rank == k);
       const int b = __builtin_ctzll(who);
       if (anyFirst ? lane == b : touched) {
         const V2 pa = v2(L.px[bodyA], L.py[bodyA]), pb = v2(L.px[bodyB], L.py[bodyB]);
@@ -1346,10 +1304,10 @@ RC_PROF(C2 = __builtin_amdgcn_s_memtime();)
         }
       }
       if (!anyFirst) break;
-      const int st = G::bcast_i(a_state, b);
+      const int st = bcast_i(a_state, b);
       if (st != ARB_FIRST_) continue;
-      const int pk = G::bcast_i(a_pair, b);
-      if (lane == 0) rc_cb_begin<EPW>(c, L, pk >> 8, pk & 0xFF);  // every RoboCup begin handler returns True
+      const int pk = bcast_i(a_pair, b);
+      if (lane == 0) rc_cb_begin(c, L, pk >> 8, pk & 0xFF);  // every RoboCup begin handler returns True
       __syncthreads();
     }
     // separate callbacks + expiry of untouched slots, canonical order over ALL occupied slots
@@ -1359,19 +1317,19 @@ RC_PROF(C2 = __builtin_amdgcn_s_memtime();)
     }
     {
       const bool sepMe = slotOcc && !touched && a_state != ARB_CACHED_;
-      const uint64_t sepMask = G::ballot(sepMe);
+      const uint64_t sepMask = wave_ballot(sepMe);
       if (sepMask) {
         int srank = 0;
         for (uint64_t mm = sepMask; mm; mm &= mm - 1) {
           int b = __builtin_ctzll(mm);
-          int pk = G::bcast_i(a_pair, b);
+          int pk = bcast_i(a_pair, b);
           srank += (pk < a_pair) ? 1 : 0;
         }
         const int ns = __popcll(sepMask);
         for (int k = 0; k < ns; ++k) {
-          const uint64_t who = G::ballot(sepMe && srank == k);
+          const uint64_t who = wave_ballot(sepMe && srank == k);
           const int b = __builtin_ctzll(who);
-          const int pk = G::bcast_i(a_pair, b);
+          const int pk = bcast_i(a_pair, b);
           if (lane == 0) rc_cb_separate(L, pk >> 8, pk & 0xFF);
           __syncthreads();
         }
@@ -1381,27 +1339,27 @@ RC_PROF(C2 = __builtin_amdgcn_s_memtime();)
 RC_PROF(C3 = __builtin_amdgcn_s_memtime();)
     // levels of the active arbiters
     active = touched && a_state != ARB_IGNORE_;
-    activeMask = G::ballot(active);
+    activeMask = wave_ballot(active);
     // The schedule is a function of the active arbiters' pairs alone.  sActive is the active mask of the PREVIOUS evaluation (every
     // one records its own; slots only change in evaluations).  An arbiter active in two consecutive evaluations was touched in both,
     // so its slot was neither freed nor handed out again in between: same mask, same pairs, same schedule.
-    const bool lvHit = G::uniform_u64(c_active) == activeMask;
+    const bool lvHit = uniform_u64(c_active) == activeMask;
     nActive = __popcll(activeMask);
     if (!lvHit && lane == 0) L.sActive = activeMask;
-    if (lvHit) { myLevel = c_level & 15; arank = c_level >> 4; maxLevel = G::uniform_i(c_maxLevel); }
+    if (lvHit) { myLevel = c_level & 15; arank = c_level >> 4; maxLevel = uniform_i(c_maxLevel); }
     else {
     for (uint64_t mm = activeMask; mm; mm &= mm - 1) {  // canonical order among the ACTIVE arbiters (ascending pair id)
       int b = __builtin_ctzll(mm);
-      int pk = G::bcast_i(a_pair, b);
+      int pk = bcast_i(a_pair, b);
       arank += (pk < a_pair) ? 1 : 0;
     }
     int blvl = 0;
     for (int k = 0; k < nActive; ++k) {
-      const uint64_t who = G::ballot(active && arank == k);
+      const uint64_t who = wave_ballot(active && arank == k);
       const int b = __builtin_ctzll(who);
-      const int ba = G::bcast_i(bodyA, b), bb2 = G::bcast_i(bodyB, b);
-      const int la = ba <= RC_BALL ? G::bcast_i(blvl, ba) : 0;
-      const int lb = bb2 <= RC_BALL ? G::bcast_i(blvl, bb2) : 0;
+      const int ba = bcast_i(bodyA, b), bb2 = bcast_i(bodyB, b);
+      const int la = ba <= RC_BALL ? bcast_i(blvl, ba) : 0;
+      const int lb = bb2 <= RC_BALL ? bcast_i(blvl, bb2) : 0;
       const int lv = la > lb ? la : lb;
       if (lane == b) myLevel = lv;
       if (lane == ba || lane == bb2) blvl = lv + 1;
@@ -1424,48 +1382,47 @@ RC_PROF(C4 = __builtin_amdgcn_s_memtime();)
           tMass[q] = 1.0 / (rk_scalar_body(a, r1[q], vperp(n)) + rk_scalar_body(b, r2[q], vperp(n)));
           const double dist = vdot_f(vadd(vsub(r2[q], r1[q]), body_delta), n);
           bias[q] = -DE_CONTACT_BIAS_COEF * fmin_cp(0.0, dist + DE_COLLISION_SLOP) / DE_DT;
-          jBias[q] = 0.0;
           bounce[q] = vdot_f(rrelative_velocity(a, b, r1[q], r2[q]), n) * arb_e;
         }
       }
     }
-    if constexpr (SPLIT) {
-      if (activeMask != 0ull) {
-        RcArbShare& H = L.u.sh;  // overlays the mailbox, which nobody reads any more
-        __syncthreads();
-        if (active) {
-          H.code[lane] = bodyA | (bodyB << 8) | (a_count << 16) | (myLevel << 24);
-          double* d = H.d[lane];
-          d[0] = n.x; d[1] = n.y; d[2] = r1[0].x; d[3] = r1[0].y; d[4] = r1[1].x; d[5] = r1[1].y;
-          d[6] = r2[0].x; d[7] = r2[0].y; d[8] = r2[1].x; d[9] = r2[1].y;
-          d[10] = nMass[0]; d[11] = nMass[1]; d[12] = bias[0]; d[13] = bias[1];
-        }
-        __syncthreads();
-        const int sl = lane - 16;
-        if (sl >= 0 && sl < RC_NS && ((activeMask >> sl) & 1ull)) {
-          biasLane = true;
-          const int code = H.code[sl];
-          bodyA = code & 0xFF; bodyB = (code >> 8) & 0xFF; a_count = (code >> 16) & 0xFF; myLevel = (code >> 24) & 0xFF;
-          const double* d = H.d[sl];
-          n = v2(d[0], d[1]); r1[0] = v2(d[2], d[3]); r1[1] = v2(d[4], d[5]); r2[0] = v2(d[6], d[7]); r2[1] = v2(d[8], d[9]);
-          nMass[0] = d[10]; nMass[1] = d[11];
-          // the bias chain in the velocity chain's form: jbn = (bias - vbn) nMass = -((-bias) + vbn) nMass (the two can only
-          // differ in the sign of a zero jbn, which jBias = max(jBias + jbn, 0) with jBias >= +0 absorbs); no tangent part
-          bounce[0] = -d[12]; bounce[1] = -d[13];
-          jn[0] = jn[1] = jt[0] = jt[1] = 0.0; tMass[0] = tMass[1] = 0.0; arb_u = 0.0;
-        }
+    if (activeMask != 0ull) {  // hand every active arbiter's bias chain to lane slot + 16
+      RcArbShare& H = L.u.sh;  // overlays the mailbox, which nobody reads any more
+      __syncthreads();
+      if (active) {
+        H.code[lane] = bodyA | (bodyB << 8) | (a_count << 16) | (myLevel << 24);
+        double* d = H.d[lane];
+        d[0] = n.x; d[1] = n.y; d[2] = r1[0].x; d[3] = r1[0].y; d[4] = r1[1].x; d[5] = r1[1].y;
+        d[6] = r2[0].x; d[7] = r2[0].y; d[8] = r2[1].x; d[9] = r2[1].y;
+        d[10] = nMass[0]; d[11] = nMass[1]; d[12] = bias[0]; d[13] = bias[1];
+      }
+      __syncthreads();
+      static_assert(RC_NS == 16, "the bias lanes are the 16 lanes above the slot lanes, below the joint lanes");
+      const int sl = lane - 16;
+      if (sl >= 0 && sl < RC_NS && ((activeMask >> sl) & 1ull)) {
+        biasLane = true;
+        const int code = H.code[sl];
+        bodyA = code & 0xFF; bodyB = (code >> 8) & 0xFF; a_count = (code >> 16) & 0xFF; myLevel = (code >> 24) & 0xFF;
+        const double* d = H.d[sl];
+        n = v2(d[0], d[1]); r1[0] = v2(d[2], d[3]); r1[1] = v2(d[4], d[5]); r2[0] = v2(d[6], d[7]); r2[1] = v2(d[8], d[9]);
+        nMass[0] = d[10]; nMass[1] = d[11];
+        // the bias chain in the velocity chain's form: jbn = (bias - vbn) nMass = -((-bias) + vbn) nMass (the two can only
+        // differ in the sign of a zero jbn, which jBias = max(jBias + jbn, 0) with jBias >= +0 absorbs); no tangent part.
+        // The accumulated bias impulse jBias, zero at the prestep, lives in this lane's jn.
+        bounce[0] = -d[12]; bounce[1] = -d[13];
+        jn[0] = jn[1] = jt[0] = jt[1] = 0.0; tMass[0] = tMass[1] = 0.0; arb_u = 0.0;
       }
     }
   }
 RC_PROF(const unsigned long long T1 = __builtin_amdgcn_s_memtime();)
   // --- joints: prestep (cpPivotJoint / cpRotaryLimitJoint preStep), one robot per lane ------------------------
-  const bool jointsOnly = activeMask == 0ull;  // then rc_joints_only() below does prestep + solve out of line
+  const bool jointsOnly = activeMask == 0ull;  // then rc_joints_only_ool() below does prestep + solve out of line
   // General path: robot r's joints live on lane 32 + r.  Those lanes are never slot lanes (RC_NS <= 32), so the joint's
   // state OVERLAYS the registers that hold arbiter state on the slot lanes (jn/jt <-> accumulated joint impulses,
   // nMass/tMass <-> pivot K^-1, bias <-> pivot bias, bounce <-> iSum / rotary bias).  Holding both sets at once pushed
   // the joint constants to scratch inside the iteration loop.
-  static_assert(RC_NS <= G::JL0 && G::JL0 + RC_MAXR <= W, "joint lanes must not be slot lanes");
-  const int rl = lane - G::JL0;
+  static_assert(RC_NS <= RC_JOINT_LANE0 && RC_JOINT_LANE0 + RC_MAXR <= DE_WAVE, "joint lanes must not be slot lanes");
+  const int rl = lane - RC_JOINT_LANE0;
   const bool isRobot = rl >= 0 && rl < c.R && !jointsOnly;
   bool hasPivot = false, pivotFirst = true;
   if (isRobot) {
@@ -1489,13 +1446,13 @@ RC_PROF(const unsigned long long T3 = __builtin_amdgcn_s_memtime(); unsigned lon
   const int la = 2 * rl, lb = 2 * rl + 1;
   if (jointsOnly) {
 RC_PROF(T4 = __builtin_amdgcn_s_memtime();)
-    rc_joints_only<EPW>(lane, c.R);
+    rc_joints_only_ool(lane, c.R);
   } else {
     // --- warm start: arbiters (level by level), then joints -------------------------------------------------
     bool jointsDirty = false;
     {
       // (only v and w change; a goalpost reads its zeros and writes to the scratch slot, as in the iterations below)
-      const int nLvW = G::uniform_i(maxLevel) + 1;
+      const int nLvW = uniform_i(maxLevel) + 1;
       const int wa = bodyA <= RC_BALL ? bodyA : RC_NB - 1, wb_ = bodyB <= RC_BALL ? bodyB : RC_NB - 1;
       for (int lv = 0; lv < nLvW; ++lv) {
         if (active && myLevel == lv && a_state != ARB_FIRST_) {
@@ -1532,127 +1489,81 @@ RC_PROF(T4 = __builtin_amdgcn_s_memtime();)
 RC_PROF(T4 = __builtin_amdgcn_s_memtime();)
     // --- 10 iterations: all arbiters (canonical order via levels), then all constraints ----------------------
     RBody a, b;
-    if constexpr (!SPLIT) { if (active) { rbody_load(L, bodyA, a); rbody_load(L, bodyB, b); } }  // p, minv, iinv do not change during the solve
-    if constexpr (SPLIT) {
-      // velocity lanes (the slot lanes) work on (v, w), bias lanes on (v_bias, w_bias): same code, other fields
-      double* const fX = biasLane ? L.vbx : L.vx;
-      double* const fY = biasLane ? L.vby : L.vy;
-      double* const fW = biasLane ? L.wb : L.w;
-      const bool solveMe = active || biasLane;
-      const bool aDyn = bodyA <= RC_BALL, bDyn = bodyB <= RC_BALL;
-      a.minv = rc_minv(bodyA); a.iinv = rc_iinv(bodyA); b.minv = rc_minv(bodyB); b.iinv = rc_iinv(bodyB);  // (0 for a goalpost)
-      a.v = b.v = v2(0.0, 0.0); a.w = b.w = 0.0;
-      {
-        // A static partner (a goalpost) reads the zeros of its own, never written LDS slot and writes to a scratch slot nobody reads:
-        // no branch around the loads and stores.  (Its velocity is +0 after every finite impulse - x * 0 + 0 - so reloading the zeros
-        // is what keeping it in registers was.)
-        const bool cleanAll = G::ballot(jointsDirty) == 0ull;
-        bool notFinite = false;
-        const int nLv = G::uniform_i(maxLevel) + 1;
-        const int sa = aDyn ? bodyA : RC_NB - 1, sb = bDyn ? bodyB : RC_NB - 1;
-        const bool two = a_count > 1;
+    // velocity lanes (the slot lanes) work on (v, w), bias lanes on (v_bias, w_bias): same code, other fields
+    double* const fX = biasLane ? L.vbx : L.vx;
+    double* const fY = biasLane ? L.vby : L.vy;
+    double* const fW = biasLane ? L.wb : L.w;
+    const bool solveMe = active || biasLane;
+    const bool aDyn = bodyA <= RC_BALL, bDyn = bodyB <= RC_BALL;
+    a.minv = rc_minv(bodyA); a.iinv = rc_iinv(bodyA); b.minv = rc_minv(bodyB); b.iinv = rc_iinv(bodyB);  // (0 for a goalpost)
+    a.v = b.v = v2(0.0, 0.0); a.w = b.w = 0.0;
+    {
+      // A static partner (a goalpost) reads the zeros of its own, never written LDS slot and writes to a scratch slot nobody reads:
+      // no branch around the loads and stores.  (Its velocity is +0 after every finite impulse - x * 0 + 0 - so reloading the zeros
+      // is what keeping it in registers was.)
+      const bool cleanAll = wave_ballot(jointsDirty) == 0ull;
+      bool notFinite = false;
+      const int nLv = uniform_i(maxLevel) + 1;
+      const int sa = aDyn ? bodyA : RC_NB - 1, sb = bDyn ? bodyB : RC_NB - 1;
+      const bool two = a_count > 1;
 #define RC_CONTACT_PASS(q)                                                                     \
-        {                                                                                      \
-          const V2 vr = rrelative_velocity(a, b, r1[q], r2[q]);                                \
-          const double vrn = vdot_f(vr, n);                                                    \
-          const double vrt = vdot_f(vr, vperp(n));                                             \
-          const double jnOld = jn[q];                                                          \
-          jn[q] = dms_acc_clamp0(-(bounce[q] + vrn), nMass[q], jnOld);                         \
-          const double jtMax = arb_u * jn[q];                                                  \
-          const double jtOld = jt[q];                                                          \
-          jt[q] = fclamp_cp(dm_fma(-vrt, tMass[q], jtOld), -jtMax, jtMax);                     \
-          const double dj = jn[q] - jnOld;                                                     \
-          const V2 jr = vrotate_f(n, v2(dj, jt[q] - jtOld));                                   \
-          const V2 jl = vmul(n, dj);                                                           \
-          const V2 jj = biasLane ? jl : jr;                                                    \
-          rapply_impulse(a, vneg(jj), r1[q]);                                                  \
-          rapply_impulse(b, jj, r2[q]);                                                        \
-        }
+      {                                                                                      \
+        const V2 vr = rrelative_velocity(a, b, r1[q], r2[q]);                                \
+        const double vrn = vdot_f(vr, n);                                                    \
+        const double vrt = vdot_f(vr, vperp(n));                                             \
+        const double jnOld = jn[q];                                                          \
+        jn[q] = dms_acc_clamp0(-(bounce[q] + vrn), nMass[q], jnOld);                         \
+        const double jtMax = arb_u * jn[q];                                                  \
+        const double jtOld = jt[q];                                                          \
+        jt[q] = fclamp_cp(dm_fma(-vrt, tMass[q], jtOld), -jtMax, jtMax);                     \
+        const double dj = jn[q] - jnOld;                                                     \
+        const V2 jr = vrotate_f(n, v2(dj, jt[q] - jtOld));                                   \
+        const V2 jl = vmul(n, dj);                                                           \
+        const V2 jj = biasLane ? jl : jr;                                                    \
+        rapply_impulse(a, vneg(jj), r1[q]);                                                  \
+        rapply_impulse(b, jj, r2[q]);                                                        \
+      }
 RC_PROF(unsigned long long nNoop = 0ull, tLv = 0ull, tJt = 0ull;)
-        for (int iter = 0; iter < 10; ++iter) {
+      for (int iter = 0; iter < 10; ++iter) {
 RC_PROF(const double pj0 = jn[0], pj1 = jn[1], pj2 = jt[0], pj3 = jt[1]; const unsigned long long S0 = __builtin_amdgcn_s_memtime();)
-          for (int lv = 0; lv < nLv; ++lv) {
-            if (solveMe && myLevel == lv) {
-              a.v = v2(fX[bodyA], fY[bodyA]); a.w = fW[bodyA];
-              b.v = v2(fX[bodyB], fY[bodyB]); b.w = fW[bodyB];
-              RC_CONTACT_PASS(0)
-              if (two) RC_CONTACT_PASS(1)
-              fX[sa] = a.v.x; fY[sa] = a.v.y; fW[sa] = a.w;
-              fX[sb] = b.v.x; fY[sb] = b.v.y; fW[sb] = b.w;
-            }
-            __syncthreads();
-          }
-RC_PROF(const unsigned long long S1 = __builtin_amdgcn_s_memtime();)
-          if (isRobot) {
-            RC_JOINT_VIEW(J)
-            RcFeet f;
-            f.vx0 = L.vx[la]; f.vy0 = L.vy[la]; f.w0 = L.w[la]; f.vx1 = L.vx[lb]; f.vy1 = L.vy[lb]; f.w1 = L.w[lb];
-            if (cleanAll) {
-              // CLEAN arithmetic (pivot_warm_start's comment): no foot velocity is -0 - checked after the warm start, and an accumulation
-              // v = fma(x, y, v) cannot produce a -0 from a v that is not one, so the arbiters' impulses keep it so - hence the pivot
-              // reads and writes (vx, vy) only, the rotary limit w only: the two are independent and their order is immaterial.
-              pivot_iterate<true>(J, f, jn[0], jn[1]);
-              rotary_iterate(J, f, jt[0]);
-              if (iter == 9) notFinite = !(is_finite(jn[0]) && is_finite(jn[1]) && is_finite(f.vx0) && is_finite(f.vy0) && is_finite(f.vx1) &&
-                                           is_finite(f.vy1) && is_finite(f.w0) && is_finite(f.w1));
-            } else
-            joints_iterate_ordered(J, f, jn[0], jn[1], jt[0]);
-            L.vx[la] = f.vx0; L.vy[la] = f.vy0; L.w[la] = f.w0; L.vx[lb] = f.vx1; L.vy[lb] = f.vy1; L.w[lb] = f.w1;
+        for (int lv = 0; lv < nLv; ++lv) {
+          if (solveMe && myLevel == lv) {
+            a.v = v2(fX[bodyA], fY[bodyA]); a.w = fW[bodyA];
+            b.v = v2(fX[bodyB], fY[bodyB]); b.w = fW[bodyB];
+            RC_CONTACT_PASS(0)
+            if (two) RC_CONTACT_PASS(1)
+            fX[sa] = a.v.x; fY[sa] = a.v.y; fW[sa] = a.w;
+            fX[sb] = b.v.x; fY[sb] = b.v.y; fW[sb] = b.w;
           }
           __syncthreads();
-RC_PROF(tLv += S1 - S0; tJt += __builtin_amdgcn_s_memtime() - S1;)
-RC_PROF(if (G::ballot((solveMe || isRobot) && !(pj0 == jn[0] && pj1 == jn[1] && pj2 == jt[0] && (isRobot || pj3 == jt[1]))) == 0ull) nNoop += 1ull;)
         }
-RC_PROF(if (lane == 0 && c.genv < 4096u) { g_rcprof2[c.genv * 8 + 7] += nNoop; g_rcprof4[c.genv * 8 + 5] += tLv; g_rcprof4[c.genv * 8 + 6] += tJt; g_rcprof4[c.genv * 8 + 7] += (unsigned long long)(10 * nLv) + (10ull << 32); })
-        // Non-finite values persist through accumulations: finite feet velocities and pivot impulses at the end mean they were finite
-        // all along, i.e. every product the CLEAN arithmetic dropped was a zero.  Otherwise (an overflowing state: never seen) this
-        // substep's joints are not the reference's: reported, error bit 5.
-        if (G::ballot(notFinite) != 0ull) err |= 32;
-#undef RC_CONTACT_PASS
-      }
-    } else
-    for (int iter = 0; iter < 10; ++iter) {
-      for (int lv = 0; lv <= maxLevel; ++lv) {
-        if (active && myLevel == lv) {
-          rbody_load_vel(L, bodyA, a);
-          rbody_load_vel(L, bodyB, b);
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            if (q < a_count) {
-              const V2 vb1 = v2(dms_point_vx(a.vb.x, r1[q].y, a.wb), dms_point_vy(a.vb.y, r1[q].x, a.wb));
-              const V2 vb2 = v2(dms_point_vx(b.vb.x, r2[q].y, b.wb), dms_point_vy(b.vb.y, r2[q].x, b.wb));
-              const V2 vr = rrelative_velocity(a, b, r1[q], r2[q]);
-              const double vbn = vdot_f(vsub(vb2, vb1), n);
-              const double vrn = vdot_f(vr, n);
-              const double vrt = vdot_f(vr, vperp(n));
-              const double jbnOld = jBias[q];
-              jBias[q] = dms_acc_clamp0(bias[q] - vbn, nMass[q], jbnOld);
-              const double jnOld = jn[q];
-              jn[q] = dms_acc_clamp0(-(bounce[q] + vrn), nMass[q], jnOld);
-              const double jtMax = arb_u * jn[q];
-              const double jtOld = jt[q];
-              jt[q] = fclamp_cp(dm_fma(-vrt, tMass[q], jtOld), -jtMax, jtMax);
-              const V2 jb = vmul(n, jBias[q] - jbnOld);
-              rapply_bias_impulse(a, vneg(jb), r1[q]);
-              rapply_bias_impulse(b, jb, r2[q]);
-              const V2 jj = vrotate_f(n, v2(jn[q] - jnOld, jt[q] - jtOld));
-              rapply_impulse(a, vneg(jj), r1[q]);
-              rapply_impulse(b, jj, r2[q]);
-            }
-          }
-          rbody_store_vel(L, bodyA, a);
-          rbody_store_vel(L, bodyB, b);
+RC_PROF(const unsigned long long S1 = __builtin_amdgcn_s_memtime();)
+        if (isRobot) {
+          RC_JOINT_VIEW(J)
+          RcFeet f;
+          f.vx0 = L.vx[la]; f.vy0 = L.vy[la]; f.w0 = L.w[la]; f.vx1 = L.vx[lb]; f.vy1 = L.vy[lb]; f.w1 = L.w[lb];
+          if (cleanAll) {
+            // CLEAN arithmetic (pivot_warm_start's comment): no foot velocity is -0 - checked after the warm start, and an accumulation
+            // v = fma(x, y, v) cannot produce a -0 from a v that is not one, so the arbiters' impulses keep it so - hence the pivot
+            // reads and writes (vx, vy) only, the rotary limit w only: the two are independent and their order is immaterial.
+            pivot_iterate<true>(J, f, jn[0], jn[1]);
+            rotary_iterate(J, f, jt[0]);
+            if (iter == 9) notFinite = !(is_finite(jn[0]) && is_finite(jn[1]) && is_finite(f.vx0) && is_finite(f.vy0) && is_finite(f.vx1) &&
+                                         is_finite(f.vy1) && is_finite(f.w0) && is_finite(f.w1));
+          } else
+          joints_iterate_ordered(J, f, jn[0], jn[1], jt[0]);
+          L.vx[la] = f.vx0; L.vy[la] = f.vy0; L.w[la] = f.w0; L.vx[lb] = f.vx1; L.vy[lb] = f.vy1; L.w[lb] = f.w1;
         }
         __syncthreads();
+RC_PROF(tLv += S1 - S0; tJt += __builtin_amdgcn_s_memtime() - S1;)
+RC_PROF(if (wave_ballot((solveMe || isRobot) && !(pj0 == jn[0] && pj1 == jn[1] && pj2 == jt[0] && (isRobot || pj3 == jt[1]))) == 0ull) nNoop += 1ull;)
       }
-      if (isRobot) {
-        RC_JOINT_VIEW(J)
-        RcFeet f;
-        f.vx0 = L.vx[la]; f.vy0 = L.vy[la]; f.w0 = L.w[la]; f.vx1 = L.vx[lb]; f.vy1 = L.vy[lb]; f.w1 = L.w[lb];
-        joints_iterate_ordered(J, f, jn[0], jn[1], jt[0]);
-        L.vx[la] = f.vx0; L.vy[la] = f.vy0; L.w[la] = f.w0; L.vx[lb] = f.vx1; L.vy[lb] = f.vy1; L.w[lb] = f.w1;
-      }
-      __syncthreads();
+RC_PROF(if (lane == 0 && c.genv < 4096u) { g_rcprof2[c.genv * 8 + 7] += nNoop; g_rcprof4[c.genv * 8 + 5] += tLv; g_rcprof4[c.genv * 8 + 6] += tJt; g_rcprof4[c.genv * 8 + 7] += (unsigned long long)(10 * nLv) + (10ull << 32); })
+      // Non-finite values persist through accumulations: finite feet velocities and pivot impulses at the end mean they were finite
+      // all along, i.e. every product the CLEAN arithmetic dropped was a zero.  Otherwise (an overflowing state: never seen) this
+      // substep's joints are not the reference's: reported, error bit 5.
+      if (wave_ballot(notFinite) != 0ull) err |= 32;
+#undef RC_CONTACT_PASS
     }
   }
 RC_PROF(const unsigned long long T5 = __builtin_amdgcn_s_memtime();)
@@ -1663,11 +1574,11 @@ RC_PROF(const unsigned long long T5 = __builtin_amdgcn_s_memtime();)
     double dice0 = 0.0, dice1 = 0.0;
     if (active && c.canFall) rc_post_solve_dice(c, L, a_pair >> 8, a_pair & 0xFF, dice0, dice1);
     for (int k = 0; k < nActive; ++k) {
-      const uint64_t who = G::ballot(active && arank == k);
+      const uint64_t who = wave_ballot(active && arank == k);
       const int b = __builtin_ctzll(who);
-      const int pk = G::bcast_i(a_pair, b);
-      const double d0 = G::bcast_d(dice0, b), d1 = G::bcast_d(dice1, b);
-      if (lane == 0) rc_cb_post_solve<EPW>(c, L, pk >> 8, pk & 0xFF, d0, d1);
+      const int pk = bcast_i(a_pair, b);
+      const double d0 = bcast_d(dice0, b), d1 = bcast_d(dice1, b);
+      if (lane == 0) rc_cb_post_solve(c, L, pk >> 8, pk & 0xFF, d0, d1);
       __syncthreads();
     }
     if (active && a_state == ARB_FIRST_) a_state = ARB_NORMAL_;
@@ -1676,7 +1587,7 @@ RC_PROF(const unsigned long long T5 = __builtin_amdgcn_s_memtime();)
       L.s_meta[lane] = a_state | (a_count << 8) | (a_age << 16);
       if (touched) { L.s_jn0[lane] = jn[0]; L.s_jt0[lane] = jt[0]; L.s_jn1[lane] = jn[1]; L.s_jt1[lane] = jt[1]; }
     }
-    occ &= ~G::ballot(freeMe);
+    occ &= ~wave_ballot(freeMe);
   }
   __syncthreads();
 RC_PROF(if (lane == 0 && c.genv < 4096u) { unsigned long long* d = g_rcprof + c.genv * 12;  /* (profile runs: env_id_offset 0) */ const unsigned long long T6 = __builtin_amdgcn_s_memtime(); d[3] += T1 - T0; d[4] += T2 - T1; d[5] += T3 - T2; d[6] += T4 - T3; d[7] += T5 - T4; d[8] += T6 - T5; d[9] += (unsigned long long)nTouched; d[10] += (unsigned long long)(maxLevel + 1);
@@ -1688,17 +1599,13 @@ RC_PROF(if (lane == 0 && c.genv < 4096u) { unsigned long long* d = g_rcprof + c.
 
 DE_OOL RcStepRet rc_physics_ool(RcCtx c_, int lane, int cand, uint64_t pairLo, uint64_t pairHi, uint64_t occ) {
   const RcCtx c = rc_ctx_uniform(c_);
-  return rc_physics_inl<1>(c, lane, cand, pairLo, pairHi, 0ull, occ);
-}
-template <int EPW>
-DE_DEV RcStepRet rc_physics(RcCtx c, int lane, int cand, uint64_t pairLo, uint64_t pairHi, uint64_t pairTop, uint64_t occ) {
-  return rc_physics_ool(c, lane, cand, pairLo, pairHi, occ);
+  return rc_physics_inl(c, lane, cand, pairLo, pairHi, occ);
 }
 
 // ------------------------------------------------------------------------------------------------
 // HBM <-> LDS
 // ------------------------------------------------------------------------------------------------
-DE_DEV void rc_load_env(const RcState& S, RcLds& L, int e, int lane, uint64_t occ, int W = 64) {  // W: lanes serving this environment
+DE_DEV void rc_load_env(const RcState& S, RcLds& L, int e, int lane, uint64_t occ) {
   const size_t E = (size_t)S.E;
   if (lane < RC_NB) {
     const bool used = lane == RC_BALL || lane < 2 * S.R;
@@ -1735,7 +1642,7 @@ DE_DEV void rc_load_env(const RcState& S, RcLds& L, int e, int lane, uint64_t oc
     L.fallc[lane] = used ? ri[RI_FALLC * E * 16] : 0;
     L.rrew[lane] = 0.0; L.rposrew[lane] = 0.0;
   }
-  for (int k = lane; k < RE_COUNT; k += W) L.envi[k] = S.envi[(size_t)e * RE_COUNT + k];
+  for (int k = lane; k < RE_COUNT; k += DE_WAVE) L.envi[k] = S.envi[(size_t)e * RE_COUNT + k];
   if (lane < RD_COUNT) L.envd[lane] = S.envd[(size_t)e * RD_COUNT + lane];
   if (lane < 2) L.teamRew[lane] = 0.0;
   if (lane < RC_NS) {
@@ -1749,7 +1656,7 @@ DE_DEV void rc_load_env(const RcState& S, RcLds& L, int e, int lane, uint64_t oc
   }
 }
 
-DE_DEV void rc_store_env(const RcState& S, const RcLds& L, int e, int lane, uint64_t occ, int W = 64) {
+DE_DEV void rc_store_env(const RcState& S, const RcLds& L, int e, int lane, uint64_t occ) {
   const size_t E = (size_t)S.E;
   if (lane == RC_BALL || lane < 2 * S.R) {
     double* b = S.body + (size_t)e * RC_NB + lane;
@@ -1770,7 +1677,7 @@ DE_DEV void rc_store_env(const RcState& S, const RcLds& L, int e, int lane, uint
     int* ri = S.robi + (size_t)e * 16 + lane;
     ri[RI_FLAGS * E * 16] = L.rflags[lane]; ri[RI_TOUCHC * E * 16] = L.touchc[lane]; ri[RI_FALLC * E * 16] = L.fallc[lane];
   }
-  for (int k = lane; k < RE_COUNT; k += W) S.envi[(size_t)e * RE_COUNT + k] = L.envi[k];
+  for (int k = lane; k < RE_COUNT; k += DE_WAVE) S.envi[(size_t)e * RE_COUNT + k] = L.envi[k];
   if (lane < RD_COUNT) S.envd[(size_t)e * RD_COUNT + lane] = L.envd[lane];
   if (lane < RC_NS && ((occ >> lane) & 1ull)) {
     size_t o = (size_t)e * RC_NS + lane;
@@ -1860,25 +1767,22 @@ struct RcCommonRet {
   uint64_t pairLo, pairHi;  // this lane's pair codes, for rc_physics (S.pairTab)
   int cand, bits;           // bits: 1 quiet
 };
-template <int EPW>
 DE_OOL RcCommonRet rc_common_substep(RcCtx c_, int serial_, int lane, const uint64_t* __restrict__ pairTab, uint64_t occ_) {
   const RcCtx c = rc_ctx_uniform(c_);
-  typedef Grp<EPW> G;
-  constexpr int W = G::W, NROUNDS = (RC_NPAIR_ROUNDS * 64) / W;
-  RcLds& L = G::tile();
-  const bool serial = G::uniform_i(serial_) != 0;  // the sequential game logic has run already: no tick here
+  RcLds& L = g_R;
+  const bool serial = uniform_i(serial_) != 0;  // the sequential game logic has run already: no tick here
   const int R = c.R;
-  const uint64_t occ = G::uniform_u64(occ_);
+  const uint64_t occ = uniform_u64(occ_);
   const bool isBody = lane == RC_BALL || lane < 2 * R;
   // my pairs: loaded here, first used by the broadphase - the latency is hidden behind the game logic and the position update.
   // They are NOT kept in registers across substeps: whatever the kernel holds across the call of rc_physics (128 VGPRs) is
   // spilled around it, 4 bytes x 64 lanes a register and call - that was most of this kernel's HBM writes.
   const uint64_t pairLo = pairTab[2 * lane], pairHiFeet = pairTab[2 * lane + 1];
-  const uint64_t pairHi = pairHiFeet & 0xFFFFull, pairTop = 0ull;
+  const uint64_t pairHi = pairHiFeet & 0xFFFFull;
   const int feetPairs = (int)(pairHiFeet >> 32);  // bit t: my pair of round t is the two feet of one robot
 RC_PROF(const unsigned long long P0 = __builtin_amdgcn_s_memtime();)
     // ---- game logic: tick per robot (one robot per lane, unless the sequential form has run), then the ball (:465-475) ----
-    if (!rc_game_logic_batched<EPW>(c, L, lane, !serial)) {
+    if (!rc_game_logic_batched(c, L, lane, !serial)) {
       RcCommonRet ret;  // a robot's tick has a cross-robot event: nothing has been changed, the kernel runs the sequential form
       ret.pairLo = 0ull; ret.pairHi = 0ull; ret.cand = 0; ret.bits = 4;
       return ret;
@@ -1926,7 +1830,7 @@ RC_PROF(const unsigned long long P2 = __builtin_amdgcn_s_memtime();)
     // keeps the double-precision box test below for the rare real prefilter hits.
     int cand = feetPairs, pre = 0;
 #pragma unroll
-    for (int t = 0; t < NROUNDS; ++t) {  // the fp32 prefilter of all my pairs first: their LDS reads are in flight together
+    for (int t = 0; t < RC_NPAIR_ROUNDS; ++t) {  // the fp32 prefilter of all my pairs first: their LDS reads are in flight together
       const int pr = RC_MY_PAIR(t);
       if (pr != 0xFFFF && !((feetPairs >> t) & 1)) {
         const int i = pr >> 8, j = pr & 0xFF;
@@ -1952,17 +1856,17 @@ RC_PROF(const unsigned long long P2 = __builtin_amdgcn_s_memtime();)
     // the narrowphase's separating-axis early out rejects every one of them.  What rc_physics does then is exactly this:
     // velocity update, then every robot's joints (prestep, warm start, 10 iterations) in registers.
 RC_PROF(const unsigned long long P3 = __builtin_amdgcn_s_memtime(); unsigned long long P4 = P3, P5 = P3, P6 = P3;)
-    bool quiet = occ == 0ull && G::ballot((cand & ~feetPairs) != 0) == 0ull;
+    bool quiet = occ == 0ull && wave_ballot((cand & ~feetPairs) != 0) == 0ull;
     if (quiet) {
       const bool far = lane < R ? feet_far_apart(L, lane) : true;
-      quiet = G::ballot(!far) == 0ull;
+      quiet = wave_ballot(!far) == 0ull;
     }
 RC_PROF(P4 = P5 = P6 = __builtin_amdgcn_s_memtime();)
     if (quiet) {
       if (isBody) rc_velocity_update(L, lane);
       __syncthreads();
 RC_PROF(P5 = __builtin_amdgcn_s_memtime();)
-      rc_joints_only_inl<EPW>(lane, R);
+      rc_joints_only_inl(lane, R);
       __syncthreads();
 RC_PROF(P6 = __builtin_amdgcn_s_memtime();)
     }
@@ -1974,22 +1878,19 @@ RC_PROF(if (lane == 0 && c.genv < 4096u) { unsigned long long* d = g_rcprof3 + c
 // mask (device uint8 [E], dynenv_step_masked; nullptr: every environment): the wave of an environment whose byte is 0 ends at once - it
 // reads no action and writes no byte of the environment's state, of its output rows or of deferList's entries.  The one thing a block
 // does for the LAUNCH, environment 0's rotation of the forecast words, does not depend on the mask.
-template <bool PARTIAL, int EPW>
+template <bool PARTIAL>
 DE_DEV void rc_step_body(const RcState& S, const uint8_t* __restrict__ mask, const int e, const int* __restrict__ actions,
                          const double* __restrict__ headActions, float* __restrict__ obs, double* __restrict__ rewards, uint8_t* __restrict__ dones) {
-  typedef Grp<EPW> G;
-  constexpr int W = G::W, NROUNDS = (RC_NPAIR_ROUNDS * 64) / W;
   static_assert(RC_NS <= 16, "sLevel packs level and rank into four bits each");
-  static_assert(!PARTIAL || EPW == 1, "the fused Partial observation works on one environment per wave");
-  int lane = G::lane();
+  int lane = (int)threadIdx.x;
   const int R = S.R;
-  if (e < 0 || e >= S.E) return;  // (two environments per wave: a half without an environment; its lanes are off from here on)
-  if (mask && G::uniform_i(mask[e]) == 0) {
+  if (e < 0 || e >= S.E) return;  // (a block beyond the batch has no environment: its wave ends here)
+  if (mask && uniform_i(mask[e]) == 0) {
     if (PARTIAL && e == 0 && lane == 0) { int* sc = S.deferList + S.E + 1; sc[0] = sc[1]; sc[1] = 0; }  // (as below)
     return;
   }
-  RcLds& L = G::tile();
-  uint64_t occ = (uint64_t)(uint32_t)G::uniform_i(S.envi[(size_t)e * RE_COUNT + RE_OCC]);
+  RcLds& L = g_R;
+  uint64_t occ = (uint64_t)(uint32_t)uniform_i(S.envi[(size_t)e * RE_COUNT + RE_OCC]);
   // Environments with live contacts are the long ones and the launch ends with the slowest: their waves get issue priority
   // over the lighter waves they share a SIMD with, from the first instruction on.
   if (occ != 0ull) __builtin_amdgcn_s_setprio(3);
@@ -1999,7 +1900,7 @@ DE_DEV void rc_step_body(const RcState& S, const uint8_t* __restrict__ mask, con
   // the forecast for this step = the slowest environment of the previous one (0: none was slow); block 0 is among the first to start,
   // everybody else reads the word when its physics is done - a million cycles later
   if (PARTIAL && e == 0 && lane == 0) { int* sc = S.deferList + S.E + 1; sc[0] = sc[1]; sc[1] = 0; }
-  rc_load_env(S, L, e, lane, occ, W);
+  rc_load_env(S, L, e, lane, occ);
   L.lastCand[lane & 63] = 0xFF;  // rc_physics' call-to-call caches start empty
   if (lane == 0) { L.candN = -1; L.sActive = ~0ull; L.sMaxLevel = -1; }
   RcCtx c;
@@ -2007,7 +1908,7 @@ DE_DEV void rc_step_body(const RcState& S, const uint8_t* __restrict__ mask, con
   c.canFall = (S.flags & DYNENV_FLAG_CAN_FALL) != 0; c.allowHead = (S.flags & DYNENV_FLAG_ALLOW_HEAD_TURN) != 0;
   c.detTurn = (S.flags & DYNENV_FLAG_DETERMINISTIC_TURN) != 0;
   __syncthreads();
-  c.episode = (uint32_t)G::uniform_i(L.envi[RE_EPISODE]);  // (an LDS read is a vector value until told otherwise: it would be spilled around every call)
+  c.episode = (uint32_t)uniform_i(L.envi[RE_EPISODE]);  // (an LDS read is a vector value until told otherwise: it would be spilled around every call)
   if (lane == 0) refresh_pivot_first(L);
   __syncthreads();
   const bool partial = PARTIAL;
@@ -2027,29 +1928,29 @@ RC_PROF(const unsigned long long A0 = __builtin_amdgcn_s_memtime();)
     //  event - it then returns without having changed anything and is called again after the sequential form)
     bool serial = it == 0;
     if (serial) {
-      if (lane == 0) rc_game_serial<EPW>(c, it, myActions, myHead);
+      if (lane == 0) rc_game_serial(c, it, myActions, myHead);
 RC_PROF(tG += 1;)  // (profile build: "game logic" = substeps with the sequential form, "position" = cycles of the whole common part)
     }
-    RcCommonRet cr = rc_common_substep<EPW>(c, serial ? 1 : 0, lane, S.pairTab, occ);
-    if (G::uniform_i(cr.bits & 4) != 0) {
+    RcCommonRet cr = rc_common_substep(c, serial ? 1 : 0, lane, S.pairTab, occ);
+    if (uniform_i(cr.bits & 4) != 0) {
       lane = fresh_lane();
-      if (lane == 0) rc_game_serial<EPW>(c, it, myActions, myHead);
+      if (lane == 0) rc_game_serial(c, it, myActions, myHead);
 RC_PROF(tG += 1;)
       lane = fresh_lane();
-      cr = rc_common_substep<EPW>(c, 1, lane, S.pairTab, occ);
+      cr = rc_common_substep(c, 1, lane, S.pairTab, occ);
     }
     const int cand = cr.cand;
-    const bool quiet = G::uniform_i(cr.bits & 1) != 0;
+    const bool quiet = uniform_i(cr.bits & 1) != 0;
 RC_PROF(tP += __builtin_amdgcn_s_memtime() - A0;)
     if (quiet) {
     } else {
       __builtin_amdgcn_s_setprio(3);  // an environment with contact work is on the launch's critical path: issue it first
       ++nGeneral;
-      const RcStepRet sr = rc_physics<EPW>(c, fresh_lane(), cand, cr.pairLo, cr.pairHi, 0ull, occ);
-      occ = G::uniform_u64(sr.occ);
+      const RcStepRet sr = rc_physics_ool(c, fresh_lane(), cand, cr.pairLo, cr.pairHi, occ);
+      occ = uniform_u64(sr.occ);
       lane = fresh_lane();
       {  // a full slot table / candidate list (bit 0), a capsule pair on the fallback normal (bit 4): reported, never silent
-        const int eb = (G::ballot((sr.err & 1) != 0) != 0ull ? 1 : 0) | (G::ballot((sr.err & 16) != 0) != 0ull ? 16 : 0) | (G::ballot((sr.err & 32) != 0) != 0ull ? 32 : 0);
+        const int eb = (wave_ballot((sr.err & 1) != 0) != 0ull ? 1 : 0) | (wave_ballot((sr.err & 16) != 0) != 0ull ? 16 : 0) | (wave_ballot((sr.err & 32) != 0) != 0ull ? 32 : 0);
         if (eb != 0 && lane == 0) L.envi[RE_ERR] |= eb;
       }
     }
@@ -2098,7 +1999,7 @@ RC_PROF(if (lane == 0 && e < 4096) { unsigned long long* d = g_rcprof + e * 12; 
   int budget = 0, ownPasses = 5 * R;
   if (PARTIAL && obs) {
     int* sc = S.deferList + S.E + 1;
-    const int slowest = G::uniform_i(__atomic_load_n(sc, __ATOMIC_RELAXED));
+    const int slowest = uniform_i(__atomic_load_n(sc, __ATOMIC_RELAXED));
     const int cycles = (int)(__builtin_amdgcn_s_memtime() - schedT0);
     if (slowest > 0) { budget = (slowest / 100) * RC_PV_DEADLINE_PCT - cycles; if (budget <= 0) ownPasses = 0; }
     else if (nGeneral >= RC_DEFER_MIN_GENERAL) ownPasses = 0;
@@ -2110,7 +2011,7 @@ RC_PROF(if (lane == 0 && e < 4096) { unsigned long long* d = g_rcprof + e * 12; 
     L.envi[RE_OCC] = (int)(uint32_t)occ;
   }
   __syncthreads();
-  rc_store_env(S, L, e, lane, occ, W);
+  rc_store_env(S, L, e, lane, occ);
   if constexpr (PARTIAL) {
     if (obs) {
       if (ownPasses > 0) {  // getAgentVision at the five snapshots (+ processSeens if it gets through all of them)
@@ -2118,7 +2019,7 @@ RC_PROF(if (lane == 0 && e < 4096) { unsigned long long* d = g_rcprof + e * 12; 
         ownPasses = rc_partial_obs_fused(S.seed, S.env_id_offset, S.envi, S.n, S.R, S.noise_type, S.noise_magn, S.snap, S.flags, S.prew0, S.epr, S.E, S.epo, e, obs,
                                          rewards, S.seenPart, budget);
       }
-      if (ownPasses < 5 * R && G::lane() == 0) S.deferList[1 + atomicAdd(&S.deferList[0], 1)] = e | (ownPasses << 20);
+      if (ownPasses < 5 * R && (int)threadIdx.x == 0) S.deferList[1 + atomicAdd(&S.deferList[0], 1)] = e | (ownPasses << 20);
     }
   }
 }
@@ -2126,12 +2027,12 @@ RC_PROF(if (lane == 0 && e < 4096) { unsigned long long* d = g_rcprof + e * 12; 
 extern "C" __global__ void __launch_bounds__(64, RC_WAVES_PER_SIMD)
 rc_step_kernel(RcState S, const uint8_t* __restrict__ mask, const int* __restrict__ actions, const double* __restrict__ headActions,
                float* __restrict__ obs, double* __restrict__ rewards, uint8_t* __restrict__ dones) {
-  rc_step_body<false, 1>(S, mask, (int)blockIdx.x, actions, headActions, obs, rewards, dones);
+  rc_step_body<false>(S, mask, (int)blockIdx.x, actions, headActions, obs, rewards, dones);
 }
 extern "C" __global__ void __launch_bounds__(64, RC_WAVES_PER_SIMD)
 rc_step_partial_kernel(RcState S, const uint8_t* __restrict__ mask, const int* __restrict__ actions, const double* __restrict__ headActions,
                        float* __restrict__ obs, double* __restrict__ rewards, uint8_t* __restrict__ dones) {
-  rc_step_body<true, 1>(S, mask, (int)blockIdx.x, actions, headActions, obs, rewards, dones);
+  rc_step_body<true>(S, mask, (int)blockIdx.x, actions, headActions, obs, rewards, dones);
 }
 
 // getFullState(agent=None) (RoboCupEnvironment.py:1149-1161), what step() stores as info['Full State'] (:511): per environment
