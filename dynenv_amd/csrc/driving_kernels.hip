@@ -57,7 +57,7 @@ struct __align__(16) DrvLds {
   // Per-lane values the step carries from substep to substep live HERE, not in the kernel's registers: whatever the kernel holds in
   // VGPRs across the call of the solver (124 VGPRs) is spilled around it, 256 B of scratch per register and call.
   int lastCand[64];        // candidate mask of the previous substep (-1: unknown), persisted in S.lastcand
-  int stepErr;             // error bits of this step (1: candidate list / contact cache overflow, 2: malformed action)
+  int stepErr;             // error bits of this step (DYNENV_ERRBIT_OVERFLOW, DYNENV_ERRBIT_ACTION)
   unsigned char act[16];   // cars: acc | steer << 2 (each 0..2), consumed by the first substep
   int still[DRV_NB];  // bit0: body had exactly zero v, w, v_bias, w_bias when positions were integrated; bit1: frozen
   unsigned short clist[DRV_CLIST];  // contact path: dense list of candidate pair ids in canonical order
@@ -78,20 +78,6 @@ struct __align__(16) DrvLds {
 static_assert(sizeof(DrvLds) <= 10240, "16 one-wave workgroups per CU - one residency round of 4096 environments on 256 CUs - need <= 160 KB / 16 of LDS each");
 __shared__ DrvLds g_L;
 
-
-// flag-word accessors (layout in driving_dev.h)
-#define CF_FIN(f) (((f) >> 4) & 1)
-#define CF_CRASHED(f) (((f) >> 5) & 1)
-#define CF_FRIC(f) (((f) >> 6) & 1)
-#define CF_LP(f) (((f) >> 8) & 7)
-#define CF_SET_LP(f, lp) (((f) & ~(7 << 8)) | ((lp) << 8))
-#define CF_CRASH_BITS ((1 << 4) | (1 << 5) | (1 << 6)) /* Car.crash(): finished, crashed, friction_car_crashed */
-#define PF_ROAD(f) ((f)&1)
-#define PF_SIDE(f) (((f) >> 1) & 1)
-#define PF_DEAD(f) (((f) >> 2) & 1)
-#define PF_CROSSING(f) (((f) >> 3) & 1)
-#define PF_BEGIN(f) (((f) >> 4) & 1)
-#define PF_SPEED(f) (((f) >> 8) & 15)
 
 // ------------------------------------------------------------------------------------------------
 // game logic (mirrors oracle/driving.c, which cites the reference lines)
@@ -121,7 +107,7 @@ struct CarK {
   static constexpr double carHy0 = 5.0, carHy1 = 6.0, carHy2 = 7.0, carHy3 = 8.0;
   static constexpr double carPower0 = 3.0, carPower1 = 4.0, carPower2 = 3.0, carPower3 = 4.0;
   static constexpr double carInertia0 = 50000.0, carInertia1 = 156600.0, carInertia2 = 0x1.ff8e555555555p+18, carInertia3 = 0x1.185ad55555555p+20;
-  static constexpr double pedMass = 90.0, pedInertia = 90.0 * (0.5 * (0.0 * 0.0 + 5.0 * 5.0) + 0.0);
+  static constexpr double pedMass = 90.0, pedInertia = 90.0 * (0.5 * (0.0 * 0.0 + DRV_PED_R * DRV_PED_R) + 0.0);
 };
 
 // Road.isPointOnRoad (Road.py:74-97) with cos(road.dirAngle - angle) supplied by the caller (cached)
@@ -178,8 +164,8 @@ DE_DEV void velocity_update(DrvLds& L, int lane, bool isCar, bool isPed) {
   const int f = L.flags[lane];
   double m, fr, rfr;
   bool dflt = false;
-  if (isCar) { m = L.cmass[lane]; fr = CF_FRIC(f) ? 5e-4 : 5e-5; rfr = CF_FRIC(f) ? 2e-5 : 1e-5; }
-  else { m = 90.0; fr = 5e-2; rfr = 2e-4; dflt = !PF_DEAD(f); }
+  if (isCar) { m = L.cmass[lane]; fr = CARF_FRIC(f) ? 5e-4 : 5e-5; rfr = CARF_FRIC(f) ? 2e-5 : 1e-5; }
+  else { m = CarK::pedMass; fr = 5e-2; rfr = 2e-4; dflt = !PEDF_DEAD(f); }
   if (dflt) { vx = vx * 1.0 + (0.0 + 0.0) * DE_DT; vy = vy * 1.0 + (0.0 + 0.0) * DE_DT; w = w * 1.0 + 0.0; }
   else apply_friction(vx, vy, w, m, fr, rfr, 0.0);
   L.vx[lane] = vx; L.vy[lane] = vy; L.w[lane] = w;
@@ -233,15 +219,6 @@ struct EdgeW {
   V2 ap, bp, n;
   int ah, bh;
 };
-
-// select element `i` of a 4-vector without dynamic register indexing (no scratch)
-DE_DEV V2 sel4(const V2* a, int i) {
-  V2 r = a[0];
-  r = (i == 1) ? a[1] : r;
-  r = (i == 2) ? a[2] : r;
-  r = (i == 3) ? a[3] : r;
-  return r;
-}
 
 // A box by its parameters.  The narrowphase derives vertices and normals from these on demand (same arithmetic as
 // box_world) instead of holding two expanded boxes (64 doubles) in registers, which spilled to scratch.
@@ -403,8 +380,8 @@ struct BodyV {
 };
 DE_DEV V2 static_pos(const DrvLds& L, int idx) {
   if (idx >= DRV_SLOT_BLD) {
-    int k = idx - DRV_SLOT_BLD; /* DrivingEnvironment.py:101-106 */
-    return v2((k & 2) ? 1385.0 : 365.0, (k & 1) ? 800.0 : 200.0);
+    int k = idx - DRV_SLOT_BLD;
+    return v2(DRV_BLD_CX(k), DRV_BLD_CY(k));
   }
   return v2(L.ox[idx - DRV_SLOT_OBST], L.oy[idx - DRV_SLOT_OBST]);
 }
@@ -415,17 +392,12 @@ DE_DEV void body_load(const DrvLds& L, int idx, BodyV& b) {
   const int bi = dyn ? idx : DRV_SLOT_OBST /* = the zero slot */, oi = (idx >= DRV_SLOT_OBST && idx < DRV_SLOT_BLD) ? idx - DRV_SLOT_OBST : 0;
   const double dpx = L.px[bi], dpy = L.py[bi], sox = L.ox[oi], soy = L.oy[oi];
   const int k = idx - DRV_SLOT_BLD;
-  const double bx = (k & 2) ? 1385.0 : 365.0, by = (k & 1) ? 800.0 : 200.0;  // DrivingEnvironment.py:101-106
+  const double bx = DRV_BLD_CX(k), by = DRV_BLD_CY(k);
   b.p = dyn ? v2(dpx, dpy) : (idx >= DRV_SLOT_BLD ? v2(bx, by) : v2(sox, soy));
   b.v = v2(L.vx[bi], L.vy[bi]); b.w = L.w[bi];
   b.vb = v2(L.vbx[bi], L.vby[bi]); b.wb = L.wb[bi]; b.minv = L.minv[bi]; b.iinv = L.iinv[bi];
 }
-// the solver's per-iteration view of a body: p, minv and iinv do not change while a substep is being solved
-DE_DEV void body_load_vel(const DrvLds& L, int idx, BodyV& b) {
-  if (idx < DRV_SLOT_OBST) {
-    b.v = v2(L.vx[idx], L.vy[idx]); b.w = L.w[idx]; b.vb = v2(L.vbx[idx], L.vby[idx]); b.wb = L.wb[idx];
-  }
-}
+// the solver's view of a body: p, minv and iinv do not change while a substep is being solved, the velocities go back to the tile
 DE_DEV void body_store_vel(DrvLds& L, int idx, const BodyV& b) {  // (a static body's all-zero velocities go to slot 31, which nobody reads)
   const int wi = idx < DRV_SLOT_OBST ? idx : DRV_NB - 1;
   L.vx[wi] = b.v.x; L.vy[wi] = b.v.y; L.w[wi] = b.w; L.vbx[wi] = b.vb.x; L.vby[wi] = b.vb.y; L.wb[wi] = b.wb;
@@ -457,12 +429,6 @@ DE_DEV double bias_rel_n(const BodyV& a, const BodyV& b, V2 r1, V2 r2, V2 n) {
 // observation writer: Full obs of DrivingEnvironment.getFullState/get_full_obs (:686-747, :121-124)
 // dense padded row per agent: [self 9 | other cars (A-1)x7 | obstacles 20x4 | pedestrians 20x2 | lanes 8x5]
 // ------------------------------------------------------------------------------------------------
-#define STD_NORM_X (0.5 / (DRV_W + 100.0))
-#define STD_NORM_Y (0.5 / (DRV_H + 100.0))
-#define STD_NORM_W (1.0 / 15.0)
-#define STD_NORM_H (1.0 / 25.0)
-DE_DEV double normalize_obs(double pt, double nf, double mean) { return ((pt * nf) - mean) * 2.0 * 1.0; }  // cutils.py:318-323
-
 DE_DEV float obs_self_or_car(const DrvObsStage& O, int A, int a, int ff) {
   if (ff < 6) return O.carRow[a][ff];
   if (ff < 8) return O.goal[a][ff - 6];
@@ -487,7 +453,7 @@ DE_OOL void write_full_obs_ool(int lane, int A, int nPed, int nObst, int obs_dim
     O.carRow[lane][3] = (float)L.rs[lane];
     O.carRow[lane][4] = (float)normalize_obs(L.chy[lane], STD_NORM_W, 0.5);  // c.width
     O.carRow[lane][5] = (float)normalize_obs(L.chx[lane], STD_NORM_H, 0.5);  // c.height
-    O.carRow[lane][6] = (float)CF_FIN(f);
+    O.carRow[lane][6] = (float)CARF_FIN(f);
     O.goal[lane][0] = (float)normalize_obs(L.goalx[lane], STD_NORM_X, 0.0);
     O.goal[lane][1] = (float)normalize_obs(L.goaly[lane], STD_NORM_Y, 0.0);
   }
@@ -501,8 +467,8 @@ DE_OOL void write_full_obs_ool(int lane, int A, int nPed, int nObst, int obs_dim
     bool on = lane < nObst;
     O.shared[4 * lane + 0] = on ? (float)normalize_obs(L.ox[lane], STD_NORM_X, 0.0) : 0.0f;
     O.shared[4 * lane + 1] = on ? (float)normalize_obs(L.oy[lane], STD_NORM_Y, 0.0) : 0.0f;
-    O.shared[4 * lane + 2] = on ? (float)normalize_obs(10.0, STD_NORM_W, 0.5) : 0.0f;
-    O.shared[4 * lane + 3] = on ? (float)normalize_obs(10.0, STD_NORM_H, 0.5) : 0.0f;
+    O.shared[4 * lane + 2] = on ? (float)normalize_obs(DRV_OBST_H, STD_NORM_W, 0.5) : 0.0f;
+    O.shared[4 * lane + 3] = on ? (float)normalize_obs(DRV_OBST_H, STD_NORM_H, 0.5) : 0.0f;
   }
   if (lane < DRV_LANE_ROWS * 5) O.shared[DRV_MAXO * 4 + DRV_MAXP * 2 + lane] = C.laneRows[lane];
   __syncthreads();
@@ -573,7 +539,7 @@ DE_DEV void load_env(const DrvState& S, DrvLds& L, int e, int lane, int A, int n
     const int f = used ? g_f : 0;
     L.flags[lane] = f;
     L.moving[lane] = used ? g_aux : 0;
-    const int ty = f & 3;
+    const int ty = CARF_TYPE(f);
     // the four car types' constants (Car.py:9-12 and cpMomentForPoly of the box) as literals selected by the type bits: no
     // memory access that depends on the flag word just loaded (dynenv_create checks them against the computed table, CarK)
 #define DRV_BY_TYPE(ARR) (ty == 3 ? CarK::ARR##3 : (ty == 2 ? CarK::ARR##2 : (ty == 1 ? CarK::ARR##1 : CarK::ARR##0)))
@@ -643,7 +609,7 @@ DE_DEV bool cb_begin(DrvLds& L, int i, int j, int lane) {
   if (j < DRV_SLOT_PED) {  // carCrash :591-637
     const double v2x = L.vx[j], v2y = L.vy[j];
     const int f2 = L.flags[j];
-    const int crashed1 = CF_CRASHED(f1), crashed2 = CF_CRASHED(f2), pos1 = CF_LP(f1), pos2 = CF_LP(f2);
+    const int crashed1 = CARF_CRASHED(f1), crashed2 = CARF_CRASHED(f2), pos1 = CARF_LP(f1), pos2 = CARF_LP(f2);
     const double v1len = vlen(v2(v1x, v1y)), v2len = vlen(v2(v2x, v2y));
     const double v1l = v1len / 5.0, v2l = v2len / 5.0;
     double r1 = L.rewAcc[i], r2 = L.rewAcc[j];
@@ -657,26 +623,26 @@ DE_DEV bool cb_begin(DrvLds& L, int i, int j, int lane) {
       if (v1len > 1.0 && dev_cos(adp - dev_atan2(v1y, v1x)) < -0.4 && !crashed1) r1 -= v1l;
       if (v2len > 1.0 && dev_cos(adp - dev_atan2(v2y, v2x)) > 0.4 && !crashed2) r2 -= v2l;
     }
-    if (lane == i) { L.rewAcc[i] = r1; L.flags[i] = f1 | CF_CRASH_BITS; }
-    if (lane == j) { L.rewAcc[j] = r2; L.flags[j] = f2 | CF_CRASH_BITS; }
+    if (lane == i) { L.rewAcc[i] = r1; L.flags[i] = f1 | CARF_CRASH_BITS; }
+    if (lane == j) { L.rewAcc[j] = r2; L.flags[j] = f2 | CARF_CRASH_BITS; }
     return true;
   } else if (j < DRV_SLOT_OBST) {  // pedHit :640-667
     const double v1l = vlen(v2(v1x, v1y));
     if (v1l > 1.0) {
       V2 dp = v2(L.px[i] - L.px[j], L.py[i] - L.py[j]);
       if (lane == j) {  // Pedestrian.die (Pedestrian.py:40-47)
-        L.moving[j] = 0; L.vx[j] = 0.0; L.vy[j] = 0.0; L.flags[j] = L.flags[j] | (1 << 2);
+        L.moving[j] = 0; L.vx[j] = 0.0; L.vy[j] = 0.0; L.flags[j] = L.flags[j] | PEDF_DEAD_BIT;
       }
-      if (dev_cos(dev_atan2(dp.y, dp.x) - dev_atan2(v1y, v1x)) < -0.4 && !CF_FIN(f1)) {
-        if (lane == i) { L.flags[i] = f1 | CF_CRASH_BITS; L.rewAcc[i] = L.rewAcc[i] - v1l / 5.0; }
+      if (dev_cos(dev_atan2(dp.y, dp.x) - dev_atan2(v1y, v1x)) < -0.4 && !CARF_FIN(f1)) {
+        if (lane == i) { L.flags[i] = f1 | CARF_CRASH_BITS; L.rewAcc[i] = L.rewAcc[i] - v1l / 5.0; }
       }
       return true;
     }
     return false;
   } else {  // carHit :670-683
     if (lane == i) {
-      if (!CF_FIN(f1)) L.rewAcc[i] = L.rewAcc[i] - vlen(v2(v1x, v1y)) / 5.0;
-      L.flags[i] = f1 | CF_CRASH_BITS;
+      if (!CARF_FIN(f1)) L.rewAcc[i] = L.rewAcc[i] - vlen(v2(v1x, v1y)) / 5.0;
+      L.flags[i] = f1 | CARF_CRASH_BITS;
     }
     return true;
   }
@@ -702,9 +668,8 @@ DE_DEV void arb_warm_start(BodyV& a, BodyV& b, V2 n, const V2* r1, const V2* r2,
   }
 }
 // one cpArbiterApplyImpulse pass over the contacts of one arbiter
-DE_DEV void arb_apply_impulse(BodyV& a, BodyV& b, V2 n, const V2* r1, const V2* r2, const double* nMass,
-                              const double* tMass, const double* bias, const double* bounce, double* jBias, double* jn,
-                              double* jt, int count, double arb_u) {
+DE_DEV void arb_apply_impulse(BodyV& a, BodyV& b, V2 n, const V2* r1, const V2* r2, const double* nMass, const double* bias,
+                              const double* bounce, double* jBias, double* jn, double* jt, int count) {
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     if (c == 0 || count > 1) {
@@ -773,12 +738,6 @@ DE_DEV bool arb_is_bias_only(const BodyV& a, const BodyV& b, const double* jn, c
     if (c == 0 || count > 1) { z |= __double_as_longlong(jn[c]) | __double_as_longlong(jt[c]); ok = ok && bounce[c] == 0.0; }
   return ok && z == 0ll;
 }
-DE_DEV void body_load_bias(const DrvLds& L, int idx, BodyV& b) {
-  if (idx < DRV_SLOT_OBST) { b.vb = v2(L.vbx[idx], L.vby[idx]); b.wb = L.wb[idx]; }
-}
-DE_DEV void body_store_bias(DrvLds& L, int idx, const BodyV& b) {
-  if (idx < DRV_SLOT_OBST) { L.vbx[idx] = b.vb.x; L.vby[idx] = b.vb.y; L.wb[idx] = b.wb; }
-}
 // Branch-free access for the sweeps (round 6, as in the RoboCup solver): a static partner reads the zeros of body slot 30 - unused,
 // cleared by load_env, never written - and writes to slot 31, which nobody reads; its velocities are +0 after every finite impulse
 // (x * 0 + 0), so reloading zeros is what keeping them in registers was.  Every `if (dynamic)` around a load or a store was a
@@ -807,7 +766,7 @@ DE_OOL DrvSplitRet drv_solve_general_split(int lane, int myLevel_, int bodyAB, i
                                            int bits3) {
   DrvLds& L = g_L;
   DrvMailbox& M = L.u.mb;
-  int code = ((pk >> 30) & 1) | (((pk >> 8) & 0xFF) << 1) | (myLevel_ << 8);  // active | contact count << 1 | level << 8
+  int code = SLOT_BIT(pk, PK_ACTIVE_SH) | (SLOT_COUNT(pk) << 1) | (myLevel_ << 8);  // active | contact count << 1 | level << 8
   const int maxLevel = (int)(signed char)(uniform_i(lvl_) & 0xFF), period = uniform_i(lvl_) >> 8;
   const bool biasLane = lane >= 32;
   const int sl = lane & 31;  // the slot this lane works for
@@ -889,21 +848,23 @@ DRV_PROF(DE_DEV int prof_any(int v) { const uint64_t m = wave_ballot(v != 0); re
 // register (round 1 had it the other way round and paid the save / restore of 47 callee-saved VGPRs per call: 3/4 of that
 // kernel's HBM traffic).  Its solver is a set of functions again (drv_prestep_solve ...), all leaves, entered with nothing of the
 // contact cache live.
-#ifndef DRV_CONTACT_INLINE
-#define DRV_CONTACT_INLINE __forceinline__
-#endif
 
-// pk: a_state | a_count << 8 | a_age << 16 | touched << 24 | freeMe << 25 | hashSame << 26 | prevInert << 27 | skipped << 28 | slotOcc << 29 | active << 30
+// What a solve function returns (the "solve bits"; a -DDRV_PROFILE build adds the kind of solve from bit SOLVE_PROF_SH up) ...
+enum { SOLVE_NEEDS_SPLIT = 1, SOLVE_ALL_INERT = 2, SOLVE_ALL_STEADY = 4, SOLVE_TOOK_SPLIT = 8, SOLVE_PROF_SH = 4 };
+// ... and the three predicates of the prestep that drv_slot_verdicts needs after the sweeps (bits3)
+enum { B3_REST_IN = 1, B3_BIAS0_ZERO = 2, B3_BIAS1_ZERO = 4 };
+// pk: the packed slot state (layout, pk_pack and the accessors in driving_dev.h).
 // The end of a solve, once for both of its callers (drv_prestep_solve: every solve whose sweeps ran inside it; drv_split_verdicts:
 // after drv_solve_general_split): the steady / inert verdicts of the slots and the slot record.  restIn: both bodies exactly at rest
-// when the arbiter was prestepped; biasZ0 / biasZ1: bias[c] == 0.0.  Returns allInert << 1 | allSteady << 2 | tookSplit << 3.
+// when the arbiter was prestepped; biasZ0 / biasZ1: bias[c] == 0.0.  Returns SOLVE_ALL_INERT | SOLVE_ALL_STEADY | SOLVE_TOOK_SPLIT.
 DE_DEV int drv_slot_verdicts(int lane, int pk, int a_pair, bool restIn, bool biasZ0, bool biasZ1, double jn0, double jn1, double jt0, double jt1,
                              double jBias0, double jBias1, bool tookSplit) {
   DrvLds& L = g_L;
-  int a_state = pk & 0xFF;
-  const int a_count = (pk >> 8) & 0xFF, a_age = (pk >> 16) & 0xFF;
-  const bool touched = (pk >> 24) & 1, freeMe = (pk >> 25) & 1, hashSame = (pk >> 26) & 1, prevInert = (pk >> 27) & 1;
-  const bool skipped = (pk >> 28) & 1, slotOcc = (pk >> 29) & 1, active = (pk >> 30) & 1;
+  int a_state = SLOT_STATE(pk);
+  const int a_count = SLOT_COUNT(pk), a_age = SLOT_AGE(pk);
+  const bool touched = SLOT_BIT(pk, PK_TOUCHED_SH), freeMe = SLOT_BIT(pk, PK_FREE_SH), hashSame = SLOT_BIT(pk, PK_HASH_SAME_SH);
+  const bool prevInert = SLOT_BIT(pk, PK_PREV_INERT_SH), skipped = SLOT_BIT(pk, PK_SKIPPED_SH), slotOcc = SLOT_BIT(pk, PK_OCC_SH);
+  const bool active = SLOT_BIT(pk, PK_ACTIVE_SH);
   // arbiters that were active this step are NORMAL from the next step on (cpSpaceStep resets the state)
   const bool wasNormal = a_state == ARB_NORMAL;  // i.e. not a first contact in this substep
   if (active && a_state == ARB_FIRST) a_state = ARB_NORMAL;
@@ -933,18 +894,19 @@ DE_DEV int drv_slot_verdicts(int lane, int pk, int a_pair, bool restIn, bool bia
   const bool inert = !slotOcc | (skipped ? prevInert : (fresh & (ignored | (normalRun & zeroImpulses))));
   if (slotOcc) {
     if (freeMe) L.s_pair[lane] = 0xFFFF;
-    L.s_meta[lane] = a_state | (a_count << 8) | (a_age << 16) | (steady ? (1 << 24) : 0) | (inert ? (1 << 25) : 0);
+    L.s_meta[lane] = meta_pack(a_state, a_count, a_age, steady, inert);
     if (touched) { L.s_jn0[lane] = jn0; L.s_jt0[lane] = jt0; L.s_jn1[lane] = jn1; L.s_jt1[lane] = jt1; }
   }
   const bool allInert = wave_ballot(!inert) == 0ull;
-  return (allInert ? 2 : 0) | (allSteady ? 4 : 0) | (tookSplit ? 8 : 0);
+  return (allInert ? SOLVE_ALL_INERT : 0) | (allSteady ? SOLVE_ALL_STEADY : 0) | (tookSplit ? SOLVE_TOOK_SPLIT : 0);
 }
 // What drv_prestep_solve_multi hands back, in registers (a vector: an aggregate of more than 16 words would come back through
-// scratch).  Every solve: the low word of [11] = needsSplit | allInert << 1 | allSteady << 2.  needsSplit (a general multi-level solve: prestep,
+// scratch).  Every solve: the low word of [11] = the solve bits.  SOLVE_NEEDS_SPLIT (a general multi-level solve: prestep,
 // velocity update and warm start are done, the sweeps and the verdicts are not) also fills in the arguments of
 // drv_solve_general_split, which the KERNEL calls - the outermost frame never saves a return address, and the solve function stays a leaf:
 // [0..9] = nMass, bias, bounce, jn, jt of the two contacts, [10] = pk | pair << 32,
-// [11] = bits | (restIn | bias0 == 0 << 1 | bias1 == 0 << 2) << 8 | myLevel << 16 | (bodyA | bodyB << 8 | level word << 16) << 32.
+// [11] = solve bits | bits3 << SR_BITS3_SH | myLevel << SR_LEVEL_SH | (bodyA | bodyB << 8 | level word << SR_LVWORD_SH) << 32.
+enum { SR_BITS3_SH = 8, SR_LEVEL_SH = 16, SR_LVWORD_SH = 16 };
 typedef double DrvSolveRet __attribute__((ext_vector_type(12)));
 DE_DEV double drv_pack2(int lo, int hi) { return __hiloint2double(hi, lo); }
 // MULTI: some active arbiters share a dynamic body (maxLevel > 0).  The two kinds of solve are two out-of-line functions
@@ -955,9 +917,9 @@ DE_DEV DrvSolveRet drv_prestep_solve_body(int lane, int nCarPed, int pk, int a_p
                                           int maxLevel_, int anyActive_, double jn0, double jn1, double jt0, double jt1) {
   DrvLds& L = g_L;
   DrvMailbox& M = L.u.mb;
-  const int a_state = pk & 0xFF;
-  const int a_count = (pk >> 8) & 0xFF;
-  const bool active = (pk >> 30) & 1;
+  const int a_state = SLOT_STATE(pk);
+  const int a_count = SLOT_COUNT(pk);
+  const bool active = SLOT_BIT(pk, PK_ACTIVE_SH);
   const bool isCar = lane < (uniform_i(nCarPed) & 0xFF), isPed = lane >= DRV_SLOT_PED && lane < DRV_SLOT_PED + (uniform_i(nCarPed) >> 8);
   const int maxLevel = (int)(signed char)(uniform_i(maxLevel_) & 0xFF), period = uniform_i(maxLevel_) >> 8;
   const uint64_t activeMask = uniform_i(anyActive_) ? 1ull : 0ull;
@@ -966,8 +928,8 @@ DRV_PROF(const unsigned long long P0 = __builtin_amdgcn_s_memtime();)
   V2 n = v2(0.0, 0.0), r1[2], r2[2];
   r1[0] = r1[1] = r2[0] = r2[1] = v2(0.0, 0.0);
   // ---- prestep (cpArbiterPreStep) on velocities BEFORE the friction update -------------------------------
-  double nMass[2] = {0.0, 0.0}, tMass[2] = {0.0, 0.0}, bias[2] = {0.0, 0.0}, bounce[2] = {0.0, 0.0}, jBias[2] = {0.0, 0.0};
-  const double arb_e = 0.05 * 0.05, arb_u = 0.0 * 0.0;
+  double nMass[2] = {0.0, 0.0}, bias[2] = {0.0, 0.0}, bounce[2] = {0.0, 0.0}, jBias[2] = {0.0, 0.0};
+  const double arb_e = 0.05 * 0.05;  // (arb_u = 0 * 0: see arb_apply_impulse)
   bool restIn = false;  // both bodies exactly at rest when the arbiter was prestepped
   if (active) {
     BodyV a, b;
@@ -1018,7 +980,7 @@ DRV_PROF(profMode = 1;)
       } else {
 DRV_PROF(profMode = 2;)
 #pragma unroll 1
-        for (int iter = 0; iter < 10; ++iter) arb_apply_impulse(a, b, n, r1, r2, nMass, tMass, bias, bounce, jBias, jn, jt, a_count, arb_u);
+        for (int iter = 0; iter < 10; ++iter) arb_apply_impulse(a, b, n, r1, r2, nMass, bias, bounce, jBias, jn, jt, a_count);
       }
       body_store_vel(L, bodyA, a);
       body_store_vel(L, bodyB, b);
@@ -1074,12 +1036,12 @@ DRV_PROF(profMode = wave_ballot(!biasOnly) == 0ull ? 3 : 4;)
       // with what the sweeps and the verdicts need (a function that calls saves its return address through a VGPR that it stores to
       // and reloads from scratch right in front of EVERY return, and keeps 16 values in scratch across the call)
 DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + blockIdx.x * 8; const unsigned long long P3 = __builtin_amdgcn_s_memtime(); d[2] += P1 - P0; d[3] += (P2 - P1) + ((P3 - P2) << 32); })
-      const int bits3 = (restIn ? 1 : 0) | (bias[0] == 0.0 ? 2 : 0) | (bias[1] == 0.0 ? 4 : 0);
+      const int bits3 = (restIn ? B3_REST_IN : 0) | (bias[0] == 0.0 ? B3_BIAS0_ZERO : 0) | (bias[1] == 0.0 ? B3_BIAS1_ZERO : 0);
       DrvSolveRet r;
       r[0] = nMass[0]; r[1] = nMass[1]; r[2] = bias[0]; r[3] = bias[1]; r[4] = bounce[0]; r[5] = bounce[1];
       r[6] = jn[0]; r[7] = jn[1]; r[8] = jt[0]; r[9] = jt[1];
       r[10] = drv_pack2(pk, a_pair);
-      r[11] = drv_pack2(1 | (bits3 << 8) | (myLevel << 16), bodyA | (bodyB << 8) | (maxLevel_ << 16));
+      r[11] = drv_pack2(SOLVE_NEEDS_SPLIT | (bits3 << SR_BITS3_SH) | (myLevel << SR_LEVEL_SH), bodyA | (bodyB << 8) | (maxLevel_ << SR_LVWORD_SH));
       return r;
     }
   }
@@ -1087,10 +1049,10 @@ DRV_PROF(const unsigned long long P3 = __builtin_amdgcn_s_memtime();)
   const int bits = drv_slot_verdicts(lane, pk, a_pair, restIn, bias[0] == 0.0, bias[1] == 0.0, jn[0], jn[1], jt[0], jt[1], jBias[0], jBias[1], false);
 DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + blockIdx.x * 8; const unsigned long long P4 = __builtin_amdgcn_s_memtime(); d[2] += (P1 - P0) + ((P4 - P3) << 32); d[3] += (P2 - P1) + ((P3 - P2) << 32); })
   DrvSolveRet r;  // (only the low word of [11] means anything)
-  r[11] = drv_pack2(bits DRV_PROF(| (prof_any(profMode) << 4)), 0);
+  r[11] = drv_pack2(bits DRV_PROF(| (prof_any(profMode) << SOLVE_PROF_SH)), 0);
   return r;
 }
-// nothing active, or no two active arbiters share a dynamic body (maxLevel = 0): returns allInert << 1 | allSteady << 2
+// nothing active, or no two active arbiters share a dynamic body (maxLevel = 0): returns SOLVE_ALL_INERT | SOLVE_ALL_STEADY
 DE_OOL int drv_prestep_solve(int lane, int nCarPed, int pk, int a_pair, int bodyA, int bodyB, int anyActive_, double jn0, double jn1, double jt0,
                              double jt1) {
   return __double2loint(drv_prestep_solve_body<false>(lane, nCarPed, pk, a_pair, bodyA, bodyB, 0, 1 << 8 /* maxLevel 0, period 1 */, anyActive_, jn0, jn1, jt0, jt1)[11]);
@@ -1103,14 +1065,20 @@ DE_OOL DrvSolveRet drv_prestep_solve_multi(int lane, int nCarPed, int pk, int a_
 // The verdicts and the slot record after drv_solve_general_split: a leaf like the sweeps before it, called by the kernel with the
 // values those hand back.
 DE_OOL int drv_split_verdicts(int lane, int pk, int a_pair, int bits3, double jn0, double jn1, double jBias0, double jBias1, double jt0, double jt1) {
-  return drv_slot_verdicts(lane, pk, a_pair, (bits3 & 1) != 0, (bits3 & 2) != 0, (bits3 & 4) != 0, jn0, jn1, jt0, jt1, jBias0, jBias1, true);
+  return drv_slot_verdicts(lane, pk, a_pair, (bits3 & B3_REST_IN) != 0, (bits3 & B3_BIAS0_ZERO) != 0, (bits3 & B3_BIAS1_ZERO) != 0, jn0, jn1, jt0, jt1, jBias0, jBias1, true);
 }
+// err: CRET_OVERFLOW a pair was dropped (-> DYNENV_ERRBIT_OVERFLOW); CRET_INERT / CRET_STEADY every slot came out inert / steady;
+// CRET_LIGHT_REPLAY light mode, no dirty pair touches: replay the previous substep; CRET_SPLIT the sweeps ran in drv_solve_general_split
+enum { CRET_OVERFLOW = 1, CRET_INERT_SH = 1, CRET_INERT = 1 << CRET_INERT_SH, CRET_STEADY_SH = 2, CRET_STEADY = 1 << CRET_STEADY_SH,
+       CRET_LIGHT_REPLAY_SH = 3, CRET_LIGHT_REPLAY = 1 << CRET_LIGHT_REPLAY_SH, CRET_SPLIT_SH = 4, CRET_SPLIT = 1 << CRET_SPLIT_SH };
+static_assert(SOLVE_ALL_INERT == CRET_INERT && SOLVE_ALL_STEADY == CRET_STEADY && (SOLVE_TOOK_SPLIT << 1) == CRET_SPLIT,
+              "drv_contact_path passes the two verdicts on in place and the split bit one place up");
 struct ContactRet {
   uint64_t occ;
   int err;
 };
 
-__device__ DRV_CONTACT_INLINE ContactRet drv_contact_path(int lane, int cand, int dirty, int light, int A, int nCarPed, uint64_t occ) {
+DE_DEV ContactRet drv_contact_path(int lane, int cand, int dirty, int light, int A, int nCarPed, uint64_t occ) {
   const bool isCar = lane < A, isPed = lane >= DRV_SLOT_PED && lane < DRV_SLOT_PED + (nCarPed >> 8);
   DrvLds& L = g_L;
   int err = 0;
@@ -1147,7 +1115,7 @@ DRV_PROF(int profCand = 0;)
     const uint64_t m = wave_ballot(c);
     if (c) {
       const int idx = nCand + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      if (idx < DRV_CLIST) L.clist[idx] = (unsigned short)((i << 8) | lane); else err |= 1;  // overflow is reported
+      if (idx < DRV_CLIST) L.clist[idx] = (unsigned short)((i << 8) | lane); else err |= CRET_OVERFLOW;  // overflow is reported
     }
     nCand += __popcll(m);
   }
@@ -1179,12 +1147,12 @@ DRV_PROF(nMath -= __builtin_amdgcn_s_memtime();)
       BoxP b1;
       b1.p = v2(L.px[i], L.py[i]); b1.c = L.rc[i]; b1.s = L.rs[i]; b1.hx = L.chx[i]; b1.hy = L.chy[i];
       if (j >= DRV_SLOT_PED && j < DRV_SLOT_OBST) {
-        circle_to_poly(v2(L.px[j], L.py[j]), 5.0, b1, q, ct);
+        circle_to_poly(v2(L.px[j], L.py[j]), DRV_PED_R, b1, q, ct);
       } else {  // car or static box: one instance of the SAT + clipping code for both
         BoxP b2;
         b2.c = 1.0; b2.s = 0.0;
         if (j < DRV_SLOT_PED) { b2.p = v2(L.px[j], L.py[j]); b2.c = L.rc[j]; b2.s = L.rs[j]; b2.hx = L.chx[j]; b2.hy = L.chy[j]; }
-        else { b2.p = static_pos(L, j); b2.hx = j >= DRV_SLOT_BLD ? 400.0 : 10.0; b2.hy = j >= DRV_SLOT_BLD ? 225.0 : 10.0; }
+        else { b2.p = static_pos(L, j); b2.hx = j >= DRV_SLOT_BLD ? DRV_BLD_HX : DRV_OBST_H; b2.hy = j >= DRV_SLOT_BLD ? DRV_BLD_HY : DRV_OBST_H; }
         poly_to_poly(b1, i, b2, j, q, ct);
       }
     }
@@ -1211,7 +1179,7 @@ DRV_PROF(nMath += __builtin_amdgcn_s_memtime();)
       if (needNew) {
         for (int r = 0; r < rank; ++r) fm &= fm - 1;
         if (fm) { slot = __builtin_ctzll(fm); L.s_pair[slot] = pr; }
-        else err |= 1;  // contact cache overflow: pair dropped (reported through EI_ERR)
+        else err |= CRET_OVERFLOW;  // contact cache overflow: pair dropped (reported through EI_ERR)
       }
       int cnt = __popcll(newMask);
       uint64_t fm2 = (~occ) & slotBits;
@@ -1237,7 +1205,7 @@ DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgl + 
   }
   if (lightOk) {
     ContactRet ret;
-    ret.occ = occ; ret.err = err | 8;
+    ret.occ = occ; ret.err = err | CRET_LIGHT_REPLAY;
     return ret;
   }
 
@@ -1263,8 +1231,8 @@ DRV_PROF(const unsigned long long T1 = __builtin_amdgcn_s_memtime();)
   if (slotOcc) {
     touched = flag != 0;
     a_pair = s_pair;
-    a_state = meta & 0xFF; a_count = (meta >> 8) & 0xFF; a_age = (meta >> 16) & 0xFF;
-    prevSteady = (meta >> 24) & 1; prevInert = (meta >> 25) & 1;
+    a_state = SLOT_STATE(meta); a_count = SLOT_COUNT(meta); a_age = SLOT_AGE(meta);
+    prevSteady = SLOT_BIT(meta, META_STEADY_SH); prevInert = SLOT_BIT(meta, META_INERT_SH);
     if (flag & 2) { a_state = ARB_FIRST; a_count = 0; a_age = 0; prevSteady = false; prevInert = false; }
     if (touched) {
       const int i = a_pair >> 8, j = a_pair & 0xFF;
@@ -1437,33 +1405,38 @@ DRV_PROF(const unsigned long long T2 = __builtin_amdgcn_s_memtime();)
 DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgs + blockIdx.x * 8; d[0] += U1 - T1; d[1] += U2 - U1; d[2] += U3 - U2; d[3] += U4 - U3; d[4] += T2 - U4; })
   // everything per-slot from here on - prestep, solve, the steady / inert verdicts and the slot record - happens inside the
   // function: nothing of the contact cache stays live in this frame across the call
-  const int pkArg = (a_state & 0xFF) | ((a_count & 0xFF) << 8) | ((a_age & 0xFF) << 16) | (touched ? 1 << 24 : 0) | (freeMe ? 1 << 25 : 0) |
-                    (hashSame ? 1 << 26 : 0) | (prevInert ? 1 << 27 : 0) | (skipped ? 1 << 28 : 0) | (slotOcc ? 1 << 29 : 0) | (active ? 1 << 30 : 0);
+  const int pkArg = pk_pack(a_state, a_count, a_age, touched, freeMe, hashSame, prevInert, skipped, slotOcc, active);
   int solveBits;
   if (activeMask == 0ull || maxLevel == 0) {
     solveBits = drv_prestep_solve(lane, nCarPed, pkArg, a_pair, bodyA, bodyB, activeMask != 0ull ? 1 : 0, jn[0], jn[1], jt[0], jt[1]);
   } else {
     const DrvSolveRet sv = drv_prestep_solve_multi(lane, nCarPed, pkArg, a_pair, bodyA, bodyB, myLevel, (maxLevel & 0xFF) | (period << 8), jn[0], jn[1], jt[0], jt[1]);
     solveBits = __double2loint(sv[11]);
-    if (uniform_i(solveBits) & 1) [[unlikely]] {
+    if (uniform_i(solveBits) & SOLVE_NEEDS_SPLIT) [[unlikely]] {
       // A general multi-level solve: the sweeps and then the verdicts, both leaves, called from here.  NOTHING of this frame lives across
       // the three calls: what one callee hands back goes straight into the next one's argument registers (the packed slot state, the
       // pair, the tangent impulses and three predicates travel through the sweeps and come back in their return value).
       const int w1 = __double2hiint(sv[11]);
 DRV_PROF(const unsigned long long S0 = __builtin_amdgcn_s_memtime();)
-      const DrvSplitRet sr = drv_solve_general_split(fresh_lane(), (solveBits >> 16) & 0xFF, w1 & 0xFFFF, w1 >> 16, sv[0], sv[1], sv[2], sv[3], sv[4], sv[5],
-                                                     sv[6], sv[7], sv[8], sv[9], __double2loint(sv[10]), __double2hiint(sv[10]), (solveBits >> 8) & 7);
+      const DrvSplitRet sr = drv_solve_general_split(fresh_lane(), (solveBits >> SR_LEVEL_SH) & 0xFF, w1 & 0xFFFF, w1 >> SR_LVWORD_SH, sv[0], sv[1], sv[2], sv[3], sv[4], sv[5],
+                                                     sv[6], sv[7], sv[8], sv[9], __double2loint(sv[10]), __double2hiint(sv[10]), (solveBits >> SR_BITS3_SH) & 7);
 DRV_PROF(const unsigned long long S1 = __builtin_amdgcn_s_memtime();)
-      solveBits = drv_split_verdicts(fresh_lane(), sr.pk, sr.pair, sr.bits, sr.jn0, sr.jn1, sr.jb0, sr.jb1, sr.jt0, sr.jt1) DRV_PROF(| (4 << 4));
+      solveBits = drv_split_verdicts(fresh_lane(), sr.pk, sr.pair, sr.bits, sr.jn0, sr.jn1, sr.jb0, sr.jb1, sr.jt0, sr.jt1) DRV_PROF(| (4 << SOLVE_PROF_SH));
 DRV_PROF(if (fresh_lane() == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + blockIdx.x * 8; d[3] += (S1 - S0) << 32; d[2] += (__builtin_amdgcn_s_memtime() - S1) << 32; })
     }
   }
   occ &= ~freeMask;
-DRV_PROF(const unsigned long long T3 = T2, T4 = T2, T5 = __builtin_amdgcn_s_memtime(); const int profModeW = (uniform_i(solveBits) >> 4) & 7;)
-DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + blockIdx.x * 8; d[0] += T1 - T0; d[1] += T2 - T1; d[2] += T3 - T2; d[3] += T4 - T3; d[4] += T5 - T4; d[5] += 1ull + (light ? (1ull << 16) : 0ull); d[6] += (unsigned long long)(maxLevel + 1) + ((unsigned long long)(maxLevel + 1) << (12 * profModeW)); d[7] += (unsigned long long)nTouched + ((unsigned long long)profCand << 16); })
+DRV_PROF(const unsigned long long T3 = T2, T4 = T2, T5 = __builtin_amdgcn_s_memtime(); const int profModeW = (uniform_i(solveBits) >> SOLVE_PROF_SH) & 7;)
+DRV_PROF(if (lane == 0 && blockIdx.x < 4096) {
+  unsigned long long* d = g_dbgp + blockIdx.x * 8;
+  d[0] += T1 - T0; d[1] += T2 - T1; d[2] += T3 - T2; d[3] += T4 - T3; d[4] += T5 - T4;
+  d[5] += 1ull + (light ? (1ull << 16) : 0ull);
+  d[6] += (unsigned long long)(maxLevel + 1) + ((unsigned long long)(maxLevel + 1) << (12 * profModeW));
+  d[7] += (unsigned long long)nTouched + ((unsigned long long)profCand << 16);
+})
   {
     ContactRet ret;
-    ret.occ = occ; ret.err = err | (uniform_i(solveBits) & 6) | ((uniform_i(solveBits) & 8) << 1);  // bit 4: split-lane sweeps
+    ret.occ = occ; ret.err = err | (uniform_i(solveBits) & (SOLVE_ALL_INERT | SOLVE_ALL_STEADY)) | ((uniform_i(solveBits) & SOLVE_TOOK_SPLIT) << 1);
     return ret;
   }
 }
@@ -1482,10 +1455,11 @@ DE_OOL int drv_partial_obs_fused(PvIn in, uint64_t seed, int A, int* envi, int e
 #ifndef DRV_FUSED_AGENTS
 #define DRV_FUSED_AGENTS 10 /* without a forecast: agent passes a light environment runs in the step launch */
 #endif
+enum { LR_MOVING = 1, LR_REMOVED = 2, LR_CAND_CHANGED = 4 };  // DrvLightRet.bits
+enum { LS_VB_VALID = 1, LS_AABB_VALID = 2 };                 // drv_light_substep's stateBits
 struct DrvLightRet {
   int cand, dirty, bits;
 };
-struct DrvSeedOnly { uint64_t seed; };
 DE_OOL DrvLightRet drv_light_substep(int it_, int lane, int A_, int nPed_, int nObst_, int elapsed_,
                                                       uint32_t seedLo, uint32_t seedHi, uint32_t genv_, uint32_t episode_, int stateBits) {
   DrvLds& L = g_L;
@@ -1493,13 +1467,12 @@ DRV_PROF(const unsigned long long Q0 = __builtin_amdgcn_s_memtime();)
   const int lastCand = L.lastCand[lane];
   const int it = uniform_i(it_), A = uniform_i(A_), nPed = uniform_i(nPed_), nObst = uniform_i(nObst_), elapsed = uniform_i(elapsed_);
   const uint32_t genv = (uint32_t)uniform_i((int)genv_), episode = (uint32_t)uniform_i((int)episode_);
-  DrvSeedOnly S;
-  S.seed = ((uint64_t)(uint32_t)uniform_i((int)seedHi) << 32) | (uint64_t)(uint32_t)uniform_i((int)seedLo);
+  const uint64_t seed = ((uint64_t)(uint32_t)uniform_i((int)seedHi) << 32) | (uint64_t)(uint32_t)uniform_i((int)seedLo);
   const bool isCar = lane < A;
   const bool isPed = lane >= DRV_SLOT_PED && lane < DRV_SLOT_PED + nPed;
   const bool isBody = isCar || isPed;
-  const bool vbValid = (uniform_i(stateBits) & 1) != 0;
-  bool aabbValid = (uniform_i(stateBits) & 2) != 0;
+  const bool vbValid = (uniform_i(stateBits) & LS_VB_VALID) != 0;
+  bool aabbValid = (uniform_i(stateBits) & LS_AABB_VALID) != 0;
     bool turned = false;  // Car.turn rotated the body in place: geometry changed even if every velocity is zero
     // ---- ONE batch of LDS loads: everything the lane's role reads below, issued before the first use (a lone wave cannot hide an
     //      LDS round trip, ~110 cycles, and the phases below would otherwise make a dozen of them one after the other).  Indices are
@@ -1523,7 +1496,7 @@ DRV_PROF(const unsigned long long Q0 = __builtin_amdgcn_s_memtime();)
       if (it == 0) {  // processAction :357-373 -> Car.accelerate (Car.py:55-94), Car.turn (Car.py:97-108)
         const int actPk = (int)L.act[lane];
         const int acc = (actPk & 3) - 1, steer = ((actPk >> 2) - 1) * 2;
-        if (!CF_FIN(f)) {
+        if (!CARF_FIN(f)) {
           double dirx = L.dirx[lane], diry = L.diry[lane];
           double power = (double)acc;
           double moveDir = vx * dirx + vy * diry;
@@ -1570,24 +1543,24 @@ DRV_PROF(const unsigned long long Q2 = __builtin_amdgcn_s_memtime();)
       // tick :376-426
       const double dnow = vlen(vsub(pos, v2(goalx, goaly)));
       const double diff = dprev - dnow;
-      if (!CF_FIN(f)) { const double d50 = diff / 50.0; rew += d50; posrew += dm_max(0.0, d50); }
+      if (!CARF_FIN(f)) { const double d50 = diff / 50.0; rew += d50; posrew += dm_max(0.0, d50); }
       L.prevx[lane] = px; L.prevy[lane] = py; L.dprev[lane] = dnow;
       if (lp >= LP_OverRoad) {
-        if (!CF_FIN(f)) {
+        if (!CARF_FIN(f)) {
           if (lp == LP_OverRoad && dnow < 100.0) {
             lp = LP_AtGoal;
-            f |= (1 << 4) | (1 << 6);  // finished, friction_car_crashed
+            f |= CARF_FIN_BIT | CARF_FRIC_BIT;
             rew += (double)(DRV_MAX_TIME - elapsed) / 100.0;
             posrew += (double)(DRV_MAX_TIME - elapsed) / 100.0;
           } else {
-            f |= CF_CRASH_BITS;
+            f |= CARF_CRASH_BITS;
             rew -= vlen(v2(vx, vy)) / 5.0;
           }
         }
       } else if (lp == LP_InOpposingLane) {
-        if (!CF_FIN(f)) rew -= vlen(v2(vx, vy)) / 10000.0;
+        if (!CARF_FIN(f)) rew -= vlen(v2(vx, vy)) / 10000.0;
       }
-      f = CF_SET_LP(f, lp);
+      f = CARF_SET_LP(f, lp);
       if (px >= DRV_W + 50.0 || px <= -50.0 || py >= DRV_H + 50.0 || py <= -50.0) { vx = 0.0; vy = 0.0; }  // prevPos == pos here
       L.flags[lane] = f;
       L.vx[lane] = vx; L.vy[lane] = vy;
@@ -1595,8 +1568,8 @@ DRV_PROF(const unsigned long long Q2 = __builtin_amdgcn_s_memtime();)
 DRV_PROF(asm volatile("" ::: "memory");)
     } else if (isPed) {
       // ======== phase 1b: pedestrian FSM (move :429-506) ====================================================
-      if (!PF_DEAD(f)) {
-        int crossing = PF_CROSSING(f), beginc = PF_BEGIN(f), side = PF_SIDE(f);
+      if (!PEDF_DEAD(f)) {
+        int crossing = PEDF_CROSSING(f), beginc = PEDF_BEGIN(f), side = PEDF_SIDE(f);
         const bool isOffRoad = lp >= LP_OverRoad;  // drv_is_off_road(pos)
         const bool isOut = drv_is_out(pos);
         if (moving > 0) {
@@ -1608,8 +1581,8 @@ DRV_PROF(asm volatile("" ::: "memory");)
           if (isOut) { moving = 0; vx = 0.0; vy = 0.0; }
         } else {
           if (!crossing) {
-            dm_u32x4 u = dm_env_rng(S.seed, genv, episode, DM_RNG_PED_MOVE, (uint32_t)(lane - DRV_SLOT_PED), (uint32_t)elapsed);
-            const bool r1 = PF_ROAD(f) != 0;
+            dm_u32x4 u = dm_env_rng(seed, genv, episode, DM_RNG_PED_MOVE, (uint32_t)(lane - DRV_SLOT_PED), (uint32_t)elapsed);
+            const bool r1 = PEDF_ROAD(f) != 0;
             const V2 rdir = r1 ? v2(RoadK<1>::dirx, RoadK<1>::diry) : v2(RoadK<0>::dirx, RoadK<0>::diry);
             const V2 rnrm = r1 ? v2(RoadK<1>::nx, RoadK<1>::ny) : v2(RoadK<0>::nx, RoadK<0>::ny);
             V2 dir = rdir;
@@ -1626,14 +1599,14 @@ DRV_PROF(asm volatile("" ::: "memory");)
               side = side ? 0 : 1;
               speed = dm_randint(u.v[3], 1, 2);
             }
-            const V2 nv = vmul(vmul(dir, (double)PF_SPEED(f)), (double)speed);
+            const V2 nv = vmul(vmul(dir, (double)PEDF_SPEED(f)), (double)speed);
             vx = nv.x; vy = nv.y;
           } else if (isOffRoad) {
             crossing = 0; beginc = 0;
           }
         }
         L.moving[lane] = moving;
-        L.flags[lane] = PEDF_PACK(PF_ROAD(f), side, 0, crossing, beginc, PF_SPEED(f));
+        L.flags[lane] = PEDF_PACK(PEDF_ROAD(f), side, 0, crossing, beginc, PEDF_SPEED(f));
         L.vx[lane] = vx; L.vy[lane] = vy;
       }
     }
@@ -1671,13 +1644,13 @@ DRV_PROF(const unsigned long long Q3 = __builtin_amdgcn_s_memtime();)
         } else {
           bl = L.aabb[lane][0]; bb = L.aabb[lane][1]; br = L.aabb[lane][2]; bt = L.aabb[lane][3];
         }
-      } else {  // pedestrian: a circle of radius 5 at the new position
-        bl = npx - 5.0; bb = npy - 5.0; br = npx + 5.0; bt = npy + 5.0;
+      } else {  // pedestrian: a circle at the new position
+        bl = npx - DRV_PED_R; bb = npy - DRV_PED_R; br = npx + DRV_PED_R; bt = npy + DRV_PED_R;
       }
     } else if (lane >= DRV_SLOT_OBST && lane < DRV_SLOT_BLD + 4) {
       live = lane >= DRV_SLOT_BLD || (lane - DRV_SLOT_OBST) < nObst;
       const V2 c = static_pos(L, lane);
-      const double ex = lane >= DRV_SLOT_BLD ? 400.0 : 10.0, ey = lane >= DRV_SLOT_BLD ? 225.0 : 10.0;
+      const double ex = lane >= DRV_SLOT_BLD ? DRV_BLD_HX : DRV_OBST_H, ey = lane >= DRV_SLOT_BLD ? DRV_BLD_HY : DRV_OBST_H;
       // static box AABB = min/max of (c +- e) exactly as cached by cpShapeCacheBB with rot = (1,0)
       bl = -ex + c.x; br = ex + c.x; bb = -ey + c.y; bt = ey + c.y;
     }
@@ -1714,9 +1687,14 @@ DRV_PROF(const unsigned long long Q4 = __builtin_amdgcn_s_memtime();)
       removed = lastCand < 0 || (lastCand & ~cand) != 0;
     }
   L.lastCand[lane] = cand;
-DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgl + blockIdx.x * 8; const unsigned long long Q5 = __builtin_amdgcn_s_memtime(); if (it == 0) { for (int k = 0; k < 8; ++k) d[k] = 0ull; } d[0] += Q1 - Q0; d[1] += Q2 - Q1; d[2] += Q3 - Q2; d[3] += Q4 - Q3; d[4] += Q5 - Q4; d[5] += Q5 - Q0; })
+DRV_PROF(if (lane == 0 && blockIdx.x < 4096) {
+  unsigned long long* d = g_dbgl + blockIdx.x * 8;
+  const unsigned long long Q5 = __builtin_amdgcn_s_memtime();
+  if (it == 0) { for (int k = 0; k < 8; ++k) d[k] = 0ull; }
+  d[0] += Q1 - Q0; d[1] += Q2 - Q1; d[2] += Q3 - Q2; d[3] += Q4 - Q3; d[4] += Q5 - Q4; d[5] += Q5 - Q0;
+})
   DrvLightRet ret;
-  ret.cand = cand; ret.dirty = dirty; ret.bits = (candMoving ? 1 : 0) | (removed ? 2 : 0) | (cand != lastCand ? 4 : 0);
+  ret.cand = cand; ret.dirty = dirty; ret.bits = (candMoving ? LR_MOVING : 0) | (removed ? LR_REMOVED : 0) | (cand != lastCand ? LR_CAND_CHANGED : 0);
   return ret;
 }
 // ------------------------------------------------------------------------------------------------
@@ -1741,15 +1719,15 @@ DE_DEV unsigned drv_hw_simd_key() {
 // tick / pv_par of this launch: kernel arguments the host advances per step - or, once a step of the handle has been captured into
 // a hipGraph (tick_src = 1: a replayed launch has frozen arguments), two device words that a one-thread kernel in front of every
 // step advances (drv_tick_advance_kernel).  An eager launch mirrors its arguments into those words, so the switch is seamless.
-DE_DEV int drv_launch_tick(const DrvState& S) { return S.tick_src ? uniform_i(__atomic_load_n(&S.iso[13], __ATOMIC_RELAXED)) : S.tick; }
-DE_DEV int drv_launch_pv(const DrvState& S) { return S.tick_src ? uniform_i(__atomic_load_n(&S.iso[14], __ATOMIC_RELAXED)) : S.pv_par; }
+DE_DEV int drv_launch_tick(const DrvState& S) { return S.tick_src ? uniform_i(__atomic_load_n(&S.iso[DRV_ISOW_TICK], __ATOMIC_RELAXED)) : S.tick; }
+DE_DEV int drv_launch_pv(const DrvState& S) { return S.tick_src ? uniform_i(__atomic_load_n(&S.iso[DRV_ISOW_PV_PAR], __ATOMIC_RELAXED)) : S.pv_par; }
 DE_DEV int drv_iso_assign(const DrvState& S, int lane, int tick) {
   const int b = blockIdx.x, E = S.E;
   if (!S.iso_on) return b;
   const int buf = tick % 3;
-  if (b == 0 && lane == 0) { const int nn = (tick + 2) % 3; S.iso[nn] = 0; S.iso[3 + nn] = 0; }  // the buffer the NEXT step fills
+  if (b == 0 && lane == 0) { const int nn = (tick + 2) % 3; S.iso[DRV_ISOW_LEN + nn] = 0; S.iso[DRV_ISOW_SLOWEST + nn] = 0; }  // the buffer the NEXT step fills
   if (S.iso_on == 3) return b;  // timing only (Partial observations): see drv_iso_report and the fused passes in drv_step_body
-  int K = uniform_i(S.iso[buf]);
+  int K = uniform_i(S.iso[DRV_ISOW_LEN + buf]);
   const int cap = S.iso_on == 1 ? DRV_ISO_MAX : DRV_ISO_LIST;
   K = K < cap ? K : cap;
   // mode 1: the regular grid is ALWAYS one residency round of the device (G = 4096 blocks, whatever E <= G is: the block -> SIMD
@@ -1774,15 +1752,15 @@ DE_DEV int drv_iso_assign(const DrvState& S, int lane, int tick) {
         // hysteresis: one launch that did not validate keeps isolation off for the next DRV_ISO_COOLDOWN validated ones as well - a
         // device shared with another kernel validates now and then by chance, and placeholders parked on such a launch's verdict
         // hold wave slots the other kernel could use
-        int cd = S.iso[12];
+        int cd = S.iso[DRV_ISOW_COOL];
         if (!ok) cd = DRV_ISO_COOLDOWN; else if (cd > 0) cd -= 1;
-        S.iso[12] = cd;
-        S.iso[8 + (tick + 1) % 3] = (ok && cd == 0) ? 1 : 0;
-        if (!ok && tick > 1) atomicAdd(&S.iso[11], 1);
+        S.iso[DRV_ISOW_COOL] = cd;
+        S.iso[DRV_ISOW_VALID + (tick + 1) % 3] = (ok && cd == 0) ? 1 : 0;
+        if (!ok && tick > 1) atomicAdd(&S.iso[DRV_ISOW_INVALID], 1);
       }
       return -1;
     }
-    if (uniform_i(S.iso[8 + buf]) != 1) K = 0;
+    if (uniform_i(S.iso[DRV_ISOW_VALID + buf]) != 1) K = 0;
   }
   if (K == 0) return b < E ? b : -1;
   const int* H = S.iso + DRV_ISO_HDR + buf * DRV_ISO_LIST;
@@ -1807,7 +1785,7 @@ DE_DEV int drv_iso_assign(const DrvState& S, int lane, int tick) {
         if (uniform_i(__atomic_load_n(&S.iso_done[h], __ATOMIC_RELAXED)) == tick) break;
         __builtin_amdgcn_s_sleep(127);
       }
-      if (i >= 96 && lane == 0) atomicAdd(&S.iso[7], 1);  // (diagnostic: a placeholder that gave up waiting; dynenv_debug_counters)
+      if (i >= 96 && lane == 0) atomicAdd(&S.iso[DRV_ISOW_GAVE_UP], 1);  // (diagnostic: a placeholder that gave up waiting; dynenv_debug_counters)
       return -1;
     }
     r = pos * (DRV_ISO_GROUPS - K) + (g < DRV_ISO_G0 ? g : g - K);
@@ -1840,12 +1818,12 @@ DE_DEV void drv_iso_report(const DrvState& S, int e, int lane, unsigned long lon
   if (!S.iso_on || lane != 0) return;
   const int cycles = (int)(__builtin_amdgcn_s_memtime() - t0);
   const int buf = tick % 3, nxt = (tick + 1) % 3;
-  const int slowest = S.iso[3 + buf];
+  const int slowest = S.iso[DRV_ISOW_SLOWEST + buf];
   // (only the few environments above the floor touch the shared words: 4096 atomics on one address serialise - 0.12 ms, measured)
-  if (cycles > DRV_ISO_MIN && cycles > (slowest / 100) * DRV_ISO_PCT) atomicMax(&S.iso[3 + nxt], cycles);
+  if (cycles > DRV_ISO_MIN && cycles > (slowest / 100) * DRV_ISO_PCT) atomicMax(&S.iso[DRV_ISOW_SLOWEST + nxt], cycles);
   if (S.iso_on == 3) return;
   if (slowest > DRV_ISO_MIN && cycles > (slowest / 100) * DRV_ISO_PCT) {
-    const int k = atomicAdd(&S.iso[nxt], 1);
+    const int k = atomicAdd(&S.iso[DRV_ISOW_LEN + nxt], 1);
     if (k < DRV_ISO_LIST) S.iso[DRV_ISO_HDR + nxt * DRV_ISO_LIST + k] = e;
   }
   __atomic_store_n(&S.iso_done[e], tick, __ATOMIC_RELAXED);
@@ -1863,7 +1841,7 @@ DRV_PROF(const unsigned long long KS = isoT0;)
   DrvLds& L = g_L;
   int lane = threadIdx.x;
   const int tick = drv_launch_tick(S);
-  if (!S.tick_src && blockIdx.x == 0 && lane == 0) { S.iso[13] = S.tick; S.iso[14] = S.pv_par; }  // (mirror for a later switch to tick_src = 1)
+  if (!S.tick_src && blockIdx.x == 0 && lane == 0) { S.iso[DRV_ISOW_TICK] = S.tick; S.iso[DRV_ISOW_PV_PAR] = S.pv_par; }  // (mirror for a later switch to tick_src = 1)
   const int e = drv_iso_assign(S, lane, tick);  // (= blockIdx.x unless the slow environments of the previous step are being isolated)
   if (e < 0) return;
   if (mask && uniform_i(mask[e]) == 0) {
@@ -1902,7 +1880,7 @@ DRV_PROF(if (lane < 8 && e < 4096) { g_dbgp[e * 8 + lane] = 0ull; g_dbgs[e * 8 +
     if (bad) { act0 = 1; act1 = 1; }
     if (lane < 16) L.act[lane] = (unsigned char)(act0 | (act1 << 2));
     const bool anyBad = wave_ballot(bad) != 0ull;
-    if (lane == 0) L.stepErr = anyBad ? 2 : 0;
+    if (lane == 0) L.stepErr = anyBad ? DYNENV_ERRBIT_ACTION : 0;
   }
   int finishedAt = -1;  // elapsed time at which the last car finished in this step: the team reward (:252-254) follows from it
   if (lane < 16) { L.rewAcc[lane] = 0.0; L.posAcc[lane] = 0.0; }
@@ -1911,10 +1889,10 @@ DRV_PROF(if (lane < 8 && e < 4096) { g_dbgp[e * 8 + lane] = 0ull; g_dbgs[e * 8 +
   // whether every cached arbiter was inert when the contact path last ran
   L.lastCand[lane] = g_lastCand;
   if (lane == 0) { L.clistN = -1; L.sActive = ~0ull; L.sLvMeta = 0; }
-  bool inertAll = (uniform_i(envi[EI_PAD]) & 1) != 0;
+  bool inertAll = (uniform_i(envi[EI_SHORTCUT]) & SC_INERT) != 0;
   // steady-replay state: the contact path ran (or was replayed) in the previous substep and reported every slot steady
-  bool steadyAll = (uniform_i(envi[EI_PAD]) & 2) != 0;
-  bool vbValid = (uniform_i(envi[EI_PAD]) & 4) != 0;
+  bool steadyAll = (uniform_i(envi[EI_SHORTCUT]) & SC_STEADY) != 0;
+  bool vbValid = (uniform_i(envi[EI_SHORTCUT]) & SC_VB_VALID) != 0;
   // The step's ten diagnostic counters (EI_N_FAST .. EI_N_SPLIT), packed into two wave-uniform words: they live in scalar registers
   // across the calls of the substep loop (ten words, two of them counted after the contact path, took vector registers that were
   // stored to scratch before every call of the solver and reloaded after it).  cntA: four bits per counter in the order of the
@@ -1934,9 +1912,9 @@ DRV_PROF(const unsigned long long K0 = __builtin_amdgcn_s_memtime(); unsigned lo
 DRV_PROF(const unsigned long long A0 = __builtin_amdgcn_s_memtime();)
     // ======== phase 1a: car game logic (processAction at substep 0, tick) ===================================
     const DrvLightRet lr = drv_light_substep(it, lane, A, nPed, nObst, elapsed, (uint32_t)S.seed, (uint32_t)(S.seed >> 32), genv, episode,
-                                             (vbValid ? 1 : 0) | (aabbValid ? 2 : 0));
+                                             (vbValid ? LS_VB_VALID : 0) | (aabbValid ? LS_AABB_VALID : 0));
     const int cand = lr.cand, dirty = lr.dirty;
-    const bool candMoving = (lr.bits & 1) != 0, removed = (lr.bits & 2) != 0;
+    const bool candMoving = (lr.bits & LR_MOVING) != 0, removed = (lr.bits & LR_REMOVED) != 0;
     aabbValid = true;
 DRV_PROF(const unsigned long long A1 = A0;)
     const uint64_t anyCand = wave_ballot(cand != 0);
@@ -1944,7 +1922,7 @@ DRV_PROF(const unsigned long long A1 = A0;)
     // every cached arbiter inert (zero bias, zero accumulated impulse, not first contact).  Then narrowphase, arbiter
     // update, warm start and all 10 solver iterations are exact no-ops (DESIGN.md "quiescent shortcut") and only the
     // velocity update remains.
-    const bool candChanged = wave_ballot((lr.bits & 4) != 0) != 0ull, anyMoving = wave_ballot(candMoving) != 0ull;
+    const bool candChanged = wave_ballot((lr.bits & LR_CAND_CHANGED) != 0) != 0ull, anyMoving = wave_ballot(candMoving) != 0ull;
     if (candChanged && lane == 0) L.clistN = -1;  // the contact path's candidate list belongs to other masks now
     const bool quiescent = inertAll && !candChanged && !anyMoving;
     // Steady replay: the contact path of the previous substep reported every slot steady, the candidate set is the
@@ -1974,15 +1952,15 @@ DRV_PROF(tookContact = true;)
       __builtin_amdgcn_s_setprio(3);  // an environment on the contact path is on the launch's critical path: issue it first
       ContactRet cr = drv_contact_path(lane, cand, dirty, light ? 1 : 0, A, A | (nPed << 8), occ);
       lane = fresh_lane();
-      if (wave_ballot((cr.err & 1) != 0) != 0ull && lane == 0) L.stepErr |= 1;
-      if (light && !(uniform_i(cr.err >> 3) & 1)) lightOff = true;
-      if (uniform_i(cr.err >> 3) & 1) {  // light mode: no dirty pair touches => replay
+      if (wave_ballot((cr.err & CRET_OVERFLOW) != 0) != 0ull && lane == 0) L.stepErr |= DYNENV_ERRBIT_OVERFLOW;
+      if (light && !(uniform_i(cr.err >> CRET_LIGHT_REPLAY_SH) & 1)) lightOff = true;
+      if (uniform_i(cr.err >> CRET_LIGHT_REPLAY_SH) & 1) {  // light mode: no dirty pair touches => replay
         replay = true; cntB = (unsigned)uniform_i((int)(cntB + (1u << 8)));
       } else {
-        cntB = (unsigned)uniform_i((int)(cntB + ((unsigned)(uniform_i(cr.err >> 4) & 1) << 12)));
+        cntB = (unsigned)uniform_i((int)(cntB + ((unsigned)(uniform_i(cr.err >> CRET_SPLIT_SH) & 1) << 12)));
         occ = uniform_u64(cr.occ);
-        inertAll = (uniform_i(cr.err >> 1) & 1) != 0;
-        steadyAll = (uniform_i(cr.err >> 2) & 1) != 0;
+        inertAll = (uniform_i(cr.err >> CRET_INERT_SH) & 1) != 0;
+        steadyAll = (uniform_i(cr.err >> CRET_STEADY_SH) & 1) != 0;
         vbValid = true;
       }
     }
@@ -1998,7 +1976,7 @@ DRV_PROF(const unsigned long long A3 = __builtin_amdgcn_s_memtime(); tPh1 += A1 
     // ======== bookkeeping :280-287 =========================================================================
     elapsed += 1;
     bool notDone = false;
-    if (isCar) { int f = L.flags[lane]; notDone = !(CF_FIN(f) && !CF_CRASHED(f)); }
+    if (isCar) { int f = L.flags[lane]; notDone = !(CARF_FIN(f) && !CARF_CRASHED(f)); }
     const bool allFin = wave_ballot(notDone) == 0ull;
     if (!allFinished && allFin) {
       allFinished = 1;
@@ -2028,7 +2006,7 @@ DRV_PROF(const unsigned long long K1 = __builtin_amdgcn_s_memtime();)
   if (lane == 0) {
     dones[e] = (uint8_t)(elapsed >= DRV_MAX_TIME);
     envi[EI_ELAPSED] = elapsed; envi[EI_ALLFIN] = allFinished; envi[EI_OCC] = (int)(uint32_t)occ;
-    envi[EI_PAD] = (inertAll ? 1 : 0) | (steadyAll ? 2 : 0) | (vbValid ? 4 : 0);
+    envi[EI_SHORTCUT] = (inertAll ? SC_INERT : 0) | (steadyAll ? SC_STEADY : 0) | (vbValid ? SC_VB_VALID : 0);
   }
   const int errBits = uniform_i(L.stepErr);
   S.lastcand[(size_t)e * 64 + lane] = L.lastCand[lane];
@@ -2053,7 +2031,7 @@ DRV_PROF(const unsigned long long K1 = __builtin_amdgcn_s_memtime();)
   // its passes), and they - not the slowest environment - were what the launch waited for.
   int budget = 0;
   if (PARTIAL && pobs && S.iso_on >= 2) {
-    const int slowest = uniform_i(S.iso[3 + tick % 3]);
+    const int slowest = uniform_i(S.iso[DRV_ISOW_SLOWEST + tick % 3]);
     if (slowest > 0) {
       budget = (slowest / 100) * DRV_PV_DEADLINE_PCT - (int)(__builtin_amdgcn_s_memtime() - isoT0);
       fusedAgents = budget > 0 ? A : 0;
@@ -2076,12 +2054,18 @@ DRV_PROF(const unsigned long long K1 = __builtin_amdgcn_s_memtime();)
     envi[EI_DEFER_OBS] = fusedAgents;  // first agent the deferred launch has to do
     if (pobs && fusedAgents < A) {  // ... and this environment on its list
       const int pv = drv_launch_pv(S);
-      const int k = atomicAdd(&S.pvq[16 * pv], 1);
-      if (k < S.E) S.pvq[32 + pv * S.E + k] = e;
-      else envi[EI_ERR] = envi[EI_ERR] | 4;  // only a host that replays a captured launch (frozen pv_par: the length is never cleared) gets here
+      const int k = atomicAdd(&S.pvq[DRV_PVQ_LEN(pv)], 1);
+      if (k < S.E) S.pvq[DRV_PVQ_LIST(pv, S.E) + k] = e;
+      else envi[EI_ERR] = envi[EI_ERR] | DYNENV_ERRBIT_DEFER_LIST;  // only a host that replays a captured launch (frozen pv_par: the length is never cleared) gets here
     }
   }
-DRV_PROF(if (lane == 0 && e < 4096) { unsigned long long* d = g_dbgw + e * 12; const unsigned long long KE = __builtin_amdgcn_s_memtime(); d[0] = KE - KS; d[1] = DRV_CNT_GET(EI_N_CONTACT); d[2] = __popcll(occ); d[3] = DRV_CNT_GET(EI_N_STEADY) + DRV_CNT_GET(EI_N_QUIET); d[4] = K0 - KS; d[5] = tPh1; d[6] = tBroad; d[7] = tFast; d[8] = tCont; d[9] = (K1 - K0) - tPh1 - tBroad - tFast - tCont; d[10] = KE - K1; d[11] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned long long)__builtin_amdgcn_s_getreg(63492); })
+DRV_PROF(if (lane == 0 && e < 4096) {
+  unsigned long long* d = g_dbgw + e * 12;
+  const unsigned long long KE = __builtin_amdgcn_s_memtime();
+  d[0] = KE - KS; d[1] = DRV_CNT_GET(EI_N_CONTACT); d[2] = __popcll(occ); d[3] = DRV_CNT_GET(EI_N_STEADY) + DRV_CNT_GET(EI_N_QUIET);
+  d[4] = K0 - KS; d[5] = tPh1; d[6] = tBroad; d[7] = tFast; d[8] = tCont; d[9] = (K1 - K0) - tPh1 - tBroad - tFast - tCont; d[10] = KE - K1;
+  d[11] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned long long)__builtin_amdgcn_s_getreg(63492);
+})
 }
 
 #undef DRV_CNT
@@ -2091,7 +2075,7 @@ DRV_PROF(if (lane == 0 && e < 4096) { unsigned long long* d = g_dbgw + e * 12; c
 // (flipPv: the deferred-vision parity alternates only over steps that run the Partial + deferred pair - a list's length word is cleared by
 //  the deferred launch of the OTHER parity, so a step without an observation buffer must leave the parity alone, as the eager host does)
 extern "C" __global__ void drv_tick_advance_kernel(DrvState S, int flipPv) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) { S.iso[13] = (S.iso[13] + 1) % (3 * (1 << 28)); if (flipPv) S.iso[14] = S.iso[14] ^ 1; }
+  if (threadIdx.x == 0 && blockIdx.x == 0) { S.iso[DRV_ISOW_TICK] = (S.iso[DRV_ISOW_TICK] + 1) % DRV_TICK_WRAP; if (flipPv) S.iso[DRV_ISOW_PV_PAR] = S.iso[DRV_ISOW_PV_PAR] ^ 1; }
 }
 
 extern "C" __global__ void __launch_bounds__(64, DRV_WAVES_PER_SIMD)
@@ -2113,7 +2097,7 @@ extern "C" __global__ void drv_stats_kernel(DrvState S, double* ep_r, double* ep
   int fin = 0, crashed = 0;
   for (int a = 0; a < S.A; ++a) {
     int f = S.flags[(size_t)e * DRV_NB + a];
-    int fi = (f >> 4) & 1, cr = (f >> 5) & 1;
+    int fi = CARF_FIN(f), cr = CARF_CRASHED(f);
     fin += fi && !cr;
     crashed += cr;
     if (ep_r) ep_r[(size_t)e * S.A + a] = S.epr[(size_t)e * 16 + a];
@@ -2192,13 +2176,13 @@ drv_get_states_kernel(DrvState S, const int* __restrict__ idx, int first, unsign
     dynenv_car_state_t& c = T.st.cars[lane];
     c.px = b[BF_PX]; c.py = b[BF_PY]; c.vx = b[BF_VX]; c.vy = b[BF_VY]; c.angle = b[BF_ANG]; c.w = b[BF_W];
     c.dirx = cx[CF_DIRX]; c.diry = cx[CF_DIRY]; c.prevx = cx[CF_PREVX]; c.prevy = cx[CF_PREVY]; c.goalx = cx[CF_GOALX]; c.goaly = cx[CF_GOALY];
-    c.type = fl & 3; c.team = (fl >> 2) & 3; c.finished = (fl >> 4) & 1; c.crashed = (fl >> 5) & 1; c.fric = (fl >> 6) & 1; c.lane_pos = (fl >> 8) & 7;
+    c.type = CARF_TYPE(fl); c.team = CARF_TEAM(fl); c.finished = CARF_FIN(fl); c.crashed = CARF_CRASHED(fl); c.fric = CARF_FRIC(fl); c.lane_pos = CARF_LP(fl);
   }
   if (lane >= DRV_SLOT_PED && lane < DRV_SLOT_PED + nPed) {
     dynenv_ped_state_t& p = T.st.peds[lane - DRV_SLOT_PED];
     p.px = b[BF_PX]; p.py = b[BF_PY]; p.vx = b[BF_VX]; p.vy = b[BF_VY];
-    p.road = fl & 1; p.side = (fl >> 1) & 1; p.dead = (fl >> 2) & 1; p.crossing = (fl >> 3) & 1; p.begin_crossing = (fl >> 4) & 1;
-    p.speed = (fl >> 8) & 15; p.moving = ax;
+    p.road = PEDF_ROAD(fl); p.side = PEDF_SIDE(fl); p.dead = PEDF_DEAD(fl); p.crossing = PEDF_CROSSING(fl); p.begin_crossing = PEDF_BEGIN(fl);
+    p.speed = PEDF_SPEED(fl); p.moving = ax;
   }
   if (lane < nObst) { T.st.obst_x[lane] = ox; T.st.obst_y[lane] = oy; }
   __syncthreads();
@@ -2221,7 +2205,7 @@ drv_set_states_kernel(DrvState S, const int* __restrict__ idx, int first, const 
   __syncthreads();
   const int nPed = uniform_i(T.st.n_peds), nObst = uniform_i(T.st.n_obst);
   if (uniform_i(T.st.n_cars) != A || nPed < 0 || nPed > DRV_MAXP || nObst < 0 || nObst > DRV_MAXO) {
-    if (lane == 0) { if (raise) atomicOr(&S.envi[(size_t)e * EI_COUNT + EI_ERR], 64); if (status) status[k] = 1; }
+    if (lane == 0) { if (raise) atomicOr(&S.envi[(size_t)e * EI_COUNT + EI_ERR], DYNENV_ERRBIT_BLOB); if (status) status[k] = 1; }
     return;
   }
   if (lane < DRV_NB) {

@@ -17,6 +17,11 @@
 #define INTER_NEARBY 1
 #define INTER_OCCLUDE 2
 #define PV_ANGLE_NOISE (DM_PI / 180.0)
+// normalize_obs factors of the Partial row: positions, a rectangle's width and height
+#define PV_NORM_X (5.0 * 2.0 / DRV_W)
+#define PV_NORM_Y (5.0 * 2.0 / DRV_H)
+#define PV_NORM_W (1.0 / 7.5)
+#define PV_NORM_H (1.0 / 15.0)
 
 struct PvBlocker {  // an object as `elem2` of doesInteractPoly: view-blocking interval + the three decisive corners
   double posx, posy, angle2, minA, maxA, p1x, p1y, p2x, p2y, pmx, pmy;
@@ -48,7 +53,6 @@ DE_DEV dm_u32x4 pv_rng(const DrvState& S, uint32_t genv, uint32_t episode, int e
   uint32_t entity = (uint32_t)agent | ((uint32_t)kind << 4) | ((uint32_t)index << 8) | ((uint32_t)block << 16);
   return dm_env_rng(S.seed, genv, episode, DM_RNG_OBS_NOISE, entity, (uint32_t)elapsed);
 }
-DE_DEV double pv_normalize(double pt, double nf, double mean) { return ((pt * nf) - mean) * 2.0 * 1.0; }
 DE_DEV V2 pv_rotated(V2 v, double a) {
   const DevSC sc = dev_sincos_v(a);
   return v2(v.x * sc.c - v.y * sc.s, v.x * sc.s + v.y * sc.c);
@@ -98,7 +102,7 @@ DE_DEV int pv_env(const DrvState& S, PvLds& L, const int e, const int lane, cons
   const bool isBldLane = lane >= DRV_SLOT_BLD && lane < DRV_SLOT_BLD + 4;
   const bool isLaneRow = lane >= 54 && lane < 60;
   const uint64_t carLanes = wave_ballot(isCarLane), pedLanes = wave_ballot(isPedLane), obsLanes = wave_ballot(isObsLane);
-  (void)carLanes;
+  (void)carLanes;  // (unused, yet the unit's emitted code differs without it - tools/device_code_hash.py: it goes in a change that is measured)
 
   int a = aBegin;
 #pragma unroll 1
@@ -110,7 +114,7 @@ PV_PROF(const unsigned long long VT0 = __builtin_amdgcn_s_memtime();)
     for (int i = lane; i < PV_DIM; i += DE_WAVE) row[i] = 0.0f;
     const V2 P = v2(L.px[a], L.py[a]);
     const double ang = L.ang[a];
-    const int typeA = L.flags[a] & 3;
+    const int typeA = CARF_TYPE(L.flags[a]);
 
     // ---- phase 1: detection of my object (isSeenInRadius) --------------------------------------------------
     int seen = SIGHT_NONE;
@@ -132,16 +136,16 @@ PV_PROF(const unsigned long long VT0 = __builtin_amdgcn_s_memtime();)
       if (isCarLane) {
         const int f = L.flags[lane];
         point = v2(L.px[lane], L.py[lane]); oangle = L.ang[lane];
-        hx = C.carHx[f & 3]; hy = C.carHy[f & 3];  // Car.points (h, w): h = length, w = width
-        dw = hy; dh = hx; dfin = CF_FIN(f);
+        hx = C.carHx[CARF_TYPE(f)]; hy = C.carHy[CARF_TYPE(f)];  // Car.points (h, w): h = length, w = width
+        dw = hy; dh = hx; dfin = CARF_FIN(f);
         hasCorners = true;
       } else if (isPedLane) {
         point = v2(L.px[lane], L.py[lane]);
       } else if (isObsLane) {
-        point = v2(L.ox[lane - DRV_SLOT_OBST], L.oy[lane - DRV_SLOT_OBST]); hx = 10.0; hy = 10.0; dw = 10.0; dh = 10.0; hasCorners = true;
+        point = v2(L.ox[lane - DRV_SLOT_OBST], L.oy[lane - DRV_SLOT_OBST]); hx = DRV_OBST_H; hy = DRV_OBST_H; dw = DRV_OBST_H; dh = DRV_OBST_H; hasCorners = true;
       } else {
         const int k = lane - DRV_SLOT_BLD;
-        point = v2((k & 2) ? 1385.0 : 365.0, (k & 1) ? 800.0 : 200.0); hx = 400.0; hy = 225.0; hasCorners = true;
+        point = v2(DRV_BLD_CX(k), DRV_BLD_CY(k)); hx = DRV_BLD_HX; hy = DRV_BLD_HY; hasCorners = true;
         maxD = 20000000.0; distD = 20000000.0;
       }
     }
@@ -482,9 +486,9 @@ PV_PROF(const unsigned long long VT7 = __builtin_amdgcn_s_memtime();)
     if (on_) {                                                                                                            \
       if ((P_) < ((car_) ? PV_LIM_CARS : PV_LIM_OBST)) {                                                                  \
         float* o = row + ((car_) ? PV_OFF_CARS + (P_)*7 : PV_OFF_OBST + (P_)*6);                                          \
-        o[0] = (float)pv_normalize((q_).x, (5.0 * 2.0 / DRV_W), 0.0); o[1] = (float)pv_normalize((q_).y, (5.0 * 2.0 / DRV_H), 0.0); \
+        o[0] = (float)normalize_obs((q_).x, PV_NORM_X, 0.0); o[1] = (float)normalize_obs((q_).y, PV_NORM_Y, 0.0); \
         o[2] = (float)(c_); o[3] = (float)(s_);                                                                           \
-        o[4] = (float)pv_normalize((w_), 1.0 / 7.5, 0.5); o[5] = (float)pv_normalize((h_), 1.0 / 15.0, 0.5);              \
+        o[4] = (float)normalize_obs((w_), PV_NORM_W, 0.5); o[5] = (float)normalize_obs((h_), PV_NORM_H, 0.5);              \
         if (car_) o[6] = (fin_);                                                                                          \
       } else overflow = 1;                                                                                                \
     }                                                                                                                     \
@@ -508,7 +512,7 @@ PV_PROF(const unsigned long long VT7 = __builtin_amdgcn_s_memtime();)
     if (on_) {                                                                                                            \
       if ((P_) < PV_LIM_PEDS) {                                                                                           \
         float* o = row + PV_OFF_PEDS + (P_)*2;                                                                            \
-        o[0] = (float)pv_normalize((q_).x, (5.0 * 2.0 / DRV_W), 0.0); o[1] = (float)pv_normalize((q_).y, (5.0 * 2.0 / DRV_H), 0.0); \
+        o[0] = (float)normalize_obs((q_).x, PV_NORM_X, 0.0); o[1] = (float)normalize_obs((q_).y, PV_NORM_Y, 0.0); \
       } else overflow = 1;                                                                                                \
     }                                                                                                                     \
   } while (0)
@@ -528,12 +532,12 @@ PV_PROF(const unsigned long long VT7 = __builtin_amdgcn_s_memtime();)
     }
     // --- self row + counts
     if (isSelf) {
-      row[0] = (float)pv_normalize(pos.x, (5.0 * 2.0 / DRV_W), 5.0); row[1] = (float)pv_normalize(pos.y, (5.0 * 2.0 / DRV_H), 5.0);
+      row[0] = (float)normalize_obs(pos.x, PV_NORM_X, 5.0); row[1] = (float)normalize_obs(pos.y, PV_NORM_Y, 5.0);
       row[2] = (float)dc; row[3] = (float)ds;
-      row[4] = (float)pv_normalize(C.carHy[typeA], 1.0 / 7.5, 0.5); row[5] = (float)pv_normalize(C.carHx[typeA], 1.0 / 15.0, 0.5);
+      row[4] = (float)normalize_obs(C.carHy[typeA], PV_NORM_W, 0.5); row[5] = (float)normalize_obs(C.carHx[typeA], PV_NORM_H, 0.5);
       const double gx = in.gx, gy = in.gy;  // isSelf: lane == a
-      row[6] = (float)pv_normalize(gx, (5.0 * 2.0 / DRV_W), 5.0); row[7] = (float)pv_normalize(gy, (5.0 * 2.0 / DRV_H), 5.0);
-      row[8] = (float)CF_FIN(L.flags[a]);
+      row[6] = (float)normalize_obs(gx, PV_NORM_X, 5.0); row[7] = (float)normalize_obs(gy, PV_NORM_Y, 5.0);
+      row[8] = (float)CARF_FIN(L.flags[a]);
       row[PV_DIM - 4] = (float)(nOutCars < PV_LIM_CARS ? nOutCars : PV_LIM_CARS);
       row[PV_DIM - 3] = (float)(nOutObst < PV_LIM_OBST ? nOutObst : PV_LIM_OBST);
       row[PV_DIM - 2] = (float)(nOutPeds < PV_LIM_PEDS ? nOutPeds : PV_LIM_PEDS);
@@ -545,7 +549,7 @@ PV_PROF(const unsigned long long VT7 = __builtin_amdgcn_s_memtime();)
     __syncthreads();
 PV_PROF(if (lane == 0) { const unsigned long long VT8 = __builtin_amdgcn_s_memtime(); atomicAdd(&g_pvprof[(e & 4095) * 16 + 0], VT1 - VT0); atomicAdd(&g_pvprof[(e & 4095) * 16 + 1], VT2 - VT1); atomicAdd(&g_pvprof[(e & 4095) * 16 + 2], VT3 - VT2); atomicAdd(&g_pvprof[(e & 4095) * 16 + 3], VT4 - VT3); atomicAdd(&g_pvprof[(e & 4095) * 16 + 4], VT5 - VT4); atomicAdd(&g_pvprof[(e & 4095) * 16 + 5], VT6 - VT5); atomicAdd(&g_pvprof[(e & 4095) * 16 + 6], VT7 - VT6); atomicAdd(&g_pvprof[(e & 4095) * 16 + 7], VT8 - VT7); atomicAdd(&g_pvprof[(e & 4095) * 16 + 8], 1ull); })
   }
-  if (wave_ballot(overflow != 0) && lane == 0) envi[EI_ERR] = envi[EI_ERR] | 8;  // rows dropped (dynenv.h, error bit 3)
+  if (wave_ballot(overflow != 0) && lane == 0) envi[EI_ERR] = envi[EI_ERR] | DYNENV_ERRBIT_ROWS_DROPPED;
   return a;
 }
 
@@ -599,10 +603,10 @@ extern "C" __global__ void __launch_bounds__(64, 4)
 drv_partial_obs_deferred_kernel(DrvState S, int noiseType, double magn, float* __restrict__ obs) {
   const int lane = threadIdx.x, A = S.A;
   const int pv = drv_launch_pv(S);
-  const int* list = S.pvq + 32 + pv * S.E;
-  int n = uniform_i(S.pvq[16 * pv]);
+  const int* list = S.pvq + DRV_PVQ_LIST(pv, S.E);
+  int n = uniform_i(S.pvq[DRV_PVQ_LEN(pv)]);
   n = n < S.E ? n : S.E;  // (longer only if the length was not cleared: see the append in drv_step_body)
-  if (blockIdx.x == 0 && lane == 0) S.pvq[16 * (pv ^ 1)] = 0;  // the next step's list starts empty (nobody reads or fills it now)
+  if (blockIdx.x == 0 && lane == 0) S.pvq[DRV_PVQ_LEN(pv ^ 1)] = 0;  // the next step's list starts empty (nobody reads or fills it now)
   // item j = (agent j / n, listed environment j % n): neighbouring blocks work on different environments
 #pragma unroll 1
   for (int j = blockIdx.x; j < n * A; j += gridDim.x) {

@@ -37,8 +37,6 @@ static double moment_for_box(double m, double hx, double hy) {  // cpMomentForPo
   return (m * sum1) / (6.0 * sum2);
 }
 
-static double norm_obs_host(double pt, double nf, double mean) { return ((pt * nf) - mean) * 2.0 * 1.0; }
-
 static void build_consts(DrvConst& c) {
   memset(&c, 0, sizeof(c));
   road_init_host(c.roads[0], 2, 35.0, v2(875.0, 0.0), v2(875.0, 1000.0));  // DrivingEnvironment.py:110-115
@@ -52,10 +50,10 @@ static void build_consts(DrvConst& c) {
       int idx = ((i - n) % cnt + cnt) % cnt;
       double s = (double)(idx - n) * l.width;
       V2 a = vadd(l.p0, vmul(l.normal, s)), b = vadd(l.p1, vmul(l.normal, s));
-      c.laneRows[row * 5 + 0] = (float)norm_obs_host(a.x, 0.5 / (DRV_W + 100.0), 0.0);
-      c.laneRows[row * 5 + 1] = (float)norm_obs_host(a.y, 0.5 / (DRV_H + 100.0), 0.0);
-      c.laneRows[row * 5 + 2] = (float)norm_obs_host(b.x, 0.5 / (DRV_W + 100.0), 0.0);
-      c.laneRows[row * 5 + 3] = (float)norm_obs_host(b.y, 0.5 / (DRV_H + 100.0), 0.0);
+      c.laneRows[row * 5 + 0] = (float)normalize_obs(a.x, STD_NORM_X, 0.0);
+      c.laneRows[row * 5 + 1] = (float)normalize_obs(a.y, STD_NORM_Y, 0.0);
+      c.laneRows[row * 5 + 2] = (float)normalize_obs(b.x, STD_NORM_X, 0.0);
+      c.laneRows[row * 5 + 3] = (float)normalize_obs(b.y, STD_NORM_Y, 0.0);
       c.laneRows[row * 5 + 4] = (float)((i == n || i == -n) ? 1 : (i == 0 ? -1 : 0));
       ++row;
     }
@@ -67,7 +65,7 @@ static void build_consts(DrvConst& c) {
     c.carInertia[t] = moment_for_box(masses[t], lengths[t], widths[t]);
   }
   c.pedMass = 90.0;  // Pedestrian.py:11-14
-  c.pedInertia = 90.0 * (0.5 * (0.0 * 0.0 + 5.0 * 5.0) + 0.0);
+  c.pedInertia = 90.0 * (0.5 * (0.0 * 0.0 + DRV_PED_R * DRV_PED_R) + 0.0);
 }
 
 // the device code spells the road constants as literals (RoadK<R>): they must equal the computed ones bit for bit
@@ -120,7 +118,7 @@ struct HOST_LOCAL DrvHandle final : dynenv {
   // ... at creation and behind a checkpoint load, where both deferred-observation lists are emptied as well
   int iso_reset() {
     if (iso_clear(false, nullptr)) return DYNENV_ERR_HIP;
-    HIP_OK(hipMemset(S.pvq, 0, sizeof(int) * 32));
+    HIP_OK(hipMemset(S.pvq, 0, sizeof(int) * DRV_PVQ_IDS));
     S.pv_par = 0;
     return 0;
   }
@@ -150,7 +148,7 @@ struct HOST_LOCAL DrvHandle final : dynenv {
     rc |= alloc(&S.iso, DRV_ISO_WORDS, SCRATCH);
     rc |= alloc(&S.iso_done, E, SCRATCH);
     rc |= alloc(&S.iso_hw, 2 * 4 * DRV_ISO_GROUPS, SCRATCH);
-    rc |= alloc(&S.pvq, 32 + 2 * (size_t)S.E, SCRATCH);
+    rc |= alloc(&S.pvq, DRV_PVQ_WORDS((size_t)S.E), SCRATCH);
     if (rc) return DYNENV_ERR_HIP;
     rows.err = S.envi; rows.errStride = EI_COUNT; rows.errIndex = EI_ERR;
     {
@@ -248,12 +246,12 @@ struct HOST_LOCAL DrvHandle final : dynenv {
           S.iso_on = 0; iso_paused_until = steps + ISO_PAUSE_STEPS; iso_pauses += 1;
         } else {
           iso_last_invalid = seen;
-          HIP_OK(hipMemcpyAsync(iso_seen, S.iso + 11, sizeof(int), hipMemcpyDeviceToHost, st));
+          HIP_OK(hipMemcpyAsync(iso_seen, S.iso + DRV_ISOW_INVALID, sizeof(int), hipMemcpyDeviceToHost, st));
         }
       }
     }
     const unsigned stepGrid = S.iso_on == 1 ? 4u * DRV_ISO_GROUPS + 3u * DRV_ISO_MAX + 1u /* one residency round + spares + the placement validator */ : (unsigned)S.E;
-    if (!S.tick_src) S.tick = (S.tick + 1) % (3 * (1 << 28));  // (wraps at a multiple of 3: the three isolation lists keep rotating in order)
+    if (!S.tick_src) S.tick = (S.tick + 1) % DRV_TICK_WRAP;
     if (partial && obs)
     {
       if (!S.tick_src) S.pv_par ^= 1;
@@ -294,12 +292,12 @@ struct HOST_LOCAL DrvHandle final : dynenv {
     {  // SIMD isolation: how many environments the next step isolates, placeholders that gave up waiting (should stay 0)
       int iso[DRV_ISO_HDR];
       HIP_OK(hipMemcpy(iso, S.iso, sizeof(iso), hipMemcpyDeviceToHost));
-      const int nxt = ((S.tick_src ? iso[13] : S.tick) + 1) % 3, k = iso[nxt];
+      const int nxt = ((S.tick_src ? iso[DRV_ISOW_TICK] : S.tick) + 1) % 3, k = iso[DRV_ISOW_LEN + nxt];
       const int cap = S.iso_on == 1 ? DRV_ISO_MAX : DRV_ISO_LIST;
-      out4[10] = S.iso_on ? (k < cap ? k : cap) : -1; out4[11] = iso[7];
+      out4[10] = S.iso_on ? (k < cap ? k : cap) : -1; out4[11] = iso[DRV_ISOW_GAVE_UP];
       // out[12]: scheduling mode (0 off, 1 SIMD isolation, 2 slow environments first, 3 timing only: Partial); out[13]: 1 = the next step found the block ->
       // SIMD placement validated (mode 1 only; 0 = isolation is holding off); out[14]: launches whose placement did not validate
-      out4[12] = iso_cfg; out4[13] = S.iso_on == 1 ? iso[8 + nxt] : (iso_cfg == 1 ? 0 : -1); out4[14] = iso[11];
+      out4[12] = iso_cfg; out4[13] = S.iso_on == 1 ? iso[DRV_ISOW_VALID + nxt] : (iso_cfg == 1 ? 0 : -1); out4[14] = iso[DRV_ISOW_INVALID];
       out4[15] = iso_pauses;  // times the host dropped to the plain launch because the placement kept failing to validate
     }
 #ifdef DRV_PROFILE
@@ -317,7 +315,7 @@ struct HOST_LOCAL DrvHandle final : dynenv {
     HIP_OK(hipDeviceSynchronize());
     const int m = n < 4 * DRV_ISO_GROUPS ? n : 4 * DRV_ISO_GROUPS;
     int tick = S.tick;
-    if (S.tick_src) HIP_OK(hipMemcpy(&tick, S.iso + 13, sizeof(int), hipMemcpyDeviceToHost));
+    if (S.tick_src) HIP_OK(hipMemcpy(&tick, S.iso + DRV_ISOW_TICK, sizeof(int), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(out, S.iso_hw + (size_t)(tick & 1) * (4 * DRV_ISO_GROUPS), sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
     return m;
   }

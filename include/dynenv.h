@@ -333,6 +333,13 @@ int dynenv_sync(dynenv_t* h, void* stream);
  * carry the handle's layout tag, and was NOT written; sticky on that environment until the next reset or the next valid set_state /
  * set_states / set_exact of it (a valid exact blob brings its own error word, saved with the rest); the host mirror's step() raises on it.
  * Synchronises the device. */
+#define DYNENV_ERRBIT_OVERFLOW 1      /* bit 0: a contact or a candidate pair was dropped */
+#define DYNENV_ERRBIT_ACTION 2        /* bit 1: an action outside the action space */
+#define DYNENV_ERRBIT_DEFER_LIST 4    /* bit 2: Driving Partial, the deferred-observation list was full */
+#define DYNENV_ERRBIT_ROWS_DROPPED 8  /* bit 3: Partial observation rows beyond a list's capacity */
+#define DYNENV_ERRBIT_DEGENERATE 16   /* bit 4: RoboCup, capsule cores collinear or touching */
+#define DYNENV_ERRBIT_NONFINITE 32    /* bit 5: RoboCup, a non-finite velocity or impulse in a solve */
+#define DYNENV_ERRBIT_BLOB 64         /* bit 6: a state blob that did not fit was not written */
 int dynenv_error_flags(dynenv_t* h, int32_t* out);
 /* The per-environment error words themselves (the bits above): flags_dev int32 [E], ordered on `stream`, no synchronisation - to
  * name the environment a sticky bit belongs to and repair only that one. */
