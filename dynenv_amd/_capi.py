@@ -72,6 +72,8 @@ FLAG_RANDOM_INIT, FLAG_DETERMINISTIC_TURN, FLAG_CAN_FALL, FLAG_USE_OBS_REWARDS, 
 
 ARR_MAX_TYPES = 4
 ARR_COUNT_CONST, ARR_COUNT_ENV, ARR_COUNT_ROW = 0, 1, 2
+ARR_F32, ARR_BF16, ARR_F16 = 0, 1, 2  # DYNENV_ARR_F32 / _BF16 / _F16: the element types of dynenv_arrange_*_as
+ERR_UNSUPPORTED = -4
 
 
 class ArrType(C.Structure):  # dynenv_arr_type_t
@@ -142,6 +144,10 @@ SIGNATURES = {
     "dynenv_arrange_fixed_pad": (C.c_int, [C.POINTER(vp), vp, C.POINTER(i32), i32, i32, i32, i32, i32, vp, vp]),
     "dynenv_arrange_fixed_pad_backward": (C.c_int, [vp, vp, C.POINTER(i32), i32, i32, i32, i32, i32, C.POINTER(vp), vp]),
     "dynenv_math_probe": (C.c_int, [i32, vp, i32, vp, i32]),
+    "dynenv_arrange_pad_as": (C.c_int, [C.POINTER(vp), i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
+    "dynenv_arrange_pad_backward_as": (C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp), i32, vp]),
+    "dynenv_arrange_fixed_pad_as": (C.c_int, [C.POINTER(vp), i32, vp, C.POINTER(i32), i32, i32, i32, i32, i32, vp, i32, vp]),
+    "dynenv_arrange_fixed_pad_backward_as": (C.c_int, [vp, i32, vp, C.POINTER(i32), i32, i32, i32, i32, i32, C.POINTER(vp), i32, vp]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -15,6 +15,10 @@ the embedding blocks train through it (a torch.autograd.Function over `dynenv_ar
 Two modes.  The default pads to the largest object count of each batch, as the reference does, and so has to wait for the device to
 learn the shapes.  `fixed=...` works at capacities the caller fixes once (`dynenv_arrange_fixed_*`, csrc/arranger_fixed_kernels.hip):
 the same layout in the leading slots, zeros behind, no host round trip, capturable into a graph.
+
+In both modes `padded_dtype=torch.bfloat16` (or float16) writes the padded tensor in that type, for a network under torch.autocast
+(`dynenv_arrange_*_as`, csrc/arranger_dtype_kernels.hip): float32 embeddings are converted on the way (round to nearest even), embeddings
+already of that type are copied bit for bit, and the backward hands every embedding a gradient of its own type.
 """
 import ctypes as C
 import os
@@ -35,14 +39,16 @@ class GpuInOutArranger(object):
     """Same role and call sequence as the reference's InOutArranger(nObjectTypes, nPlayers, nTime) (models.py:208-216);
     `nPlayers` is E*A as in InputLayer (:283).  `types` describes where each object type lives in an observation row."""
 
-    def __init__(self, types, nEnvs, nAgents, nTime, obs_dim, device=None, fixed=None):
+    def __init__(self, types, nEnvs, nAgents, nTime, obs_dim, device=None, fixed=None, padded_dtype=None):
         """fixed=None: the reference's shapes - every call pads to the largest object count of ITS batch, which the host has to wait
         for (dynenv_arrange_plan synchronises).  fixed=True or fixed=dict(max_count=M, rows=[...]): the fixed-shape mode
         (dynenv_arrange_fixed_*): inputs[i] always has rows[i] rows per (time, player) - rows past the count are zero - and the
         padded tensor always M slots; True means rows = the types' capacities and M = their sum.  Nothing is copied to the host
         and nothing waited for, so the calls can be captured into a graph.  Objects beyond rows[i] or M are dropped, earlier types
         winning, and counted per type in the persistent int32 tensor `self.dropped` (added to by every call; nothing here reads or
-        zeroes it)."""
+        zeroes it).
+        padded_dtype=None: `padded` is float32, the code path it always was.  torch.bfloat16 / torch.float16, in either mode: `padded` is
+        written in that type (_rearrange_outputs_as); the embedding width must then be a multiple of 8."""
         import torch
         if not torch.cuda.is_available():
             raise _capi.DynEnvError("dynenv_amd needs an MI355X (HIP device); there is no CPU fallback")
@@ -60,6 +66,9 @@ class GpuInOutArranger(object):
         n = int(self._lib.dynenv_arrange_scratch_ints(self.E, self.nTime, self.A, self.nObjectTypes))
         self._scratch = torch.empty((n + 2,), dtype=torch.int32, device=self.device)
         self.feats = [int(t.feat) for t in types]
+        if padded_dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError("padded_dtype is None (float32), torch.bfloat16 or torch.float16, got %r" % (padded_dtype,))
+        self.padded_dtype = padded_dtype
         self.fixed = fixed is not None and fixed is not False
         if self.fixed:
             caps = [int(t.cap) for t in types]
@@ -144,6 +153,8 @@ class GpuInOutArranger(object):
                 raise ValueError("rearrange_outputs: outs[%d] is None but object type %d has rows[%d] = %d" % (i, i, i, self.rows[i]))
             if o is not None and tuple(o.shape) != (TP * self.rows[i], F):
                 raise ValueError("rearrange_outputs: outs[%d] is %s, not %s" % (i, tuple(o.shape), (TP * self.rows[i], F)))
+        if self.padded_dtype is not None:
+            return self._rearrange_outputs_as(outs, counts, None, self.max_count, F), [mask[t].bool() for t in range(self.nTime)]
         # float32 and contiguous inside the Function; torch differentiates a cast or a copy made out here
         outs = [o if o is None else (o if o.dtype == torch.float32 else o.float()).contiguous() for o in outs]
         if F % 4 or any(o is not None and o.data_ptr() % 16 for o in outs):
@@ -219,6 +230,14 @@ class GpuInOutArranger(object):
             if o is None and int(slots[i].shape[0]):
                 raise ValueError("rearrange_outputs: outs[%d] is None but object type %d has %d objects"
                                  % (i, i, int(slots[i].shape[0])))
+        if self.padded_dtype is not None:
+            F = next((int(o.shape[1]) for o in outs if o is not None), None)
+            if F is None:
+                raise ValueError("rearrange_outputs: every output is None")
+            for i, o in enumerate(outs):   # (the kernel takes the rows' starts from the plan: the row counts are the plan's)
+                if o is not None and tuple(o.shape) != (int(slots[i].shape[0]), F):
+                    raise ValueError("rearrange_outputs: outs[%d] is %s, not %s" % (i, tuple(o.shape), (int(slots[i].shape[0]), F)))
+            return self._rearrange_outputs_as(outs, *plan[:3], F), [mask[t].bool() for t in range(self.nTime)]
         if torch.is_grad_enabled() and any(o is not None and o.requires_grad for o in outs):
             # float32 inside the Function; another dtype is cast out here, where torch differentiates the cast
             outs = [o if o is None or o.dtype == torch.float32 else o.float() for o in outs]
@@ -254,6 +273,72 @@ class GpuInOutArranger(object):
                 _capi.check(self._lib.dynenv_arrange_scatter(_capi.ptr(out), _capi.ptr(slots[i]), int(out.shape[0]), F,
                                                              _capi.ptr(padded), self._stream()), "dynenv_arrange_scatter")
         return padded
+
+    # ---- padded_dtype = bfloat16 / float16, both modes: `base` is the plan's in the default mode and None in the fixed one ----
+    _DTYPE_CODES = {"torch.float32": _capi.ARR_F32, "torch.bfloat16": _capi.ARR_BF16, "torch.float16": _capi.ARR_F16}
+
+    def _rearrange_outputs_as(self, outs, counts, base, max_count, F):
+        """rearrange_outputs with a 16-bit padded tensor (shapes already checked).  Embeddings that are all float32 are converted by the
+        kernel; embeddings that are all of padded_dtype are copied bit for bit; anything else is cast to float32 out here, where torch
+        differentiates the cast.  One launch in either mode - the default mode has no scatter route here and DYNENV_ARR_DENSE_MIN is not
+        consulted.  Differentiable: every embedding gets a gradient of its own dtype."""
+        torch = self._torch
+        if not all(o is None or o.dtype == self.padded_dtype for o in outs):
+            outs = [o if o is None or o.dtype == torch.float32 else o.float() for o in outs]
+        outs = [o if o is None else o.contiguous() for o in outs]
+        if F % 8 or any(o is not None and o.numel() and o.data_ptr() % 16 for o in outs):
+            raise _capi.DynEnvError("a %s padded tensor needs an embedding width that is a multiple of 8 (got %d) and 16-byte aligned embeddings: "
+                                    "a 16-byte unit of it is 8 elements, and there is no per-row fallback; use padded_dtype=None"
+                                    % (self.padded_dtype, F))
+        if torch.is_grad_enabled() and any(o is not None and o.requires_grad for o in outs):
+            return _arrange_as_function().apply(self, (counts, base, max_count), *outs)
+        return self._pad_as(outs, counts, base, max_count, F)
+
+    def _pad_as(self, outs, counts, base, max_count, F):
+        """one launch: every element of the padded tensor [T, max_count, P, F] of padded_dtype is written"""
+        padded = self._torch.empty((self.nTime, max_count, self.nPlayers, F), dtype=self.padded_dtype, device=self.device)
+        if max_count == 0:
+            return padded
+        emb_code = self._DTYPE_CODES[str(next(o.dtype for o in outs if o is not None))]
+        code = self._DTYPE_CODES[str(self.padded_dtype)]
+        if base is None:
+            _capi.check(self._lib.dynenv_arrange_fixed_pad_as(self._type_ptrs(outs), emb_code, _capi.ptr(counts), self._rows_c, self.nObjectTypes,
+                                                              self.nTime, self.nPlayers, max_count, F, _capi.ptr(padded), code, self._stream()),
+                        "dynenv_arrange_fixed_pad_as")
+        else:
+            _capi.check(self._lib.dynenv_arrange_pad_as(self._type_ptrs(outs), emb_code, _capi.ptr(counts), _capi.ptr(base), self.nObjectTypes,
+                                                        self.nTime, self.nPlayers, max_count, F, _capi.ptr(padded), code, self._stream()),
+                        "dynenv_arrange_pad_as")
+        return padded
+
+    def _unpad_as(self, grad, rows, emb_dtype, F, wanted, counts, base, max_count):
+        """the backward of _pad_as, one launch: grad [T, max_count, P, F] -> per type [rows[i], F] of the embeddings' dtype - widened exactly
+        to float32 or copied bit for bit - None where rows[i] is None or the gradient is not wanted.  Every row is written: the fixed
+        mode's rows behind the kept ones are zero."""
+        torch = self._torch
+        g = grad.contiguous()   # (an attention layer often hands back a permuted view)
+        if g.dtype != self.padded_dtype:
+            g = g.to(self.padded_dtype)
+        if g.data_ptr() % 16:
+            g = g.clone()
+        assert tuple(g.shape) == (self.nTime, max_count, self.nPlayers, F), tuple(g.shape)
+        make = torch.zeros if max_count == 0 else torch.empty   # (M == 0: nothing is launched and every gradient row is zero)
+        grads = [make((n, F), dtype=emb_dtype, device=g.device) if (n is not None and w) else None for n, w in zip(rows, wanted)]
+        if base is not None:
+            self.last_backward = None
+        if max_count == 0 or not any(ge is not None and ge.shape[0] for ge in grads):
+            return grads
+        emb_code, code = self._DTYPE_CODES[str(emb_dtype)], self._DTYPE_CODES[str(self.padded_dtype)]
+        if base is None:
+            _capi.check(self._lib.dynenv_arrange_fixed_pad_backward_as(_capi.ptr(g), code, _capi.ptr(counts), self._rows_c, self.nObjectTypes,
+                                                                       self.nTime, self.nPlayers, max_count, F, self._type_ptrs(grads),
+                                                                       emb_code, self._stream()), "dynenv_arrange_fixed_pad_backward_as")
+        else:
+            _capi.check(self._lib.dynenv_arrange_pad_backward_as(_capi.ptr(g), code, _capi.ptr(counts), _capi.ptr(base), self.nObjectTypes,
+                                                                 self.nTime, self.nPlayers, max_count, F, self._type_ptrs(grads), emb_code,
+                                                                 self._stream()), "dynenv_arrange_pad_backward_as")
+            self.last_backward = "fused"
+        return grads
 
     def _unpad(self, grad, rows, F, wanted, counts, base, max_count, slots):
         """the backward of _pad: grad [T, maxCount, P, F] -> per type float32 [N_i, F] (None where rows[i] is None or the gradient
@@ -351,6 +436,32 @@ def _arrange_fixed_function():
     return _lazy["fixed_fn"]
 
 
+def _arrange_as_function():
+    if "as_fn" not in _lazy:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class ArrangeOutputsAs(torch.autograd.Function):
+            """padded = arranger._pad_as(outs, plan) in the arranger's padded_dtype; d padded / d outs[i] = arranger._unpad_as, in outs[i]'s own
+            dtype.  plan = (counts, base, max_count) of the forward call, base None in the fixed mode."""
+
+            @staticmethod
+            def forward(ctx, arr, plan, *outs):
+                ctx.arr, ctx.plan = arr, plan
+                ctx.rows = [None if o is None else int(o.shape[0]) for o in outs]
+                first = next(o for o in outs if o is not None)
+                ctx.F, ctx.emb_dtype = int(first.shape[1]), first.dtype
+                return arr._pad_as(outs, *plan, ctx.F)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad):
+                return (None, None) + tuple(ctx.arr._unpad_as(grad, ctx.rows, ctx.emb_dtype, ctx.F, ctx.needs_input_grad[2:], *ctx.plan))
+
+        _lazy["as_fn"] = ArrangeOutputsAs
+    return _lazy["as_fn"]
+
+
 def _input_layer_class():
     if "layer" not in _lazy:
         import torch
@@ -370,14 +481,19 @@ def _input_layer_class():
             rows[i] == 0 contributes None.  CAVEAT: the blocks also see the all-zero rows behind each player's objects (their output is
             discarded and their gradient is zero), so they must be ROW-WISE - Linear, LayerNorm, activations, as the reference's
             EmbedBlock; a block that mixes rows (BatchNorm in training mode, attention across rows) would let the zero rows leak into
-            the real ones."""
+            the real ones.
 
-            def __init__(self, blocks, types, nEnvs, nAgents, nTime, obs_dim, fixed=None):
+            padded_dtype=torch.bfloat16 / torch.float16 (GpuInOutArranger), in either mode: `padded` comes out in that type - what a
+            network under torch.autocast reads - from float32 blocks (an EmbedBlock ends in a LayerNorm: float32 under autocast) or from
+            blocks that already return it; the blocks' parameters get the gradients they would get through a float32 padded tensor cast
+            to that type."""
+
+            def __init__(self, blocks, types, nEnvs, nAgents, nTime, obs_dim, fixed=None, padded_dtype=None):
                 super().__init__()
                 if len(blocks) != len(types):
                     raise ValueError("GpuInputLayer: %d blocks for %d object types" % (len(blocks), len(types)))
                 self.blocks = blocks if isinstance(blocks, torch.nn.ModuleList) else torch.nn.ModuleList(blocks)
-                self.arranger = GpuInOutArranger(types, nEnvs, nAgents, nTime, obs_dim, fixed=fixed)
+                self.arranger = GpuInOutArranger(types, nEnvs, nAgents, nTime, obs_dim, fixed=fixed, padded_dtype=padded_dtype)
 
             def forward(self, obs, count_env=None):
                 inputs, countArr = self.arranger.rearrange_inputs(obs, count_env)

@@ -502,6 +502,59 @@ int dynenv_arrange_fixed_pad_backward(const float* grad_padded_dev, const int32_
                                       int32_t n_types, int32_t T, int32_t P, int32_t max_count, int32_t F,
                                       float* const* grad_emb_dev, void* stream);
 
+/* ---- the padded tensor in a 16-BIT type.  A network under torch.autocast reads the padded tensor in bf16 (or fp16): the four calls
+ * below are dynenv_arrange_pad / _pad_backward / _fixed_pad / _fixed_pad_backward with an element type for the per-type buffers
+ * (emb_dtype) and one for the padded tensor or its gradient (padded_dtype).  Layout, slots, counts, NULL entries and clamping are
+ * those of the call each mirrors, element for element; only the element types differ.  Supported pairs (emb_dtype, padded_dtype):
+ *   (F32, BF16), (F32, F16)    the forward converts, the backward widens to float32 rows;
+ *   (BF16, BF16), (F16, F16)   a bit copy both ways;
+ *   (F32, F32)                 forwarded to the call it mirrors;
+ *   anything else              DYNENV_ERR_UNSUPPORTED.
+ * Conversion contract, the same on every path: float32 -> 16 bit is IEEE round to nearest, ties to even - overflow to infinity, fp16
+ * subnormal results, underflow to a signed zero, +-0 and +-inf unchanged - so it is bit for bit what torch's CPU `.to(dtype)` gives for
+ * every non-NaN input; a NaN stays a NaN, its payload is not part of the contract.  16 bit -> float32 is exact for every bit pattern,
+ * fp16 subnormals included.  Padding is +0.0 (all-zero bits).
+ * With a 16-bit padded tensor F must be a multiple of 8 (a 16-byte unit of the padded tensor is 8 elements) and EVERY buffer 16-byte
+ * aligned; there is no per-row fallback.
+ * Errors, DYNENV_ERR_ARG, all reported before a device is looked for: a NULL padded / grad_padded, counts_dev, base_dev / rows or
+ * per-type pointer array; n_types outside 1..DYNENV_ARR_MAX_TYPES; T < 1, P < 1, max_count < 0; rows[i] < 0 (fixed mode); a dtype
+ * outside 0..2; F < 8 or F & 7 with a 16-bit padded tensor (F < 4 or F & 3 with a float32 one); T > 65535, P * F / 8 (or / 4) >= 2^31,
+ * and in the fixed mode T * P > 2^30 (the launch limits); the padded tensor or a per-type buffer not 16-byte aligned.  Then an
+ * unsupported pair: DYNENV_ERR_UNSUPPORTED, also before the device.  max_count == 0 launches nothing and returns DYNENV_OK. */
+#define DYNENV_ARR_F32 0
+#define DYNENV_ARR_BF16 1
+#define DYNENV_ARR_F16 2
+/* dynenv_arrange_pad in these types (rearrange_outputs, models.py:252-274, catAndPad :147-180), one launch: padded_dev
+ * [T][max_count][P][F] of padded_dtype, EVERY element written - the embedding of the object that owns the slot, converted by the
+ * contract above, or +0.0; emb_dev[i] is [N_i][F] of emb_dtype (NULL for a type without objects: zeros in its slots).  Errors: the
+ * list above (DYNENV_ERR_ARG, then DYNENV_ERR_UNSUPPORTED, before a device is looked for). */
+int dynenv_arrange_pad_as(const void* const* emb_dev, int32_t emb_dtype, const int32_t* counts_dev, const int32_t* base_dev,
+                          int32_t n_types, int32_t T, int32_t P, int32_t max_count, int32_t F, void* padded_dev,
+                          int32_t padded_dtype, void* stream);
+/* dynenv_arrange_pad_backward in these types (autograd's derivative of catAndPad, models.py:147-180), one launch:
+ * grad_emb_dev[i][base[i][t][p] + k][:] = grad_padded_dev[t][j][p][:], widened exactly to float32 or bit-copied; grad_padded_dev is
+ * [T][max_count][P][F] of padded_dtype, grad_emb_dev[i] [N_i][F] of emb_dtype.  Every row of every non-NULL grad_emb_dev[i] is written
+ * exactly once; a NULL entry is stepped over; padding slots are never read.  Errors: the list above (DYNENV_ERR_ARG, then
+ * DYNENV_ERR_UNSUPPORTED, before a device is looked for). */
+int dynenv_arrange_pad_backward_as(const void* grad_padded_dev, int32_t padded_dtype, const int32_t* counts_dev,
+                                   const int32_t* base_dev, int32_t n_types, int32_t T, int32_t P, int32_t max_count, int32_t F,
+                                   void* const* grad_emb_dev, int32_t emb_dtype, void* stream);
+/* dynenv_arrange_fixed_pad in these types (rearrange_outputs, models.py:252-274, catAndPad :147-180), one launch, capturable:
+ * padded_dev [T][M][P][F] of padded_dtype, every element written; emb_dev[i] is [T*P*rows[i]][F] of emb_dtype, a NULL entry writes
+ * zeros in its slots; the conversion is the contract above.  Errors: the list above (DYNENV_ERR_ARG, then DYNENV_ERR_UNSUPPORTED,
+ * before a device is looked for); every buffer 16-byte aligned. */
+int dynenv_arrange_fixed_pad_as(const void* const* emb_dev, int32_t emb_dtype, const int32_t* counts_dev, const int32_t* rows,
+                                int32_t n_types, int32_t T, int32_t P, int32_t max_count, int32_t F, void* padded_dev,
+                                int32_t padded_dtype, void* stream);
+/* dynenv_arrange_fixed_pad_backward in these types (models.py:147-180), one launch, capturable: grad_emb_dev[i][tp*rows[i] + r][:] =
+ * grad_padded_dev[t][j][p][:] for r < k_i, widened exactly or bit-copied, and +0.0 in the rows behind the kept ones.  Every row of
+ * every non-NULL grad_emb_dev[i] ([T*P*rows[i]][F] of emb_dtype) is written exactly once; a NULL entry is stepped over; padding
+ * slots of grad_padded_dev are never read.  Errors: the list above (DYNENV_ERR_ARG, then DYNENV_ERR_UNSUPPORTED, before a device is
+ * looked for). */
+int dynenv_arrange_fixed_pad_backward_as(const void* grad_padded_dev, int32_t padded_dtype, const int32_t* counts_dev,
+                                         const int32_t* rows, int32_t n_types, int32_t T, int32_t P, int32_t max_count, int32_t F,
+                                         void* const* grad_emb_dev, int32_t emb_dtype, void* stream);
+
 
 /* Device self-test of the deterministic math header: evaluates sincos/atan2/sqrt/div on n host-provided doubles and
  * returns the raw results so tests can compare them bit-for-bit with the host evaluation. out: [n,5]. */

@@ -6,7 +6,12 @@ bounded sample.  Usage (GPU box):  python tools/bench_arranger.py [--envs 4096] 
 --backward adds, from the same run and on the same plan: the backward of rearrange_outputs (GpuInOutArranger._unpad: the fused HIP
 kernel), the torch composition a user would write without it (per type G.reshape(-1, F).index_select(0, slot_i)) and the forward,
 each as the median over --reps of HIP-event timings of --inner back-to-back calls, the three taking turns inside every repetition;
-algorithmic bytes of the backward are 2 * n_obj * F * 4 (every gradient row read once and written once) plus counts and bases."""
+algorithmic bytes of the backward are 2 * n_obj * F * 4 (every gradient row read once and written once) plus counts and bases.
+
+--padded-dtype bf16|f16 adds, from the same run and on the same plan, the padded tensor in that type (GpuInOutArranger(padded_dtype=...))
+beside the float32 one: the float32 leg, the converting leg (float32 embeddings) and the same-type leg (embeddings already in that type;
+--emb-dtype keeps one of the two), forward only or, with --backward, forward and backward, the legs taking turns inside every
+repetition; per leg the device time (median, min .. max over --reps), the bytes moved and its time relative to the float32 leg."""
 import argparse
 import json
 import os
@@ -65,6 +70,60 @@ def backward_leg(torch, arr, outs, countArr, padded, args, plan_bytes):
     return out
 
 
+def dtype_legs(torch, GpuInOutArranger, shape, countArr, n_obj, args, plan_bytes):
+    """forward (and backward) of rearrange_outputs with a float32 and with a 16-bit padded tensor on one plan: {leg: {forward, backward}}"""
+    import statistics
+    F = args.feat
+    tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+    size = {"f32": 4, "bf16": 2, "f16": 2}
+    pk = args.padded_dtype
+    emb_kinds = [args.emb_dtype] if args.emb_dtype else ["f32", pk]
+    if any(k not in ("f32", pk) for k in emb_kinds):
+        raise SystemExit("--emb-dtype is f32 or the --padded-dtype")
+    pairs = [("f32", "f32")] + [(k, pk) for k in emb_kinds]
+    arrs = {"f32": GpuInOutArranger(*shape), pk: GpuInOutArranger(*shape, padded_dtype=tdt[pk])}
+    plan = arrs["f32"]._plan_of(countArr)
+    counts, base, max_count = plan[:3]
+    base32 = [torch.randn((n, F), device="cuda") for n in n_obj]
+    wanted = [True] * len(n_obj)
+    legs, nbytes = {}, {}
+    with torch.no_grad():
+        for ek, pd in pairs:
+            arr = arrs[pd]
+            outs = [o.to(tdt[ek]) for o in base32]
+            G = torch.randn((arr.nTime, max_count, arr.nPlayers, F), device="cuda").to(tdt[pd])
+            name = "%s -> %s" % (ek, pd)
+            legs[name, "forward"] = (lambda arr=arr, outs=outs: arr.rearrange_outputs(outs, countArr))
+            nbytes[name, "forward"] = sum(n_obj) * F * size[ek] + G.numel() * size[pd] + plan_bytes
+            if args.backward:
+                if pd == "f32":
+                    legs[name, "backward"] = (lambda arr=arr, G=G: arr._unpad(G, n_obj, F, wanted, *plan))
+                else:
+                    legs[name, "backward"] = (lambda arr=arr, G=G, ek=ek: arr._unpad_as(G, n_obj, tdt[ek], F, wanted, counts, base, max_count))
+                nbytes[name, "backward"] = sum(n_obj) * F * (size[ek] + size[pd]) + plan_bytes
+        for fn in legs.values():   # warm-up of every shape
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        times = {k: [] for k in legs}
+        for _ in range(args.reps):
+            for k, fn in legs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _i in range(args.inner):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) / args.inner)
+    out = {}
+    for (name, way), t in times.items():
+        med = statistics.median(t)
+        ref = statistics.median(times["f32 -> f32", way])
+        out.setdefault(name, {})[way] = {"median_ms": med, "min_ms": min(t), "max_ms": max(t), "bytes_moved": nbytes[name, way],
+                                         "achieved": nbytes[name, way] / (med * 1e-3) / 1e12, "unit": "TB/s", "vs_f32": med / ref}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
@@ -72,6 +131,10 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--backward", action="store_true", help="also time the backward of rearrange_outputs against the torch composition")
     ap.add_argument("--inner", type=int, default=10, help="--backward: calls between two events (keeps the queue full)")
+    ap.add_argument("--padded-dtype", choices=("f32", "bf16", "f16"), default="f32",
+                    help="bf16 / f16: also time rearrange_outputs with a padded tensor of that type, beside the float32 leg, in the same run")
+    ap.add_argument("--emb-dtype", choices=("f32", "bf16", "f16"), default=None,
+                    help="with --padded-dtype: the embeddings' type of the 16-bit leg, f32 (converting) or the padded type (bit copy); default both")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -128,6 +191,10 @@ def main():
         cpu_s = time.perf_counter() - t0
         agent_rows = E * env.n_agents * env.n_time_steps
         bwd = backward_leg(torch, arr, outs, countArr, padded, args, TP * len(types) * 8) if args.backward else None
+        dt = None
+        if args.padded_dtype != "f32":
+            dt = dtype_legs(torch, GpuInOutArranger, (types, E, env.n_agents, env.n_time_steps, env.obs_dim), countArr, n_obj, args,
+                            TP * len(types) * 8)
         print(json.dumps({
             "metric": "arranged agent-observations/s", "config": cfg, "envs": E, "players": E * env.n_agents,
             "time_steps": env.n_time_steps, "objects": n_obj, "max_count": countArr[1], "embed_width": args.feat,
@@ -140,6 +207,7 @@ def main():
                              "unit": "agent-observations/s",
                              "sample": "oracle/arranger.py (numpy restatement of InOutArranger) on the first %d envs, %.2f s" % (Es, cpu_s)},
             **({"backward": bwd} if bwd is not None else {}),
+            **({"padded_dtype": {"dtype": args.padded_dtype, "reps": args.reps, "inner": args.inner, "legs": dt}} if dt is not None else {}),
         }))
         env.close()
 
