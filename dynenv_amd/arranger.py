@@ -6,18 +6,20 @@ The reference's input layer does, per forward pass, in triple-nested Python over
     outs = [block(torch.tensor(obj)) for block, obj in zip(blocks, inputs)]
     outs, masks = arranger.rearrange_outputs(outs, counts, device)
 Here the same three calls exist with the same results, but `x` is the dense device tensor and all index work runs in the
-HIP kernels of `csrc/arranger_kernels.hip` through the C ABI (`dynenv_arrange_*`, include/dynenv.h).  No CPU fallback.
+HIP kernels of `csrc/arranger_kernels.hip` and `csrc/arranger_cols_kernels.hip` through the C ABI (`dynenv_arrange_*`,
+include/dynenv.h).  No CPU fallback.
 
 Like the reference's (out[range] -> torch.cat -> F.pad -> torch.stack, models.py:250-274), `rearrange_outputs` is differentiable:
 the embedding blocks train through it (a torch.autograd.Function over `dynenv_arrange_pad_backward` /
 `dynenv_arrange_scatter_backward`).  `GpuInputLayer` is the three calls as one nn.Module.
 
 Two modes.  The default pads to the largest object count of each batch, as the reference does, and so has to wait for the device to
-learn the shapes.  `fixed=...` works at capacities the caller fixes once (`dynenv_arrange_fixed_*`, csrc/arranger_fixed_kernels.hip):
-the same layout in the leading slots, zeros behind, no host round trip, capturable into a graph.
+learn the shapes.  `fixed=...` works at capacities the caller fixes once (`dynenv_arrange_fixed_*`, csrc/arranger_fixed_kernels.hip and
+the fixed-mode kernels of csrc/arranger_cols_kernels.hip): the same layout in the leading slots, zeros behind, no host round trip,
+capturable into a graph.
 
 In both modes `padded_dtype=torch.bfloat16` (or float16) writes the padded tensor in that type, for a network under torch.autocast
-(`dynenv_arrange_*_as`, csrc/arranger_dtype_kernels.hip): float32 embeddings are converted on the way (round to nearest even), embeddings
+(`dynenv_arrange_*_as`, csrc/arranger_cols_kernels.hip): float32 embeddings are converted on the way (round to nearest even), embeddings
 already of that type are copied bit for bit, and the backward hands every embedding a gradient of its own type.
 """
 import ctypes as C
@@ -47,8 +49,8 @@ class GpuInOutArranger(object):
         and nothing waited for, so the calls can be captured into a graph.  Objects beyond rows[i] or M are dropped, earlier types
         winning, and counted per type in the persistent int32 tensor `self.dropped` (added to by every call; nothing here reads or
         zeroes it).
-        padded_dtype=None: `padded` is float32, the code path it always was.  torch.bfloat16 / torch.float16, in either mode: `padded` is
-        written in that type (_rearrange_outputs_as); the embedding width must then be a multiple of 8."""
+        padded_dtype=None: `padded` is float32.  torch.bfloat16 / torch.float16, in either mode: `padded` is written in that type; the
+        embedding width must then be a multiple of 8.  (_rearrange_outputs_as: every case but the default mode's float32, which is _pad.)"""
         import torch
         if not torch.cuda.is_available():
             raise _capi.DynEnvError("dynenv_amd needs an MI355X (HIP device); there is no CPU fallback")
@@ -153,51 +155,10 @@ class GpuInOutArranger(object):
                 raise ValueError("rearrange_outputs: outs[%d] is None but object type %d has rows[%d] = %d" % (i, i, i, self.rows[i]))
             if o is not None and tuple(o.shape) != (TP * self.rows[i], F):
                 raise ValueError("rearrange_outputs: outs[%d] is %s, not %s" % (i, tuple(o.shape), (TP * self.rows[i], F)))
-        if self.padded_dtype is not None:
-            return self._rearrange_outputs_as(outs, counts, None, self.max_count, F), [mask[t].bool() for t in range(self.nTime)]
-        # float32 and contiguous inside the Function; torch differentiates a cast or a copy made out here
-        outs = [o if o is None else (o if o.dtype == torch.float32 else o.float()).contiguous() for o in outs]
-        if F % 4 or any(o is not None and o.data_ptr() % 16 for o in outs):
-            raise _capi.DynEnvError("the fixed-shape arranger needs an embedding width that is a multiple of 4 (got %d) and 16-byte aligned "
-                                    "embeddings; it has no per-type scatter fallback: use the default mode (fixed=None)" % F)
-        if torch.is_grad_enabled() and any(o is not None and o.requires_grad for o in outs):
-            padded = _arrange_fixed_function().apply(self, counts, *outs)
-        else:
-            padded = self._pad_fixed(outs, counts, F)
-        return padded, [mask[t].bool() for t in range(self.nTime)]
+        return self._rearrange_outputs_as(outs, counts, None, self.max_count, F), [mask[t].bool() for t in range(self.nTime)]
 
     def _type_ptrs(self, tensors):
         return (C.c_void_p * self.nObjectTypes)(*[t.data_ptr() if (t is not None and t.numel()) else None for t in tensors])
-
-    def _pad_fixed(self, outs, counts, F):
-        """one launch: every element of the padded tensor [T, M, P, F] is written"""
-        padded = self._torch.empty((self.nTime, self.max_count, self.nPlayers, F), dtype=self._torch.float32, device=self.device)
-        if self.max_count == 0:   # (an empty tensor has no address to hand over, and the call would launch nothing)
-            return padded
-        _capi.check(self._lib.dynenv_arrange_fixed_pad(self._type_ptrs(outs), _capi.ptr(counts), self._rows_c, self.nObjectTypes,
-                                                       self.nTime, self.nPlayers, self.max_count, F, _capi.ptr(padded), self._stream()),
-                    "dynenv_arrange_fixed_pad")
-        return padded
-
-    def _unpad_fixed(self, grad, counts, F, wanted):
-        """the backward of _pad_fixed, one launch: per type float32 [T*P*rows[i], F], zero in the rows past the kept count; None where
-        rows[i] == 0 or the gradient is not wanted"""
-        torch = self._torch
-        g = grad.contiguous()   # (an attention layer often hands back a permuted view)
-        if g.dtype != torch.float32:
-            g = g.float()
-        if g.data_ptr() % 16:
-            g = g.clone()
-        assert tuple(g.shape) == (self.nTime, self.max_count, self.nPlayers, F), tuple(g.shape)
-        TP = self.nTime * self.nPlayers
-        make = torch.zeros if self.max_count == 0 else torch.empty   # (M == 0: nothing is launched and every gradient row is zero)
-        grads = [make((TP * r, F), dtype=torch.float32, device=g.device) if (r and w) else None for r, w in zip(self.rows, wanted)]
-        if self.max_count and any(ge is not None for ge in grads):
-            _capi.check(self._lib.dynenv_arrange_fixed_pad_backward(_capi.ptr(g), _capi.ptr(counts), self._rows_c, self.nObjectTypes,
-                                                                    self.nTime, self.nPlayers, self.max_count, F,
-                                                                    self._type_ptrs(grads), self._stream()),
-                        "dynenv_arrange_fixed_pad_backward")
-        return grads
 
     def _plan_of(self, countArr):
         """(counts, base, max_count, slots) of a countArr.  A plain tuple (rebuilt by the caller, no `.base`) gets its bases from
@@ -213,7 +174,7 @@ class GpuInOutArranger(object):
     def rearrange_outputs(self, outs, countArr, device=None):
         """outs[i]: float32 [N_i, F] embeddings of inputs[i] (or None).  Returns (padded [T, maxCount, P, F],
         masks = list over time of bool [P, maxCount]) like models.py:252-274, and differentiable like it: when an outs[i]
-        requires grad, `padded` carries a grad_fn whose backward (csrc/arranger_kernels.hip, K5' / K4') hands every embedding
+        requires grad, `padded` carries a grad_fn whose backward (K5' of csrc/arranger_cols_kernels.hip, K4') hands every embedding
         row the upstream gradient's row at its slot.  The masks are not differentiable outputs."""
         torch = self._torch
         if self.fixed:
@@ -274,19 +235,25 @@ class GpuInOutArranger(object):
                                                              _capi.ptr(padded), self._stream()), "dynenv_arrange_scatter")
         return padded
 
-    # ---- padded_dtype = bfloat16 / float16, both modes: `base` is the plan's in the default mode and None in the fixed one ----
+    # ---- padded_dtype = bfloat16 / float16 in both modes, and float32 (None) in the fixed one: `base` is the plan's in the default
+    # mode and None in the fixed one ----
     _DTYPE_CODES = {"torch.float32": _capi.ARR_F32, "torch.bfloat16": _capi.ARR_BF16, "torch.float16": _capi.ARR_F16}
 
     def _rearrange_outputs_as(self, outs, counts, base, max_count, F):
-        """rearrange_outputs with a 16-bit padded tensor (shapes already checked).  Embeddings that are all float32 are converted by the
-        kernel; embeddings that are all of padded_dtype are copied bit for bit; anything else is cast to float32 out here, where torch
-        differentiates the cast.  One launch in either mode - the default mode has no scatter route here and DYNENV_ARR_DENSE_MIN is not
-        consulted.  Differentiable: every embedding gets a gradient of its own dtype."""
+        """rearrange_outputs through dynenv_arrange_*_as (shapes already checked): a 16-bit padded tensor, or the fixed mode's float32 one.
+        Embeddings that are all float32 are converted by the kernel; embeddings that are all of the padded tensor's dtype are copied bit
+        for bit; anything else is cast to float32 out here, where torch differentiates the cast.  One launch in either mode - the default
+        mode has no scatter route here and DYNENV_ARR_DENSE_MIN is not consulted.  Differentiable: every embedding gets a gradient of
+        its own dtype."""
         torch = self._torch
-        if not all(o is None or o.dtype == self.padded_dtype for o in outs):
+        if not all(o is None or o.dtype == (self.padded_dtype or torch.float32) for o in outs):
             outs = [o if o is None or o.dtype == torch.float32 else o.float() for o in outs]
         outs = [o if o is None else o.contiguous() for o in outs]
-        if F % 8 or any(o is not None and o.numel() and o.data_ptr() % 16 for o in outs):
+        unit = 4 if self.padded_dtype is None else 8   # elements of a 16-byte unit of the padded tensor
+        if F % unit or any(o is not None and o.numel() and o.data_ptr() % 16 for o in outs):
+            if self.padded_dtype is None:
+                raise _capi.DynEnvError("the fixed-shape arranger needs an embedding width that is a multiple of 4 (got %d) and 16-byte aligned "
+                                        "embeddings; it has no per-type scatter fallback: use the default mode (fixed=None)" % F)
             raise _capi.DynEnvError("a %s padded tensor needs an embedding width that is a multiple of 8 (got %d) and 16-byte aligned embeddings: "
                                     "a 16-byte unit of it is 8 elements, and there is no per-row fallback; use padded_dtype=None"
                                     % (self.padded_dtype, F))
@@ -295,12 +262,13 @@ class GpuInOutArranger(object):
         return self._pad_as(outs, counts, base, max_count, F)
 
     def _pad_as(self, outs, counts, base, max_count, F):
-        """one launch: every element of the padded tensor [T, max_count, P, F] of padded_dtype is written"""
-        padded = self._torch.empty((self.nTime, max_count, self.nPlayers, F), dtype=self.padded_dtype, device=self.device)
-        if max_count == 0:
+        """one launch: every element of the padded tensor [T, max_count, P, F] of padded_dtype (None: float32) is written"""
+        padded_dtype = self.padded_dtype or self._torch.float32
+        padded = self._torch.empty((self.nTime, max_count, self.nPlayers, F), dtype=padded_dtype, device=self.device)
+        if max_count == 0:   # (an empty tensor has no address to hand over, and the call would launch nothing)
             return padded
         emb_code = self._DTYPE_CODES[str(next(o.dtype for o in outs if o is not None))]
-        code = self._DTYPE_CODES[str(self.padded_dtype)]
+        code = self._DTYPE_CODES[str(padded_dtype)]
         if base is None:
             _capi.check(self._lib.dynenv_arrange_fixed_pad_as(self._type_ptrs(outs), emb_code, _capi.ptr(counts), self._rows_c, self.nObjectTypes,
                                                               self.nTime, self.nPlayers, max_count, F, _capi.ptr(padded), code, self._stream()),
@@ -316,9 +284,10 @@ class GpuInOutArranger(object):
         to float32 or copied bit for bit - None where rows[i] is None or the gradient is not wanted.  Every row is written: the fixed
         mode's rows behind the kept ones are zero."""
         torch = self._torch
+        padded_dtype = self.padded_dtype or torch.float32
         g = grad.contiguous()   # (an attention layer often hands back a permuted view)
-        if g.dtype != self.padded_dtype:
-            g = g.to(self.padded_dtype)
+        if g.dtype != padded_dtype:
+            g = g.to(padded_dtype)
         if g.data_ptr() % 16:
             g = g.clone()
         assert tuple(g.shape) == (self.nTime, max_count, self.nPlayers, F), tuple(g.shape)
@@ -328,7 +297,7 @@ class GpuInOutArranger(object):
             self.last_backward = None
         if max_count == 0 or not any(ge is not None and ge.shape[0] for ge in grads):
             return grads
-        emb_code, code = self._DTYPE_CODES[str(emb_dtype)], self._DTYPE_CODES[str(self.padded_dtype)]
+        emb_code, code = self._DTYPE_CODES[str(emb_dtype)], self._DTYPE_CODES[str(padded_dtype)]
         if base is None:
             _capi.check(self._lib.dynenv_arrange_fixed_pad_backward_as(_capi.ptr(g), code, _capi.ptr(counts), self._rows_c, self.nObjectTypes,
                                                                        self.nTime, self.nPlayers, max_count, F, self._type_ptrs(grads),
@@ -413,36 +382,13 @@ def _arrange_function():
     return _lazy["fn"]
 
 
-def _arrange_fixed_function():
-    if "fixed_fn" not in _lazy:
-        import torch
-        from torch.autograd.function import once_differentiable
-
-        class ArrangeOutputsFixed(torch.autograd.Function):
-            """padded = arranger._pad_fixed(outs, counts); d padded / d outs[i] = arranger._unpad_fixed.  The counts are the forward call's own."""
-
-            @staticmethod
-            def forward(ctx, arr, counts, *outs):
-                ctx.arr, ctx.counts = arr, counts
-                ctx.F = next(int(o.shape[1]) for o in outs if o is not None)
-                return arr._pad_fixed(outs, counts, ctx.F)
-
-            @staticmethod
-            @once_differentiable
-            def backward(ctx, grad):
-                return (None, None) + tuple(ctx.arr._unpad_fixed(grad, ctx.counts, ctx.F, ctx.needs_input_grad[2:]))
-
-        _lazy["fixed_fn"] = ArrangeOutputsFixed
-    return _lazy["fixed_fn"]
-
-
 def _arrange_as_function():
     if "as_fn" not in _lazy:
         import torch
         from torch.autograd.function import once_differentiable
 
         class ArrangeOutputsAs(torch.autograd.Function):
-            """padded = arranger._pad_as(outs, plan) in the arranger's padded_dtype; d padded / d outs[i] = arranger._unpad_as, in outs[i]'s own
+            """padded = arranger._pad_as(outs, plan) in the arranger's padded_dtype (None: float32); d padded / d outs[i] = arranger._unpad_as, in outs[i]'s own
             dtype.  plan = (counts, base, max_count) of the forward call, base None in the fixed mode."""
 
             @staticmethod

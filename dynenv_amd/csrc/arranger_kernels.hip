@@ -157,112 +157,9 @@ arr_scatter_kernel(const float* __restrict__ emb, const int32_t* __restrict__ sl
   padded[(size_t)slot[n] * F + f] = emb[gid];
 }
 
-// K5: the padded tensor in one pass, no pre-zeroing: one thread per float4 COLUMN (t, p, f) of padded[t][:][p][:] walking down its
-// player's slots j = 0 .. maxCount-1 (round 1-4: one thread per slot, 3.8-4.4 TB/s; this form 5.0-5.7 TB/s): the counts and bases
-// of the player are read once (not once per slot), the index arithmetic is one add per slot, and four independent 16-byte loads
-// are in flight per thread before their stores.  A wave still writes 1 KB contiguous per slot; the reads walk the player's
-// consecutive embedding rows.  (HBM-bound: the padded tensor is written once, every embedding read once.)
-// (the padded tensor is written once and not read here: non-temporal stores - worth 15-25 % where most slots are padding zeros, nothing
-//  where most carry an embedding; non-temporal LOADS of the embeddings gain 5-10 % on dense inputs and lose 17 % on sparse ones: not used)
+// (K5 / K5', the padded tensor in one pass and its backward, are arranger_cols_kernels.hip's)
 typedef float arr_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void arr_st_nt(float4* p, float4 v) { arr_f4 w = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(w, reinterpret_cast<arr_f4*>(p)); }
-#define ARR_ST(p, v) arr_st_nt((p), (v))
-extern "C" __global__ void __launch_bounds__(ARR_BLOCK)
-arr_pad_cols_kernel(const float* __restrict__ e0, const float* __restrict__ e1, const float* __restrict__ e2, const float* __restrict__ e3,
-                    const int32_t* __restrict__ counts, const int32_t* __restrict__ base, int nTypes, int T, int P, int maxCount, int F4,
-                    float4* __restrict__ padded) {
-  const unsigned x = blockIdx.x * ARR_BLOCK + threadIdx.x;
-  if (x >= (unsigned)P * (unsigned)F4) return;
-  const int p = (int)(x / (unsigned)F4), f = (int)(x % (unsigned)F4);
-  const int t = (int)blockIdx.y, TP = T * P, tp = t * P + p;
-  const size_t stride = (size_t)P * F4;  // float4s between consecutive slots of one column
-  float4* out = padded + (size_t)t * maxCount * stride + x;
-  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-  int j = 0;
-  for (int i = 0; i < nTypes && j < maxCount; ++i) {
-    int c = counts[(size_t)i * TP + tp];
-    if (c > maxCount - j) c = maxCount - j;  // (cannot happen: maxCount is the largest total; keeps the writes in bounds whatever the counts hold)
-    const float* e = i == 0 ? e0 : i == 1 ? e1 : i == 2 ? e2 : e3;
-    if (e) {
-      const float4* src = reinterpret_cast<const float4*>(e) + (size_t)base[(size_t)i * TP + tp] * F4 + f;
-      int k = 0;
-      for (; k + 4 <= c; k += 4) {
-        const float4 v0 = src[(size_t)(k + 0) * F4], v1 = src[(size_t)(k + 1) * F4], v2 = src[(size_t)(k + 2) * F4], v3 = src[(size_t)(k + 3) * F4];
-        ARR_ST(out, v0); ARR_ST(out + stride, v1); ARR_ST(out + 2 * stride, v2); ARR_ST(out + 3 * stride, v3);
-        out += 4 * stride;
-      }
-      for (; k < c; ++k) { ARR_ST(out, src[(size_t)k * F4]); out += stride; }
-    } else {
-      for (int k = 0; k < c; ++k) { ARR_ST(out, zero); out += stride; }
-    }
-    j += c;
-  }
-  for (; j < maxCount; ++j) { ARR_ST(out, zero); out += stride; }
-}
-
-// K5': the backward of K5 (autograd's derivative of catAndPad, models.py:147-166: a slice per embedding row, nothing summed), same
-// thread-to-data map: one thread per float4 column (t, p, f) walks down its player's slots and hands the upstream gradient of slot j
-// to the embedding row that owns it: g_i[base_i(t,p) + k][f] = grad[t][j][p][f].  Padding slots are never read, and every row of
-// every g_i is written exactly once (each row owns one slot): no pre-zeroing, no atomics, no second pass.  A type whose g_i is NULL
-// (no gradient wanted) is stepped over unread.  Four independent 16-byte loads in flight per thread before their stores, as in K5.
-// (the gradient is read once and every row written once: non-temporal stores AND loads.  Measured at 4096 environments, F = 128,
-//  four builds taking turns, three runs each, medians in ms for Driving Full (77 % of the slots carry an object) / RoboCup (100 %) /
-//  Driving Partial (19 %):  plain 0.286-0.304 / 0.376-0.377 / 0.052-0.053;  loads only 0.270-0.299 / 0.373 / 0.047;
-//  stores only 0.286-0.290 / 0.361-0.364 / 0.0426-0.0429;  both 0.278-0.279 / 0.349-0.350 / 0.048.  Stores alone never lose and are
-//  the best form of the sparse case (-18 %); both gain 7 % on the two dense cases, where the time is, and still 8 % on the sparse one.
-//  Not measured: what the rows' next reader - the embedding block's own backward - pays or saves; at these sizes, 130 MB to 1 GB of
-//  rows, they do not stay in L2 either way.  ARR_BWD_NT_LOAD / ARR_BWD_NT_STORE = 0 rebuild the other forms for an A/B.)
-#ifndef ARR_BWD_NT_LOAD
-#define ARR_BWD_NT_LOAD 1
-#endif
-#ifndef ARR_BWD_NT_STORE
-#define ARR_BWD_NT_STORE 1
-#endif
-__device__ __forceinline__ float4 arr_bwd_ld(const float4* p) {
-#if ARR_BWD_NT_LOAD
-  const arr_f4 w = __builtin_nontemporal_load(reinterpret_cast<const arr_f4*>(p));
-  return make_float4(w.x, w.y, w.z, w.w);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ void arr_bwd_st(float4* p, float4 v) {
-#if ARR_BWD_NT_STORE
-  arr_st_nt(p, v);
-#else
-  *p = v;
-#endif
-}
-extern "C" __global__ void __launch_bounds__(ARR_BLOCK)
-arr_unpad_cols_kernel(const float4* __restrict__ grad, const int32_t* __restrict__ counts, const int32_t* __restrict__ base, int nTypes,
-                      int T, int P, int maxCount, int F4, float* __restrict__ g0, float* __restrict__ g1, float* __restrict__ g2,
-                      float* __restrict__ g3) {
-  const unsigned x = blockIdx.x * ARR_BLOCK + threadIdx.x;
-  if (x >= (unsigned)P * (unsigned)F4) return;
-  const int p = (int)(x / (unsigned)F4), f = (int)(x % (unsigned)F4);
-  const int t = (int)blockIdx.y, TP = T * P, tp = t * P + p;
-  const size_t stride = (size_t)P * F4;  // float4s between consecutive slots of one column
-  const float4* in = grad + (size_t)t * maxCount * stride + x;
-  int j = 0;
-  for (int i = 0; i < nTypes && j < maxCount; ++i) {
-    int c = counts[(size_t)i * TP + tp];
-    if (c > maxCount - j) c = maxCount - j;  // (cannot happen, as in K5: keeps the reads inside the gradient whatever the counts hold)
-    float* g = i == 0 ? g0 : i == 1 ? g1 : i == 2 ? g2 : g3;
-    if (g && c > 0) {
-      float4* dst = reinterpret_cast<float4*>(g) + (size_t)base[(size_t)i * TP + tp] * F4 + f;
-      const float4* src = in;
-      int k = 0;
-      for (; k + 4 <= c; k += 4) {
-        const float4 v0 = arr_bwd_ld(src), v1 = arr_bwd_ld(src + stride), v2 = arr_bwd_ld(src + 2 * stride), v3 = arr_bwd_ld(src + 3 * stride);
-        arr_bwd_st(dst + (size_t)(k + 0) * F4, v0); arr_bwd_st(dst + (size_t)(k + 1) * F4, v1);
-        arr_bwd_st(dst + (size_t)(k + 2) * F4, v2); arr_bwd_st(dst + (size_t)(k + 3) * F4, v3);
-        src += 4 * stride;
-      }
-      for (; k < c; ++k) { arr_bwd_st(dst + (size_t)k * F4, arr_bwd_ld(src)); src += stride; }
-    }
-    if (c > 0) { in += (size_t)c * stride; j += c; }
-  }
-}
 
 // K4': the backward of K4, for any width and alignment: g[n][:] = grad[slot[n]][:]   (one thread per float)
 extern "C" __global__ void __launch_bounds__(ARR_BLOCK)

@@ -9,6 +9,7 @@
 #include "driving_host.h"   /* the Driving kernels and their host code are a translation unit of their own: driving_tu.hip */
 #include "robocup_kernels.hip"
 #include "arranger_kernels.hip"
+#include "arranger_cols_kernels.hip"
 #include "dynenv_host.h"
 #include "robocup_host.hip"
 #include "dynenv_math_probe.h"   /* (inline device code and two sizes: nothing is emitted here) */
@@ -16,37 +17,12 @@
 // the kernels of env_rows_kernels.hip, which this unit includes last (behind everything the step launches run)
 extern "C" __global__ void env_rows_save_kernel(EnvRowTable T, const int* __restrict__ idx, unsigned char* __restrict__ blobs);
 extern "C" __global__ void env_rows_load_kernel(EnvRowTable T, const int* __restrict__ idx, const unsigned char* __restrict__ blobs, int* __restrict__ status);
-// ... and those of arranger_fixed_kernels.hip, with the two structs they take by value
+// ... and the plan and gather of arranger_fixed_kernels.hip, with the struct they take by value
 struct ArrFixed { ArrTypes ty; int rows[DYNENV_ARR_MAX_TYPES]; int maxCount; };
-struct ArrFixedRows { int rows[DYNENV_ARR_MAX_TYPES]; };
 extern "C" __global__ void arrf_plan_kernel(const float* __restrict__ obs, int E, int T, int A, int D, ArrFixed fx, const int32_t* __restrict__ count_env, int jSpan,
                                             int32_t* __restrict__ counts, int32_t* __restrict__ obj_counts, uint8_t* __restrict__ mask, int32_t* __restrict__ dropped);
 extern "C" __global__ void arrf_gather_kernel(const float* __restrict__ obs, int E, int T, int A, int D, ArrFixed fx, const int32_t* __restrict__ count_env,
                                               float* in0, float* in1, float* in2, float* in3);
-extern "C" __global__ void arrf_pad_cols_kernel(const float* __restrict__ e0, const float* __restrict__ e1, const float* __restrict__ e2, const float* __restrict__ e3,
-                                                const int32_t* __restrict__ counts, ArrFixedRows rw, int nTypes, int T, int P, int maxCount, int F4,
-                                                float4* __restrict__ padded);
-extern "C" __global__ void arrf_unpad_cols_kernel(const float4* __restrict__ grad, const int32_t* __restrict__ counts, ArrFixedRows rw, int nTypes, int T, int P,
-                                                  int maxCount, int F4, float* __restrict__ g0, float* __restrict__ g1, float* __restrict__ g2, float* __restrict__ g3);
-// ... and those of arranger_dtype_kernels.hip (a 16-bit padded tensor from float32 embeddings), included behind everything else
-typedef unsigned arr_u4 __attribute__((ext_vector_type(4)));
-#define ARRD_DECLARE(NAME)                                                                                                                              \
-  extern "C" __global__ void arr_pad_cols_##NAME##_kernel(const float* __restrict__ e0, const float* __restrict__ e1, const float* __restrict__ e2,    \
-                                                          const float* __restrict__ e3, const int32_t* __restrict__ counts,                            \
-                                                          const int32_t* __restrict__ base, int nTypes, int T, int P, int maxCount, int F8,             \
-                                                          arr_u4* __restrict__ padded);                                                                \
-  extern "C" __global__ void arr_unpad_cols_##NAME##_kernel(const arr_u4* __restrict__ grad, const int32_t* __restrict__ counts,                       \
-                                                            const int32_t* __restrict__ base, int nTypes, int T, int P, int maxCount, int F8, int G,    \
-                                                            float* __restrict__ g0, float* __restrict__ g1, float* __restrict__ g2,                    \
-                                                            float* __restrict__ g3);                                                                   \
-  extern "C" __global__ void arrf_pad_cols_##NAME##_kernel(const float* __restrict__ e0, const float* __restrict__ e1, const float* __restrict__ e2,   \
-                                                           const float* __restrict__ e3, const int32_t* __restrict__ counts, ArrFixedRows rw,          \
-                                                           int nTypes, int T, int P, int maxCount, int F8, arr_u4* __restrict__ padded);               \
-  extern "C" __global__ void arrf_unpad_cols_##NAME##_kernel(const arr_u4* __restrict__ grad, const int32_t* __restrict__ counts, ArrFixedRows rw,     \
-                                                             int nTypes, int T, int P, int maxCount, int F8, int G, float* __restrict__ g0,            \
-                                                             float* __restrict__ g1, float* __restrict__ g2, float* __restrict__ g3);
-ARRD_DECLARE(bf16)
-ARRD_DECLARE(f16)
 // ... and this unit's math probe (include/dynenv_math_probe.h), the last kernel of the unit
 extern "C" __global__ void rc_math_probe_kernel(const double* in, int n, double* out);
 
@@ -400,19 +376,72 @@ int dynenv_arrange_scatter(const float* emb_dev, const int32_t* slot_dev, int64_
   return launched();
 }
 
+// ---- the padded tensor in one pass and its backward (arranger_cols_kernels.hip): eight entry points, one launcher.
+// What the checked entry points share: every argument error, before a device is looked for.  `third` is base_dev (default mode,
+// rw == nullptr) or rows (fixed mode).
+static int arr_as_args(const void* big, const void* const* per_type, const int32_t* counts_dev, const void* third, int32_t n_types, int32_t T,
+                       int32_t P, int32_t max_count, int32_t F, int32_t emb_dtype, int32_t padded_dtype, ArrFixedRows* rw) {
+  if (!big || !per_type || !counts_dev || !third) return fail(DYNENV_ERR_ARG, "null argument");
+  if (emb_dtype < DYNENV_ARR_F32 || emb_dtype > DYNENV_ARR_F16 || padded_dtype < DYNENV_ARR_F32 || padded_dtype > DYNENV_ARR_F16)
+    return fail(DYNENV_ERR_ARG, "arranger: unknown dtype (DYNENV_ARR_F32, _BF16 or _F16)");
+  const int u = padded_dtype == DYNENV_ARR_F32 ? 4 : 8;
+  if (n_types < 1 || n_types > DYNENV_ARR_MAX_TYPES || T < 1 || P < 1 || max_count < 0 || F < u || (F & (u - 1)))
+    return fail(DYNENV_ERR_ARG, u == 8 ? "arranger: bad shape (F must be a multiple of 8 for a 16-bit padded tensor)" : "arranger: bad shape (F must be a multiple of 4)");
+  if ((long long)P * (F / u) > 0x7fffffffLL || T > 65535 || (rw && (int64_t)T * P > (int64_t)1 << 30))
+    return fail(DYNENV_ERR_ARG, "arranger: padded tensor too large for one launch");
+  if ((uintptr_t)big % 16) return fail(DYNENV_ERR_ARG, "arranger: buffers must be 16-byte aligned");
+  for (int i = 0; i < DYNENV_ARR_MAX_TYPES; ++i) {
+    if (rw) {
+      rw->rows[i] = i < n_types ? ((const int32_t*)third)[i] : 0;
+      if (rw->rows[i] < 0) return fail(DYNENV_ERR_ARG, "arranger: rows[i] < 0");
+    }
+    if (i < n_types && (uintptr_t)per_type[i] % 16) return fail(DYNENV_ERR_ARG, "arranger: buffers must be 16-byte aligned");
+  }
+  const bool ok = emb_dtype == padded_dtype || emb_dtype == DYNENV_ARR_F32;
+  if (!ok) return fail(DYNENV_ERR_UNSUPPORTED, "arranger: embeddings are float32 or of the padded tensor's own dtype");
+  return DYNENV_OK;
+}
+// The launch behind the eight, arguments already checked and a device found: forward (big = the padded tensor, per_type = the
+// embeddings) or backward (big = its gradient, per_type = the embeddings' gradients), default mode (base, rw == nullptr) or fixed mode
+// (rw).  Embeddings of the padded tensor's own dtype are a copy of 16-byte units - 4 float32 or 8 16-bit elements - else float32 is
+// narrowed to / widened from bf16 or fp16.  max_count == 0 launches nothing.
+static int arr_cols_launch(bool backward, const void* big, const void* const* per_type, const int32_t* counts_dev, const int32_t* base_dev,
+                           const ArrFixedRows* rw, int32_t n_types, int32_t T, int32_t P, int32_t max_count, int32_t F, int32_t emb_dtype,
+                           int32_t padded_dtype, void* stream) {
+  static decltype(&arr_pad_cols_kernel) const pad[2][3] = {{arr_pad_cols_kernel, arr_pad_cols_bf16_kernel, arr_pad_cols_f16_kernel},
+                                                           {arrf_pad_cols_kernel, arrf_pad_cols_bf16_kernel, arrf_pad_cols_f16_kernel}};
+  static decltype(&arr_unpad_cols_kernel) const unpad[2][3] = {{arr_unpad_cols_kernel, arr_unpad_cols_bf16_kernel, arr_unpad_cols_f16_kernel},
+                                                               {arrf_unpad_cols_kernel, arrf_unpad_cols_bf16_kernel, arrf_unpad_cols_f16_kernel}};
+  if (max_count == 0) return DYNENV_OK;
+  const int unit = emb_dtype == padded_dtype ? 0 : padded_dtype == DYNENV_ARR_BF16 ? 1 : 2;
+  const int units = F / (padded_dtype == DYNENV_ARR_F32 ? 4 : 8);   // 16-byte units of a padded row
+  // the lanes that exchange their units in the widening backward (arrd_widen_st): the largest power of two that divides F / 8, at most a wave
+  int G = 1;
+  while (unit && G < 64 && units % (2 * G) == 0) G *= 2;
+  const void* q[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < n_types; ++i) q[i] = per_type[i];
+  const dim3 grid((unsigned)(((long long)P * units + ARR_BLOCK - 1) / ARR_BLOCK), (unsigned)T);
+  const ArrFixedRows rows = rw ? *rw : ArrFixedRows();
+  if (backward)
+    hipLaunchKernelGGL(unpad[rw != nullptr][unit], grid, dim3(ARR_BLOCK), 0, (hipStream_t)stream, static_cast<const arr_u4*>(big), counts_dev, base_dev,
+                       rows, n_types, T, P, max_count, units, G, const_cast<void*>(q[0]), const_cast<void*>(q[1]), const_cast<void*>(q[2]),
+                       const_cast<void*>(q[3]));
+  else
+    hipLaunchKernelGGL(pad[rw != nullptr][unit], grid, dim3(ARR_BLOCK), 0, (hipStream_t)stream, q[0], q[1], q[2], q[3], counts_dev, base_dev, rows, n_types,
+                       T, P, max_count, units, static_cast<arr_u4*>(const_cast<void*>(big)));
+  return launched();
+}
+
+// (device first, and no alignment check here or in the backward: the Python side routes misaligned buffers to the scatter kernels)
 int dynenv_arrange_pad(const float* const* emb_dev, const int32_t* counts_dev, const int32_t* base_dev, int32_t n_types,
                        int32_t T, int32_t P, int32_t max_count, int32_t F, float* padded_dev, void* stream) {
   if (int rc = have_device()) return rc;
   if (!emb_dev || !counts_dev || !base_dev || !padded_dev) return fail(DYNENV_ERR_ARG, "null argument");
   if (n_types < 1 || n_types > DYNENV_ARR_MAX_TYPES || T < 1 || P < 1 || max_count < 0 || F < 4 || (F & 3)) return fail(DYNENV_ERR_ARG, "arranger: bad shape (F must be a multiple of 4)");
   if (max_count == 0) return DYNENV_OK;
-  const float* e[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < n_types; ++i) e[i] = emb_dev[i];
-  const long long perRow = (long long)P * (F / 4);
-  if (perRow > 0x7fffffffLL || T > 65535) return fail(DYNENV_ERR_ARG, "arranger: padded tensor too large for one launch");
-  hipLaunchKernelGGL(arr_pad_cols_kernel, dim3((unsigned)((perRow + ARR_BLOCK - 1) / ARR_BLOCK), (unsigned)T), dim3(ARR_BLOCK), 0, (hipStream_t)stream,
-                     e[0], e[1], e[2], e[3], counts_dev, base_dev, n_types, T, P, max_count, F / 4, reinterpret_cast<float4*>(padded_dev));
-  return launched();
+  if ((long long)P * (F / 4) > 0x7fffffffLL || T > 65535) return fail(DYNENV_ERR_ARG, "arranger: padded tensor too large for one launch");
+  return arr_cols_launch(false, padded_dev, (const void* const*)emb_dev, counts_dev, base_dev, nullptr, n_types, T, P, max_count, F, DYNENV_ARR_F32,
+                         DYNENV_ARR_F32, stream);
 }
 
 // the backward of the two calls above.  Argument errors come before a device is looked for (as in dynenv_reset_masked): they are
@@ -421,15 +450,10 @@ int dynenv_arrange_pad_backward(const float* grad_padded_dev, const int32_t* cou
                                 int32_t T, int32_t P, int32_t max_count, int32_t F, float* const* grad_emb_dev, void* stream) {
   if (!grad_padded_dev || !counts_dev || !base_dev || !grad_emb_dev) return fail(DYNENV_ERR_ARG, "null argument");
   if (n_types < 1 || n_types > DYNENV_ARR_MAX_TYPES || T < 1 || P < 1 || max_count < 0 || F < 4 || (F & 3)) return fail(DYNENV_ERR_ARG, "arranger: bad shape (F must be a multiple of 4)");
-  const long long perRow = (long long)P * (F / 4);
-  if (perRow > 0x7fffffffLL || T > 65535) return fail(DYNENV_ERR_ARG, "arranger: padded tensor too large for one launch");
+  if ((long long)P * (F / 4) > 0x7fffffffLL || T > 65535) return fail(DYNENV_ERR_ARG, "arranger: padded tensor too large for one launch");
   if (int rc = have_device()) return rc;
-  if (max_count == 0) return DYNENV_OK;
-  float* g[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < n_types; ++i) g[i] = grad_emb_dev[i];
-  hipLaunchKernelGGL(arr_unpad_cols_kernel, dim3((unsigned)((perRow + ARR_BLOCK - 1) / ARR_BLOCK), (unsigned)T), dim3(ARR_BLOCK), 0, (hipStream_t)stream,
-                     reinterpret_cast<const float4*>(grad_padded_dev), counts_dev, base_dev, n_types, T, P, max_count, F / 4, g[0], g[1], g[2], g[3]);
-  return launched();
+  return arr_cols_launch(true, grad_padded_dev, (const void* const*)grad_emb_dev, counts_dev, base_dev, nullptr, n_types, T, P, max_count, F,
+                         DYNENV_ARR_F32, DYNENV_ARR_F32, stream);
 }
 
 int dynenv_arrange_scatter_backward(const float* grad_padded_dev, const int32_t* slot_dev, int64_t N, int32_t F, float* grad_emb_dev, void* stream) {
@@ -480,148 +504,42 @@ int dynenv_arrange_fixed_gather(const float* obs_dev, int32_t E, int32_t T, int3
   return launched();
 }
 
-// what the two pad calls share: shapes, launch limits, rows and the 16-byte alignment of the float buffers (NULL entries pass)
-static int arr_fixed_pad_args(const void* big, const void* const* per_type, const int32_t* counts_dev, const int32_t* rows, int32_t n_types,
-                              int32_t T, int32_t P, int32_t max_count, int32_t F, ArrFixedRows& rw) {
-  if (!big || !per_type || !counts_dev || !rows) return fail(DYNENV_ERR_ARG, "null argument");
-  if (n_types < 1 || n_types > DYNENV_ARR_MAX_TYPES || T < 1 || P < 1 || max_count < 0 || F < 4 || (F & 3)) return fail(DYNENV_ERR_ARG, "arranger: bad shape (F must be a multiple of 4)");
-  if ((long long)P * (F / 4) > 0x7fffffffLL || T > 65535 || (int64_t)T * P > (int64_t)1 << 30) return fail(DYNENV_ERR_ARG, "arranger: padded tensor too large for one launch");
-  if ((uintptr_t)big % 16) return fail(DYNENV_ERR_ARG, "arranger: buffers must be 16-byte aligned");
-  for (int i = 0; i < DYNENV_ARR_MAX_TYPES; ++i) {
-    rw.rows[i] = i < n_types ? rows[i] : 0;
-    if (rw.rows[i] < 0) return fail(DYNENV_ERR_ARG, "arranger: rows[i] < 0");
-    if (i < n_types && (uintptr_t)per_type[i] % 16) return fail(DYNENV_ERR_ARG, "arranger: buffers must be 16-byte aligned");
-  }
-  return DYNENV_OK;
-}
-
+// the float32 calls are the _as calls with float32 twice
 int dynenv_arrange_fixed_pad(const float* const* emb_dev, const int32_t* counts_dev, const int32_t* rows, int32_t n_types, int32_t T,
                              int32_t P, int32_t max_count, int32_t F, float* padded_dev, void* stream) {
-  ArrFixedRows rw;
-  if (int rc = arr_fixed_pad_args(padded_dev, (const void* const*)emb_dev, counts_dev, rows, n_types, T, P, max_count, F, rw)) return rc;
-  if (int rc = have_device()) return rc;
-  if (max_count == 0) return DYNENV_OK;
-  const float* e[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < n_types; ++i) e[i] = emb_dev[i];
-  const long long perRow = (long long)P * (F / 4);
-  hipLaunchKernelGGL(arrf_pad_cols_kernel, dim3((unsigned)((perRow + ARR_BLOCK - 1) / ARR_BLOCK), (unsigned)T), dim3(ARR_BLOCK), 0, (hipStream_t)stream,
-                     e[0], e[1], e[2], e[3], counts_dev, rw, n_types, T, P, max_count, F / 4, reinterpret_cast<float4*>(padded_dev));
-  return launched();
+  return dynenv_arrange_fixed_pad_as((const void* const*)emb_dev, DYNENV_ARR_F32, counts_dev, rows, n_types, T, P, max_count, F, padded_dev, DYNENV_ARR_F32, stream);
 }
 
 int dynenv_arrange_fixed_pad_backward(const float* grad_padded_dev, const int32_t* counts_dev, const int32_t* rows, int32_t n_types, int32_t T,
                                       int32_t P, int32_t max_count, int32_t F, float* const* grad_emb_dev, void* stream) {
-  ArrFixedRows rw;
-  if (int rc = arr_fixed_pad_args(grad_padded_dev, (const void* const*)grad_emb_dev, counts_dev, rows, n_types, T, P, max_count, F, rw)) return rc;
-  if (int rc = have_device()) return rc;
-  if (max_count == 0) return DYNENV_OK;
-  float* g[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < n_types; ++i) g[i] = grad_emb_dev[i];
-  const long long perRow = (long long)P * (F / 4);
-  hipLaunchKernelGGL(arrf_unpad_cols_kernel, dim3((unsigned)((perRow + ARR_BLOCK - 1) / ARR_BLOCK), (unsigned)T), dim3(ARR_BLOCK), 0, (hipStream_t)stream,
-                     reinterpret_cast<const float4*>(grad_padded_dev), counts_dev, rw, n_types, T, P, max_count, F / 4, g[0], g[1], g[2], g[3]);
-  return launched();
+  return dynenv_arrange_fixed_pad_backward_as(grad_padded_dev, DYNENV_ARR_F32, counts_dev, rows, n_types, T, P, max_count, F, (void* const*)grad_emb_dev,
+                                              DYNENV_ARR_F32, stream);
 }
 
-// ---- the padded tensor in a 16-bit type (arranger_dtype_kernels.hip): dynenv_arrange_pad / _pad_backward / _fixed_pad / _fixed_pad_backward
-// with a dtype for the per-type buffers and one for the padded tensor.  What the four share: every argument error, before a device is
-// looked for.  `third` is base_dev (default mode, rw == nullptr) or rows (fixed mode).
-static int arr_as_args(const void* big, const void* const* per_type, const int32_t* counts_dev, const void* third, int32_t n_types, int32_t T,
-                       int32_t P, int32_t max_count, int32_t F, int32_t emb_dtype, int32_t padded_dtype, ArrFixedRows* rw) {
-  if (!big || !per_type || !counts_dev || !third) return fail(DYNENV_ERR_ARG, "null argument");
-  if (emb_dtype < DYNENV_ARR_F32 || emb_dtype > DYNENV_ARR_F16 || padded_dtype < DYNENV_ARR_F32 || padded_dtype > DYNENV_ARR_F16)
-    return fail(DYNENV_ERR_ARG, "arranger: unknown dtype (DYNENV_ARR_F32, _BF16 or _F16)");
-  const int u = padded_dtype == DYNENV_ARR_F32 ? 4 : 8;
-  if (n_types < 1 || n_types > DYNENV_ARR_MAX_TYPES || T < 1 || P < 1 || max_count < 0 || F < u || (F & (u - 1)))
-    return fail(DYNENV_ERR_ARG, u == 8 ? "arranger: bad shape (F must be a multiple of 8 for a 16-bit padded tensor)" : "arranger: bad shape (F must be a multiple of 4)");
-  if ((long long)P * (F / u) > 0x7fffffffLL || T > 65535 || (rw && (int64_t)T * P > (int64_t)1 << 30))
-    return fail(DYNENV_ERR_ARG, "arranger: padded tensor too large for one launch");
-  if ((uintptr_t)big % 16) return fail(DYNENV_ERR_ARG, "arranger: buffers must be 16-byte aligned");
-  for (int i = 0; i < DYNENV_ARR_MAX_TYPES; ++i) {
-    if (rw) {
-      rw->rows[i] = i < n_types ? ((const int32_t*)third)[i] : 0;
-      if (rw->rows[i] < 0) return fail(DYNENV_ERR_ARG, "arranger: rows[i] < 0");
-    }
-    if (i < n_types && (uintptr_t)per_type[i] % 16) return fail(DYNENV_ERR_ARG, "arranger: buffers must be 16-byte aligned");
-  }
-  const bool ok = emb_dtype == padded_dtype || emb_dtype == DYNENV_ARR_F32;
-  if (!ok) return fail(DYNENV_ERR_UNSUPPORTED, "arranger: embeddings are float32 or of the padded tensor's own dtype");
-  return DYNENV_OK;
-}
-// the lanes that exchange their units in the widening backward (arrd_widen_st): the largest power of two that divides F / 8, at most a wave
-static int arrd_group(int32_t F) {
-  int G = 1;
-  while (G < 64 && (F / 8) % (2 * G) == 0) G *= 2;
-  return G;
-}
-#define ARRD_GRID(perRow, T) dim3((unsigned)(((perRow) + ARR_BLOCK - 1) / ARR_BLOCK), (unsigned)(T)), dim3(ARR_BLOCK), 0, (hipStream_t)stream
-
+// ---- dynenv_arrange_pad / _pad_backward / _fixed_pad / _fixed_pad_backward with a dtype for the per-type buffers and one for the
+// padded tensor
 int dynenv_arrange_pad_as(const void* const* emb_dev, int32_t emb_dtype, const int32_t* counts_dev, const int32_t* base_dev, int32_t n_types,
                           int32_t T, int32_t P, int32_t max_count, int32_t F, void* padded_dev, int32_t padded_dtype, void* stream) {
   if (int rc = arr_as_args(padded_dev, emb_dev, counts_dev, base_dev, n_types, T, P, max_count, F, emb_dtype, padded_dtype, nullptr)) return rc;
-  if (padded_dtype == DYNENV_ARR_F32)
-    return dynenv_arrange_pad((const float* const*)emb_dev, counts_dev, base_dev, n_types, T, P, max_count, F, (float*)padded_dev, stream);
   if (int rc = have_device()) return rc;
-  if (max_count == 0) return DYNENV_OK;
-  const float* e[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < n_types; ++i) e[i] = (const float*)emb_dev[i];
-  const long long perRow = (long long)P * (F / 8);
-  if (emb_dtype == padded_dtype)  // a bit copy of 16-byte units: K5 itself, F / 8 units per row
-    hipLaunchKernelGGL(arr_pad_cols_kernel, ARRD_GRID(perRow, T), e[0], e[1], e[2], e[3], counts_dev, base_dev, n_types, T, P, max_count, F / 8,
-                       reinterpret_cast<float4*>(padded_dev));
-  else if (padded_dtype == DYNENV_ARR_BF16)
-    hipLaunchKernelGGL(arr_pad_cols_bf16_kernel, ARRD_GRID(perRow, T), e[0], e[1], e[2], e[3], counts_dev, base_dev, n_types, T, P, max_count, F / 8,
-                       reinterpret_cast<arr_u4*>(padded_dev));
-  else
-    hipLaunchKernelGGL(arr_pad_cols_f16_kernel, ARRD_GRID(perRow, T), e[0], e[1], e[2], e[3], counts_dev, base_dev, n_types, T, P, max_count, F / 8,
-                       reinterpret_cast<arr_u4*>(padded_dev));
-  return launched();
+  return arr_cols_launch(false, padded_dev, emb_dev, counts_dev, base_dev, nullptr, n_types, T, P, max_count, F, emb_dtype, padded_dtype, stream);
 }
 
 int dynenv_arrange_pad_backward_as(const void* grad_padded_dev, int32_t padded_dtype, const int32_t* counts_dev, const int32_t* base_dev,
                                    int32_t n_types, int32_t T, int32_t P, int32_t max_count, int32_t F, void* const* grad_emb_dev,
                                    int32_t emb_dtype, void* stream) {
   if (int rc = arr_as_args(grad_padded_dev, (const void* const*)grad_emb_dev, counts_dev, base_dev, n_types, T, P, max_count, F, emb_dtype, padded_dtype, nullptr)) return rc;
-  if (padded_dtype == DYNENV_ARR_F32)
-    return dynenv_arrange_pad_backward((const float*)grad_padded_dev, counts_dev, base_dev, n_types, T, P, max_count, F, (float* const*)grad_emb_dev, stream);
   if (int rc = have_device()) return rc;
-  if (max_count == 0) return DYNENV_OK;
-  float* g[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < n_types; ++i) g[i] = (float*)grad_emb_dev[i];
-  const long long perRow = (long long)P * (F / 8);
-  if (emb_dtype == padded_dtype)  // K5' itself, F / 8 units per row
-    hipLaunchKernelGGL(arr_unpad_cols_kernel, ARRD_GRID(perRow, T), reinterpret_cast<const float4*>(grad_padded_dev), counts_dev, base_dev, n_types, T, P,
-                       max_count, F / 8, g[0], g[1], g[2], g[3]);
-  else if (padded_dtype == DYNENV_ARR_BF16)
-    hipLaunchKernelGGL(arr_unpad_cols_bf16_kernel, ARRD_GRID(perRow, T), reinterpret_cast<const arr_u4*>(grad_padded_dev), counts_dev, base_dev, n_types, T,
-                       P, max_count, F / 8, arrd_group(F), g[0], g[1], g[2], g[3]);
-  else
-    hipLaunchKernelGGL(arr_unpad_cols_f16_kernel, ARRD_GRID(perRow, T), reinterpret_cast<const arr_u4*>(grad_padded_dev), counts_dev, base_dev, n_types, T,
-                       P, max_count, F / 8, arrd_group(F), g[0], g[1], g[2], g[3]);
-  return launched();
+  return arr_cols_launch(true, grad_padded_dev, (const void* const*)grad_emb_dev, counts_dev, base_dev, nullptr, n_types, T, P, max_count, F, emb_dtype,
+                         padded_dtype, stream);
 }
 
 int dynenv_arrange_fixed_pad_as(const void* const* emb_dev, int32_t emb_dtype, const int32_t* counts_dev, const int32_t* rows, int32_t n_types,
                                 int32_t T, int32_t P, int32_t max_count, int32_t F, void* padded_dev, int32_t padded_dtype, void* stream) {
   ArrFixedRows rw;
   if (int rc = arr_as_args(padded_dev, emb_dev, counts_dev, rows, n_types, T, P, max_count, F, emb_dtype, padded_dtype, &rw)) return rc;
-  if (padded_dtype == DYNENV_ARR_F32)
-    return dynenv_arrange_fixed_pad((const float* const*)emb_dev, counts_dev, rows, n_types, T, P, max_count, F, (float*)padded_dev, stream);
   if (int rc = have_device()) return rc;
-  if (max_count == 0) return DYNENV_OK;
-  const float* e[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < n_types; ++i) e[i] = (const float*)emb_dev[i];
-  const long long perRow = (long long)P * (F / 8);
-  if (emb_dtype == padded_dtype)  // KF3 itself, F / 8 units per row
-    hipLaunchKernelGGL(arrf_pad_cols_kernel, ARRD_GRID(perRow, T), e[0], e[1], e[2], e[3], counts_dev, rw, n_types, T, P, max_count, F / 8,
-                       reinterpret_cast<float4*>(padded_dev));
-  else if (padded_dtype == DYNENV_ARR_BF16)
-    hipLaunchKernelGGL(arrf_pad_cols_bf16_kernel, ARRD_GRID(perRow, T), e[0], e[1], e[2], e[3], counts_dev, rw, n_types, T, P, max_count, F / 8,
-                       reinterpret_cast<arr_u4*>(padded_dev));
-  else
-    hipLaunchKernelGGL(arrf_pad_cols_f16_kernel, ARRD_GRID(perRow, T), e[0], e[1], e[2], e[3], counts_dev, rw, n_types, T, P, max_count, F / 8,
-                       reinterpret_cast<arr_u4*>(padded_dev));
-  return launched();
+  return arr_cols_launch(false, padded_dev, emb_dev, counts_dev, nullptr, &rw, n_types, T, P, max_count, F, emb_dtype, padded_dtype, stream);
 }
 
 int dynenv_arrange_fixed_pad_backward_as(const void* grad_padded_dev, int32_t padded_dtype, const int32_t* counts_dev, const int32_t* rows,
@@ -629,23 +547,9 @@ int dynenv_arrange_fixed_pad_backward_as(const void* grad_padded_dev, int32_t pa
                                          int32_t emb_dtype, void* stream) {
   ArrFixedRows rw;
   if (int rc = arr_as_args(grad_padded_dev, (const void* const*)grad_emb_dev, counts_dev, rows, n_types, T, P, max_count, F, emb_dtype, padded_dtype, &rw)) return rc;
-  if (padded_dtype == DYNENV_ARR_F32)
-    return dynenv_arrange_fixed_pad_backward((const float*)grad_padded_dev, counts_dev, rows, n_types, T, P, max_count, F, (float* const*)grad_emb_dev, stream);
   if (int rc = have_device()) return rc;
-  if (max_count == 0) return DYNENV_OK;
-  float* g[DYNENV_ARR_MAX_TYPES] = {nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < n_types; ++i) g[i] = (float*)grad_emb_dev[i];
-  const long long perRow = (long long)P * (F / 8);
-  if (emb_dtype == padded_dtype)  // KF3' itself, F / 8 units per row
-    hipLaunchKernelGGL(arrf_unpad_cols_kernel, ARRD_GRID(perRow, T), reinterpret_cast<const float4*>(grad_padded_dev), counts_dev, rw, n_types, T, P,
-                       max_count, F / 8, g[0], g[1], g[2], g[3]);
-  else if (padded_dtype == DYNENV_ARR_BF16)
-    hipLaunchKernelGGL(arrf_unpad_cols_bf16_kernel, ARRD_GRID(perRow, T), reinterpret_cast<const arr_u4*>(grad_padded_dev), counts_dev, rw, n_types, T, P,
-                       max_count, F / 8, arrd_group(F), g[0], g[1], g[2], g[3]);
-  else
-    hipLaunchKernelGGL(arrf_unpad_cols_f16_kernel, ARRD_GRID(perRow, T), reinterpret_cast<const arr_u4*>(grad_padded_dev), counts_dev, rw, n_types, T, P,
-                       max_count, F / 8, arrd_group(F), g[0], g[1], g[2], g[3]);
-  return launched();
+  return arr_cols_launch(true, grad_padded_dev, (const void* const*)grad_emb_dev, counts_dev, nullptr, &rw, n_types, T, P, max_count, F, emb_dtype,
+                         padded_dtype, stream);
 }
 
 int dynenv_obs_pack(const float* obs_dev, int64_t n_env_time, int32_t A, int32_t D, int32_t split, float* packed_dev, void* stream) {
@@ -828,5 +732,3 @@ int dynenv_math_probe(int32_t unit, const double* in_host, int32_t n, double* ou
 #include "arranger_fixed_kernels.hip"
 // this unit's math probe: every routine of include/dynenv_math.h as compiled here (-O3), the row of include/dynenv_math_probe.h
 extern "C" __global__ void __launch_bounds__(64) rc_math_probe_kernel(const double* in, int n, double* out) { dm_probe_wave(in, n, out); }
-// the arranger's 16-bit padded tensor, behind every kernel the unit had (the typedef of arr_u4 above is repeated there: the same type)
-#include "arranger_dtype_kernels.hip"

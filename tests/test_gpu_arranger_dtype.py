@@ -1,5 +1,5 @@
-"""The 16-bit padded tensor on the device (csrc/arranger_dtype_kernels.hip and the bit-copy launches of the float32 kernels, through
-dynenv_arrange_*_as and GpuInOutArranger / GpuInputLayer(padded_dtype=...)), bit for bit - no tolerance anywhere - against the numpy
+"""The 16-bit padded tensor on the device (csrc/arranger_cols_kernels.hip: the narrowing kernels and the bit-copy launches of the
+copying ones, through dynenv_arrange_*_as and GpuInOutArranger / GpuInputLayer(padded_dtype=...)), bit for bit - no tolerance anywhere - against the numpy
 statements of the arranger (tests/arranger_ref.py, arranger_grad_ref.py, arranger_fixed_ref.py) converted by tests/arranger_dtype_ref.py,
 against the float32 path of the same device, and against the reference's recorded vectors.  Bit-compared inputs hold no NaN; one
 assertion of its own checks that a NaN embedding gives a NaN slot.  -m gpu.

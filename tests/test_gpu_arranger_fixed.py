@@ -1,5 +1,5 @@
-"""The fixed-shape arranger on the device (arranger_fixed_kernels.hip through dynenv_arrange_fixed_* and GpuInOutArranger / GpuInputLayer
-(fixed=...)), bit for bit against the numpy statement of its contract (tests/arranger_fixed_ref.py) and, where nothing is dropped,
+"""The fixed-shape arranger on the device (arranger_fixed_kernels.hip and arranger_cols_kernels.hip through dynenv_arrange_fixed_* and
+GpuInOutArranger / GpuInputLayer (fixed=...)), bit for bit against the numpy statement of its contract (tests/arranger_fixed_ref.py) and, where nothing is dropped,
 against the default mode on the same device; guard bands around every output of the C ABI; autograd; and a whole rollout step -
 environment step, counts, input layer - captured into one graph and replayed.  -m gpu."""
 import ctypes as C
@@ -336,8 +336,8 @@ def test_input_layer_trains_its_blocks():
         return forward_hook
 
     hooks = [b.register_forward_hook(watch(i)) for i, b in enumerate(blocks)]
-    unpad = layer.arranger._unpad_fixed
-    layer.arranger._unpad_fixed = lambda *a: handed.append(unpad(*a)) or handed[-1]
+    unpad = layer.arranger._unpad_as
+    layer.arranger._unpad_as = lambda *a: handed.append(unpad(*a)) or handed[-1]
     padded, masks = layer(obs, ce)
     P = E * A
     assert padded.grad_fn is not None and tuple(padded.shape) == (T, M, P, F) and len(masks) == T

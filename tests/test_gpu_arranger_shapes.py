@@ -268,3 +268,73 @@ def test_arranger_c_abi_writes_nothing_outside_its_outputs():
                     "scatter")
     assert np.array_equal(padded.cpu().numpy().reshape(want.shape), want)
     intact(pb, F32S, "padded (scatter)")
+
+
+@pytest.mark.parametrize("padded_kind", ["f32", "bf16"])
+@pytest.mark.parametrize("fixed", [False, True], ids=["default", "fixed"])
+def test_counts_the_plan_did_not_make(fixed, padded_kind):
+    """The C ABI takes counts_dev from the caller: a negative count, and one beyond rows[i] and beyond the slots left, through the
+    pad and pad_backward calls of both modes (arranger_cols_kernels.hip), float32 embeddings, a float32 and a bf16 padded tensor.
+    Every kernel keeps c' = max(0, min(c, rows[i] if fixed, slots left)), so with counts = [[-2, 2], [2, 5]] (type x player), M = 3:
+        player 0: type 0 keeps 0, type 1 keeps 2      -> slots: type 1's first row, its second row, zeros
+        player 1: type 0 keeps 2, type 1 keeps 1 of 5 -> slots: type 0's first row, its second row, type 1's first row
+    All values are small integers, exact in bf16.  Every output lies between guard bands that even an unclamped walk stays inside."""
+    import torch
+    from dynenv_amd import _capi
+    from test_gpu_arranger_dtype import Guarded, SENTINEL
+    lib = _capi.load()
+    vp = C.c_void_p
+    st = vp(torch.cuda.current_stream().cuda_stream)
+    n, T, P, M, F = 2, 1, 2, 3, 8
+    counts = torch.tensor([[-2, 2], [2, 5]], dtype=torch.int32).cuda()
+    if fixed:
+        rows = [2, 3]
+        nrows = [T * P * r for r in rows]
+        start = [[0, 2], [0, 3]]             # tp * rows[i], type x player
+        third = (C.c_int32 * n)(*rows)
+        pad_fn, bwd_fn = lib.dynenv_arrange_fixed_pad_as, lib.dynenv_arrange_fixed_pad_backward_as
+    else:
+        nrows = [2, 5]
+        start = [[0, 0], [0, 2]]
+        base = torch.tensor(start, dtype=torch.int32).cuda()
+        third = vp(base.data_ptr())
+        pad_fn, bwd_fn = lib.dynenv_arrange_pad_as, lib.dynenv_arrange_pad_backward_as
+    kept = [[0, 2], [2, 1]]                  # c', type x player
+    owner = {(0, 0): (1, 0), (1, 0): (1, 1), (0, 1): (0, 0), (1, 1): (0, 1), (2, 1): (1, 0)}   # (slot, player) -> (type, the player's k-th row)
+    pc, words = (0, 2) if padded_kind == "f32" else (1, 1)
+    to_padded = lambda a: a.view(np.uint32) if words == 2 else (a.view(np.uint32) >> 16).astype(np.uint16)   # exact: small integers
+
+    host = [(1 + 100 * i + np.arange(r * F)).reshape(r, F).astype(np.float32) for i, r in enumerate(nrows)]
+    assert host[1].max() < 256
+    embs = [torch.from_numpy(h).cuda() for h in host]
+    want = np.zeros((T, M, P, F), np.float32)
+    for (j, p), (i, k) in owner.items():
+        want[0, j, p] = host[i][start[i][p] + k]
+    out = Guarded(T * M * P * F, 2 * words)
+    e_ptrs = (vp * n)(*[e.data_ptr() for e in embs])
+    _capi.check(pad_fn(e_ptrs, 0, vp(counts.data_ptr()), third, n, T, P, M, F, vp(out.ptr()), pc, st), "pad")
+    got = out.check("padded", True)          # the bands are intact and every element was written
+    assert np.array_equal(got.view(np.uint32 if words == 2 else np.uint16).reshape(T, M, P, F), to_padded(want)), "padded, bit for bit"
+
+    up = (1 + np.arange(T * M * P * F)).reshape(T, M, P, F).astype(np.float32)
+    up[0, 2, 0] = np.nan                     # player 0's padding slot
+    if words == 2:
+        upd = torch.from_numpy(up).cuda()
+    else:
+        upd = torch.from_numpy((up.view(np.uint32) >> 16).astype(np.uint16).view(np.int16)).cuda()
+    gs = [Guarded(r * F, 4) for r in nrows]
+    g_ptrs = (vp * n)(*[g.ptr() for g in gs])
+    _capi.check(bwd_fn(vp(upd.data_ptr()), pc, vp(counts.data_ptr()), third, n, T, P, M, F, g_ptrs, 0, st), "pad_backward")
+    unwritten = np.uint32(SENTINEL << 16 | SENTINEL)
+    for i, g in enumerate(gs):
+        b = g.buf.cpu().numpy().view(np.uint16)
+        band = g.G * g.words
+        assert (b[:band] == SENTINEL).all() and (b[b.size - band:] == SENTINEL).all(), "grad_emb %d: a guard band was written" % i
+        pay = b[band:b.size - band].view(np.uint32).reshape(nrows[i], F)
+        expect = np.full((nrows[i], F), 0 if fixed else unwritten, np.uint32)   # fixed mode: +0.0 behind the kept rows; default: not touched
+        for (j, p), (ti, k) in owner.items():
+            if ti == i:
+                expect[start[i][p] + k] = up[0, j, p].view(np.uint32)
+        assert np.array_equal(pay, expect), "grad_emb %d: the kept rows are their slots, the rest %s" % (i, "+0.0" if fixed else "untouched")
+        written = pay[pay != unwritten].view(np.float32)
+        assert not np.isnan(written).any(), "grad_emb %d: the padding slot was read" % i
