@@ -8,11 +8,11 @@ from .vec_env import BatchedDynEnv, make_dyn_env
 from .arranger import GpuInOutArranger, groups_for
 
 __all__ = ["BatchedDynEnv", "make_dyn_env", "DynEnvType", "NoiseType", "ObservationType", "GpuInOutArranger", "GpuInputLayer",
-           "groups_for"]
+           "GpuEmbedInputLayer", "EmbedBlock", "groups_for"]
 
 
 def __getattr__(name):
-    if name == "GpuInputLayer":   # an nn.Module: built on first use, so that the package imports without torch
+    if name in ("GpuInputLayer", "GpuEmbedInputLayer", "EmbedBlock"):   # nn.Modules: built on first use, so that the package imports without torch
         from . import arranger
-        return arranger.GpuInputLayer
+        return getattr(arranger, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -87,6 +87,10 @@ class ArrPlan(C.Structure):  # dynenv_arr_plan_t
                 ("total", C.c_int64 * ARR_MAX_TYPES)]
 
 
+class EmbedBlock(C.Structure):  # dynenv_embed_block_t: device pointers of one EmbedBlock's six float32 parameters
+    _fields_ = [(n, C.c_void_p) for n in ("w1", "ln1_w", "ln1_b", "w2", "ln2_w", "ln2_b")]
+
+
 vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
 
 # THE binding of include/dynenv.h: name -> (restype, argtypes), in the header's order of growth.  load() sets exactly these, so an entry
@@ -148,6 +152,8 @@ SIGNATURES = {
     "dynenv_arrange_pad_backward_as": (C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp), i32, vp]),
     "dynenv_arrange_fixed_pad_as": (C.c_int, [C.POINTER(vp), i32, vp, C.POINTER(i32), i32, i32, i32, i32, i32, vp, i32, vp]),
     "dynenv_arrange_fixed_pad_backward_as": (C.c_int, [vp, i32, vp, C.POINTER(i32), i32, i32, i32, i32, i32, C.POINTER(vp), i32, vp]),
+    "dynenv_arrange_embed_pad": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, i32, C.POINTER(EmbedBlock), i32, C.c_float, C.c_float,
+                                           vp, i32, vp]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -21,6 +21,10 @@ capturable into a graph.
 In both modes `padded_dtype=torch.bfloat16` (or float16) writes the padded tensor in that type, for a network under torch.autocast
 (`dynenv_arrange_*_as`, csrc/arranger_cols_kernels.hip): float32 embeddings are converted on the way (round to nearest even), embeddings
 already of that type are copied bit for bit, and the backward hands every embedding a gradient of its own type.
+
+`GpuEmbedInputLayer` is the reference's whole InputLayer (models.py:278-307), its EmbedBlocks (:99-124) included: the three calls above
+when a gradient is wanted, and otherwise ONE kernel from the observation rows to the padded tensor (`dynenv_arrange_embed_pad`,
+csrc/arranger_embed_kernels.hip) - no inputs[i], no activation and no embedding is written or read back.
 """
 import ctypes as C
 import os
@@ -451,7 +455,142 @@ def _input_layer_class():
     return _lazy["layer"]
 
 
+def _embed_classes():
+    if "embed" not in _lazy:
+        import torch
+        nn = torch.nn
+
+        class EmbedBlock(nn.Module):
+            """The reference's embedding block for one object type (models.py:99-124), parameter for parameter and name for name:
+            Linear(feat -> F/2, no bias), LeakyReLU(0.1), LayerNorm(F/2), Linear(F/2 -> F, no bias), LeakyReLU(0.1), LayerNorm(F)."""
+
+            def __init__(self, inputs, features, device=None):
+                super().__init__()
+                self.Layer1 = nn.Linear(inputs, features // 2, bias=False, device=device)
+                self.relu = nn.LeakyReLU(0.1)
+                self.bn1 = nn.LayerNorm(features // 2, device=device)
+                self.Layer2 = nn.Linear(features // 2, features, bias=False, device=device)
+                self.bn2 = nn.LayerNorm(features, device=device)
+
+            def forward(self, x):
+                x = self.bn1(self.relu(self.Layer1(x)))
+                return self.bn2(self.relu(self.Layer2(x)))
+
+        class GpuEmbedInputLayer(nn.Module):
+            """The reference's WHOLE InputLayer (models.py:278-307) over the dense observation tensor, embedding blocks included:
+            GpuEmbedInputLayer(types, features, nEnvs, nAgents, nTime, obs_dim, fixed=None, padded_dtype=None) owns `blocks`, one EmbedBlock
+            (models.py:99-124) per object type of `types` (groups_for(env)[...]), created on the arranger's device under the reference's
+            parameter names (Layer1.weight, bn1.weight, bn1.bias, Layer2.weight, bn2.weight, bn2.bias): an InputLayer.state_dict() of
+            the reference loads with strict=True.  forward(obs, count_env=None) -> (padded [T, maxCount, E*A, F], masks) with the shapes,
+            masks, `arranger.dropped` accounting and `padded_dtype` meaning of GpuInputLayer (fixed=, padded_dtype=: GpuInOutArranger).
+
+            Two routes; `last_route` names the one the latest forward took.
+              "blocks"  when gradients are enabled and a parameter requires one: GpuInputLayer's route - rearrange_inputs, the blocks
+                        as torch modules, rearrange_outputs - unchanged and differentiable.
+              "fused"   otherwise (acting in a rollout, evaluation, look-ahead, the no_grad value bootstrap): one kernel reads the
+                        observation rows and writes the padded tensor (dynenv_arrange_embed_pad, csrc/arranger_embed_kernels.hip);
+                        neither inputs[i], nor an activation, nor the embeddings exist.  Fixed mode: dynenv_arrange_fixed_gather without
+                        inputs (counts, mask, dropped), then the kernel - nothing is waited for, so the route is capturable.  Default
+                        mode: dynenv_arrange_plan (its one synchronisation, as ever), the gather for the mask alone, then the kernel.
+              "blocks (fallback: ...)"  where no gradient is wanted but the kernel does not take the module: F other than 64 or 128, a
+                        type of more than 16 features, parameters that are not float32, contiguous and on the arranger's device, a
+                        LayerNorm without affine parameters - or DYNENV_ARR_EMBED_FUSED=0 in the environment.  Nothing is raised.
+            AUTOCAST.  The fused route computes in float32 whatever torch.autocast says - only the store converts, to `padded_dtype` -
+            while the unfused route's Linears run in 16 bits under autocast (its LayerNorms stay float32): under autocast the two
+            routes differ by the 16-bit rounding of the two products, the fused one being the more exact."""
+
+            def __init__(self, types, features, nEnvs, nAgents, nTime, obs_dim, fixed=None, padded_dtype=None):
+                super().__init__()
+                self.arranger = GpuInOutArranger(types, nEnvs, nAgents, nTime, obs_dim, fixed=fixed, padded_dtype=padded_dtype)
+                self.features = int(features)
+                self.blocks = nn.ModuleList([EmbedBlock(int(t.feat), self.features, device=self.arranger.device) for t in types])
+                self.last_route = None
+
+            def _not_fusable(self):
+                """why the kernel does not take this module as it stands, or None"""
+                arr = self.arranger
+                if os.environ.get("DYNENV_ARR_EMBED_FUSED", "1") == "0":
+                    return "DYNENV_ARR_EMBED_FUSED=0"
+                if self.features not in (64, 128):
+                    return "F = %d, not 64 or 128" % self.features
+                if max(arr.feats) > 16:
+                    return "an object type of more than 16 features"
+                b0 = self.blocks[0]
+                for b in self.blocks:
+                    if (b.bn1.eps, b.bn2.eps, b.relu.negative_slope) != (b0.bn2.eps, b0.bn2.eps, b0.relu.negative_slope):
+                        return "blocks that differ in eps or slope"
+                    if not (b.bn1.elementwise_affine and b.bn2.elementwise_affine and b.bn1.bias is not None and b.bn2.bias is not None):
+                        return "a LayerNorm without affine parameters"
+                    for p in b.parameters():
+                        if p.dtype != torch.float32 or not p.is_contiguous() or p.device != arr.device:
+                            return "parameters that are not float32, contiguous and on %s" % (arr.device,)
+                return None
+
+            def forward(self, obs, count_env=None):
+                if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+                    self.last_route = "blocks"
+                    return self._forward_blocks(obs, count_env)
+                why = self._not_fusable()
+                if why is not None:
+                    self.last_route = "blocks (fallback: %s)" % why
+                    return self._forward_blocks(obs, count_env)
+                self.last_route = "fused"
+                return self._forward_fused(obs, count_env)
+
+            def _forward_blocks(self, obs, count_env):
+                inputs, countArr = self.arranger.rearrange_inputs(obs, count_env)
+                outs = [block(x) if x.shape[0] else None for block, x in zip(self.blocks, inputs)]
+                return self.arranger.rearrange_outputs(outs, countArr)
+
+            def _forward_fused(self, obs, count_env):
+                arr = self.arranger
+                lib, vp, n = arr._lib, C.c_void_p, arr.nObjectTypes
+                assert obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous()
+                assert tuple(obs.shape) == (arr.E, arr.nTime, arr.A, arr.D), (tuple(obs.shape), (arr.E, arr.nTime, arr.A, arr.D))
+                i32 = dict(dtype=torch.int32, device=arr.device)
+                counts = torch.empty((n, arr.nTime, arr.nPlayers), **i32)
+                obj_counts = torch.empty((arr.nTime, arr.nPlayers), **i32)
+                if arr.fixed:
+                    max_count = arr.max_count
+                    mask = torch.empty((arr.nTime, arr.nPlayers, max_count), dtype=torch.uint8, device=arr.device)
+                    _capi.check(lib.dynenv_arrange_fixed_gather(_capi.ptr(obs), arr.E, arr.nTime, arr.A, arr.D, arr.types, n, _capi.ptr(count_env),
+                                                                arr._rows_c, max_count, _capi.ptr(counts), _capi.ptr(obj_counts), None,
+                                                                _capi.ptr(mask) if max_count else vp(0), _capi.ptr(arr.dropped), arr._stream()),
+                                "dynenv_arrange_fixed_gather")
+                else:
+                    base = torch.empty((n, arr.nTime, arr.nPlayers), **i32)
+                    plan = _capi.ArrPlan()
+                    _capi.check(lib.dynenv_arrange_plan(_capi.ptr(obs), arr.E, arr.nTime, arr.A, arr.D, arr.types, n, _capi.ptr(count_env),
+                                                        _capi.ptr(counts), _capi.ptr(obj_counts), _capi.ptr(base), _capi.ptr(arr._scratch),
+                                                        C.byref(plan), arr._stream()), "dynenv_arrange_plan")
+                    max_count = int(plan.max_count)
+                    mask = torch.empty((arr.nTime, arr.nPlayers, max_count), dtype=torch.uint8, device=arr.device)
+                    if max_count:   # (the gather for the mask alone: no inputs, no slots)
+                        _capi.check(lib.dynenv_arrange_gather(_capi.ptr(obs), arr.E, arr.nTime, arr.A, arr.D, arr.types, n, _capi.ptr(counts),
+                                                              _capi.ptr(base), max_count, None, None, _capi.ptr(mask), arr._stream()),
+                                    "dynenv_arrange_gather")
+                padded_dtype = arr.padded_dtype or torch.float32
+                padded = torch.empty((arr.nTime, max_count, arr.nPlayers, self.features), dtype=padded_dtype, device=arr.device)
+                if max_count:
+                    blocks = (_capi.EmbedBlock * n)(*[_capi.EmbedBlock(*[p.data_ptr() for p in (b.Layer1.weight, b.bn1.weight, b.bn1.bias,
+                                                                                               b.Layer2.weight, b.bn2.weight, b.bn2.bias)])
+                                                      for b in self.blocks])
+                    b0 = self.blocks[0]
+                    _capi.check(lib.dynenv_arrange_embed_pad(_capi.ptr(obs), arr.E, arr.nTime, arr.A, arr.D, arr.types, n, _capi.ptr(counts), max_count,
+                                                             blocks, self.features, float(b0.relu.negative_slope), float(b0.bn2.eps),
+                                                             _capi.ptr(padded), arr._DTYPE_CODES[str(padded_dtype)], arr._stream()),
+                                "dynenv_arrange_embed_pad")
+                self.last_counts, self.last_obj_counts = counts, obj_counts   # (the latest fused call's plan, for whoever wants the counts)
+                return padded, [mask[t].bool() for t in range(arr.nTime)]
+
+        EmbedBlock.__qualname__, GpuEmbedInputLayer.__qualname__ = "EmbedBlock", "GpuEmbedInputLayer"
+        _lazy["embed"] = (EmbedBlock, GpuEmbedInputLayer)
+    return _lazy["embed"]
+
+
 def __getattr__(name):
     if name == "GpuInputLayer":
         return _input_layer_class()
+    if name in ("EmbedBlock", "GpuEmbedInputLayer"):
+        return _embed_classes()[name == "GpuEmbedInputLayer"]
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -555,6 +555,39 @@ int dynenv_arrange_fixed_pad_backward_as(const void* grad_padded_dev, int32_t pa
                                          const int32_t* rows, int32_t n_types, int32_t T, int32_t P, int32_t max_count, int32_t F,
                                          void* const* grad_emb_dev, int32_t emb_dtype, void* stream);
 
+/* ---- embed and pad in ONE pass, where no gradient is wanted: the reference's whole InputLayer (models.py:278-307) - rearrange_inputs,
+ * one EmbedBlock per object type (models.py:99-124), rearrange_outputs - from the observation row straight to the padded tensor.
+ * Neither inputs[i], nor an activation, nor the embeddings exist in memory.  One EmbedBlock, float32, in torch's layouts:
+ *   h = LayerNorm(LeakyReLU(w1 x)),  y = LayerNorm(LeakyReLU(w2 h)):  Linear(feat -> F/2, no bias), LeakyReLU(slope), LayerNorm(F/2),
+ *   Linear(F/2 -> F, no bias), LeakyReLU(slope), LayerNorm(F);  LayerNorm as torch defines it: biased variance,
+ *   (x - mean) / sqrt(var + eps) * w + b. */
+typedef struct dynenv_embed_block {
+  const float *w1;            /* [F/2][feat]  Layer1.weight */
+  const float *ln1_w, *ln1_b; /* [F/2]        bn1 */
+  const float *w2;            /* [F][F/2]     Layer2.weight */
+  const float *ln2_w, *ln2_b; /* [F]          bn2 */
+} dynenv_embed_block_t;
+/* dynenv_arrange_embed_pad, one launch, capturable (launches only: nothing is synchronised or allocated; pointers and sizes are frozen
+ * by a capture, contents are read at replay): padded_dev [T][max_count][P][F] of padded_dtype (DYNENV_ARR_F32 / _BF16 / _F16), P = E*A,
+ * p = e*A + a.  Slot j = sum_{i'<i} k_i' + r, r < k_i, holds block_i(obs[e][t][a][offset_i + r*feat_i .. + feat_i]); every slot behind
+ * the player's last object holds +0.0; EVERY element is written exactly once - no pre-zeroing, no second pass.  counts_dev int32
+ * [n_types][T][P] is what dynenv_arrange_plan or dynenv_arrange_fixed_gather wrote; the kernel clamps each count to 0..cap_i and to the
+ * slots left (k_i), so reads and writes stay in bounds whatever the buffer holds.  Neither `base` nor `rows` is needed - the call reads
+ * the observation row itself - so it serves the default and the fixed-shape mode.  blocks is a HOST array of n_types entries of device
+ * pointers; an entry has all six pointers or none: a type all of whose counts are zero may leave them NULL (a type with objects and
+ * NULL weights gets +0.0 in its slots, as a NULL embedding does in dynenv_arrange_pad_as).
+ * Arithmetic: float32 throughout, every sum in one fixed order: an object's result depends on its features and its type alone - not
+ * on its slot, its lane or the batch around it - and the same call twice gives the same bits.  A 16-bit padded tensor is the float32
+ * result converted at the store by the contract above (round to nearest, ties to even).
+ * Errors, DYNENV_ERR_ARG, all reported before a device is looked for: a NULL obs_dev, types, counts_dev, blocks or padded_dev; E, T, A or
+ * D < 1; n_types outside 1..DYNENV_ARR_MAX_TYPES; a type outside the observation row; a dtype outside 0..2; max_count < 0; padded_dev
+ * not 16-byte aligned; T * max_count * P >= 2^31, max_count >= 2^23 or E * T * A > 2^30 (the launch limits); a block with some but not all of its pointers.
+ * Then what the kernels do not take: F other than 64 or 128, or a feat_i above 16: DYNENV_ERR_UNSUPPORTED, also before the device.
+ * max_count == 0 launches nothing and returns DYNENV_OK. */
+int dynenv_arrange_embed_pad(const float* obs_dev, int32_t E, int32_t T, int32_t A, int32_t D, const dynenv_arr_type_t* types,
+                             int32_t n_types, const int32_t* counts_dev, int32_t max_count, const dynenv_embed_block_t* blocks,
+                             int32_t F, float slope, float eps, void* padded_dev, int32_t padded_dtype, void* stream);
+
 
 /* Device self-test of the deterministic math header: evaluates sincos/atan2/sqrt/div on n host-provided doubles and
  * returns the raw results so tests can compare them bit-for-bit with the host evaluation. out: [n,5]. */

@@ -11,7 +11,14 @@ algorithmic bytes of the backward are 2 * n_obj * F * 4 (every gradient row read
 --padded-dtype bf16|f16 adds, from the same run and on the same plan, the padded tensor in that type (GpuInOutArranger(padded_dtype=...))
 beside the float32 one: the float32 leg, the converting leg (float32 embeddings) and the same-type leg (embeddings already in that type;
 --emb-dtype keeps one of the two), forward only or, with --backward, forward and backward, the legs taking turns inside every
-repetition; per leg the device time (median, min .. max over --reps), the bytes moved and its time relative to the float32 leg."""
+repetition; per leg the device time (median, min .. max over --reps), the bytes moved and its time relative to the float32 leg.
+
+--fused-embed adds, from the same run and on the same observations, the whole input layer with its embedding blocks (GpuEmbedInputLayer):
+the fused route (dynenv_arrange_embed_pad: observation rows in, padded tensor out) against the unfused route of the same module
+(rearrange_inputs, the blocks as torch modules, rearrange_outputs), under no_grad, the two taking turns inside every repetition, for
+F = 128 and 64, a float32 and a bf16 padded tensor, the default and the fixed-shape mode (rows = capacities); per leg the device time
+(median, min .. max) of a whole forward, and for the fused leg the bytes it moves (object rows read, every padded element written,
+counts and mask) and TB/s, its FLOP rate, and the unfused leg's time over its own."""
 import argparse
 import json
 import os
@@ -124,6 +131,52 @@ def dtype_legs(torch, GpuInOutArranger, shape, countArr, n_obj, args, plan_bytes
     return out
 
 
+def fused_embed_legs(torch, GpuEmbedInputLayer, shape, obs, count_env, args):
+    """{F: {padded dtype: {mode: {fused, blocks, speedup}}}} of GpuEmbedInputLayer's two routes on one batch"""
+    import statistics
+    types, E, A, T, D = shape
+    out = {}
+    for F in (128, 64):
+        for pk, pdt in (("f32", None), ("bf16", torch.bfloat16)):
+            for mode, fixed in (("default", None), ("fixed", True)):
+                torch.manual_seed(F)
+                layer = GpuEmbedInputLayer(types, F, E, A, T, D, fixed=fixed, padded_dtype=pdt).requires_grad_(False)
+                legs = {"fused": lambda: layer(obs, count_env), "blocks": lambda: layer._forward_blocks(obs, count_env)}
+                with torch.no_grad():
+                    padded, _ = legs["fused"]()
+                    assert layer.last_route == "fused", layer.last_route
+                    ref, _ = legs["blocks"]()
+                    err = float((padded.float() - ref.float()).abs().max())
+                    for fn in legs.values():   # warm-up of every shape
+                        for _ in range(2):
+                            fn()
+                    torch.cuda.synchronize()
+                    times = {k: [] for k in legs}
+                    for _ in range(args.reps):
+                        for k, fn in legs.items():
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record()
+                            for _i in range(args.inner):
+                                fn()
+                            e1.record()
+                            e1.synchronize()
+                            times[k].append(e0.elapsed_time(e1) / args.inner)
+                n_obj = [int(v) for v in layer.last_counts.clamp(min=0).sum((1, 2)).tolist()]
+                TP = T * E * A
+                nbytes = sum(n * t.feat * 4 for n, t in zip(n_obj, types)) + padded.numel() * padded.element_size() + TP * len(types) * 8 + TP * padded.shape[1]
+                flop = sum(n * 2 * (t.feat * F // 2 + F * F // 2) for n, t in zip(n_obj, types))
+                res = {}
+                for k, t in times.items():
+                    res[k] = {"median_ms": statistics.median(t), "min_ms": min(t), "max_ms": max(t)}
+                fm = res["fused"]["median_ms"]
+                res["fused"].update(bytes_moved=nbytes, achieved=nbytes / (fm * 1e-3) / 1e12, unit="TB/s", tflops=flop / (fm * 1e-3) / 1e12)
+                res["speedup"] = res["blocks"]["median_ms"] / fm
+                res["objects"], res["max_count"], res["max_abs_difference"] = n_obj, int(padded.shape[1]), err
+                out.setdefault("F%d" % F, {}).setdefault(pk, {})[mode] = res
+                del layer, padded, ref
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
@@ -135,12 +188,14 @@ def main():
                     help="bf16 / f16: also time rearrange_outputs with a padded tensor of that type, beside the float32 leg, in the same run")
     ap.add_argument("--emb-dtype", choices=("f32", "bf16", "f16"), default=None,
                     help="with --padded-dtype: the embeddings' type of the 16-bit leg, f32 (converting) or the padded type (bit copy); default both")
+    ap.add_argument("--fused-embed", action="store_true",
+                    help="also time GpuEmbedInputLayer's fused route (embed and pad in one kernel) against its unfused route, in the same run")
     args = ap.parse_args()
     import numpy as np
     import torch
     import arranger as oa
     from compat_ref import compat_obs_of
-    from dynenv_amd import BatchedDynEnv, DynEnvType, GpuInOutArranger, NoiseType, ObservationType, groups_for
+    from dynenv_amd import BatchedDynEnv, DynEnvType, GpuEmbedInputLayer, GpuInOutArranger, NoiseType, ObservationType, groups_for
     E = args.envs
     for cfg in ("driving_full", "robocup", "driving_partial"):
         if cfg == "robocup":
@@ -195,6 +250,9 @@ def main():
         if args.padded_dtype != "f32":
             dt = dtype_legs(torch, GpuInOutArranger, (types, E, env.n_agents, env.n_time_steps, env.obs_dim), countArr, n_obj, args,
                             TP * len(types) * 8)
+        fe = None
+        if args.fused_embed:
+            fe = fused_embed_legs(torch, GpuEmbedInputLayer, (types, E, env.n_agents, env.n_time_steps, env.obs_dim), obs, count_env, args)
         print(json.dumps({
             "metric": "arranged agent-observations/s", "config": cfg, "envs": E, "players": E * env.n_agents,
             "time_steps": env.n_time_steps, "objects": n_obj, "max_count": countArr[1], "embed_width": args.feat,
@@ -208,6 +266,7 @@ def main():
                              "sample": "oracle/arranger.py (numpy restatement of InOutArranger) on the first %d envs, %.2f s" % (Es, cpu_s)},
             **({"backward": bwd} if bwd is not None else {}),
             **({"padded_dtype": {"dtype": args.padded_dtype, "reps": args.reps, "inner": args.inner, "legs": dt}} if dt is not None else {}),
+            **({"fused_embed": {"reps": args.reps, "inner": args.inner, "legs": fe}} if fe is not None else {}),
         }))
         env.close()
 
