@@ -8,11 +8,14 @@ from .vec_env import BatchedDynEnv, make_dyn_env
 from .arranger import GpuInOutArranger, groups_for
 
 __all__ = ["BatchedDynEnv", "make_dyn_env", "DynEnvType", "NoiseType", "ObservationType", "GpuInOutArranger", "GpuInputLayer",
-           "GpuEmbedInputLayer", "EmbedBlock", "groups_for"]
+           "GpuEmbedInputLayer", "EmbedBlock", "GpuTemporalAttention", "groups_for"]
 
 
 def __getattr__(name):
     if name in ("GpuInputLayer", "GpuEmbedInputLayer", "EmbedBlock"):   # nn.Modules: built on first use, so that the package imports without torch
         from . import arranger
         return getattr(arranger, name)
+    if name == "GpuTemporalAttention":
+        from . import attention
+        return attention.GpuTemporalAttention
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -91,6 +91,10 @@ class EmbedBlock(C.Structure):  # dynenv_embed_block_t: device pointers of one E
     _fields_ = [(n, C.c_void_p) for n in ("w1", "ln1_w", "ln1_b", "w2", "ln2_w", "ln2_b")]
 
 
+class Mha(C.Structure):  # dynenv_mha_t: device pointers of one nn.MultiheadAttention(F, 1, add_bias_kv=True); the first four 16 bit, the last two float32
+    _fields_ = [(n, C.c_void_p) for n in ("in_w", "out_w", "bias_k", "bias_v", "in_b", "out_b")]
+
+
 vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
 
 # THE binding of include/dynenv.h: name -> (restype, argtypes), in the header's order of growth.  load() sets exactly these, so an entry
@@ -154,6 +158,7 @@ SIGNATURES = {
     "dynenv_arrange_fixed_pad_backward_as": (C.c_int, [vp, i32, vp, C.POINTER(i32), i32, i32, i32, i32, i32, C.POINTER(vp), i32, vp]),
     "dynenv_arrange_embed_pad": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, i32, C.POINTER(EmbedBlock), i32, C.c_float, C.c_float,
                                            vp, i32, vp]),
+    "dynenv_attend_pool": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, C.POINTER(Mha), C.POINTER(Mha), vp, vp, C.c_float, vp, vp, vp, vp]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -588,6 +588,49 @@ int dynenv_arrange_embed_pad(const float* obs_dev, int32_t E, int32_t T, int32_t
                              int32_t n_types, const int32_t* counts_dev, int32_t max_count, const dynenv_embed_block_t* blocks,
                              int32_t F, float slope, float eps, void* padded_dev, int32_t padded_dtype, void* stream);
 
+/* ---- attention over the padded tensor in ONE launch, where no gradient is wanted: the reference's RecurrentTemporalAttention
+ * (models.py:311-386), from the 16-bit padded tensor and the object counts to the pooled feature of every player.  Neither q, k, v,
+ * the probabilities nor an attention output exist in memory.  One nn.MultiheadAttention(F, 1, add_bias_kv=True), in torch's layouts:
+ * the four matrices and the two bias rows in the padded tensor's 16-bit type (the operands of the matrix units), the two bias vectors
+ * float32. */
+typedef struct dynenv_mha {
+  const void *in_w;            /* [3F][F]  in_proj_weight: Wq, Wk, Wv     (padded_dtype) */
+  const void *out_w;           /* [F][F]   out_proj.weight                (padded_dtype) */
+  const void *bias_k, *bias_v; /* [F]      bias_k, bias_v                 (padded_dtype) */
+  const float *in_b;           /* [3F]     in_proj_bias: bq, bk, bv */
+  const float *out_b;          /* [F]      out_proj.bias */
+} dynenv_mha_t;
+/* dynenv_attend_pool, one launch, capturable (a launch and nothing else: nothing is synchronised, allocated or copied; pointers and
+ * sizes are frozen by a capture, contents are read at replay): out_dev float32 [P][F], EVERY element written exactly once.
+ * padded_dev is [T][M][P][F] of padded_dtype (DYNENV_ARR_BF16 / _F16), obj_counts_dev int32 [T][P] (what dynenv_arrange_plan or
+ * dynenv_arrange_fixed_gather wrote); obj_att and temp_att are HOST structs of device pointers, ln_w_dev / ln_b_dev [F] and ln_eps the
+ * LayerNorm `bn`, conf_w_dev [F] and conf_b_dev [1] the Linear of `confLayer`, all float32 on the device.  For player p, with c_t its
+ * count at time t clamped to 0..M, n = max_t c_t and X_t its M slots at time t, every slot at or behind c_t taken as +0.0 WITHOUT
+ * being read (the masks of the arranger are prefixes: True from the count on):
+ *   mha(w; Qin, KVin, k):  q = Qin Wq^T + bq;  K = KVin[:k] Wk^T + bk with the row bias_k appended, V likewise with bias_v;
+ *                          softmax(q K^T / sqrt(F)) over the k + 1 keys (the bias key is never masked: a row of probabilities always
+ *                          exists);  the result is (probs V) Wo^T + bo
+ *   att_t = mha(obj_att; X_t[:n], X_t, c_t) for every t - the query rows between c_t and n are zero rows, q = bq, and they count;
+ *   fin = att_0, k = c_0;  for t = 1..T-1: fin = LayerNorm(mha(temp_att; att_t, fin, k)), then k = max(k, c_t) (models.py:362-363:
+ *   the temporal keys take the mask from before the update);
+ *   out[p] = sum_{r < n} sigmoid(fin_r . conf_w + conf_b) fin_r / n, and +0.0 where n == 0.  Rows at or behind n are never computed.
+ * M == 0 writes +0.0 everywhere and returns DYNENV_OK (the reference returns the sum over an empty axis, models.py:376-377);
+ * padded_dev may then be NULL.
+ * Arithmetic: every matrix product takes 16-bit operands (padded_dtype) on the matrix units and accumulates in float32; biases,
+ * softmax, LayerNorm, the sigmoid and the pooled mean are float32 - what torch.autocast does to the reference's layer, with one
+ * rounding fewer where a product feeds the next from registers.  Every sum has one fixed order: a player's result depends on its own
+ * slots and counts alone - not on p, on M or on the batch - and the same call twice gives the same bits.  Inputs that are not finite
+ * are outside the contract.
+ * Errors, DYNENV_ERR_ARG, all reported before a device is looked for: a NULL obj_counts_dev, obj_att, temp_att, ln_w_dev, ln_b_dev,
+ * conf_w_dev, conf_b_dev or out_dev, a NULL padded_dev with M > 0, an attention with fewer than its six pointers; T, P or F < 1,
+ * M < 0; a dtype outside 0..2; padded_dev, out_dev or a weight, LayerNorm or conf_w buffer not 16-byte aligned (bias_k, bias_v: 8-byte);
+ * T * P > 2^30 (the launch limit).  Then what the kernel does not take: DYNENV_ARR_F32, an F other than 64 or 128, M > 128:
+ * DYNENV_ERR_UNSUPPORTED, also before the device. */
+int dynenv_attend_pool(const void* padded_dev, int32_t padded_dtype, const int32_t* obj_counts_dev, int32_t T, int32_t M, int32_t P,
+                       int32_t F, const dynenv_mha_t* obj_att, const dynenv_mha_t* temp_att, const float* ln_w_dev,
+                       const float* ln_b_dev, float ln_eps, const float* conf_w_dev, const float* conf_b_dev, float* out_dev,
+                       void* stream);
+
 
 /* Device self-test of the deterministic math header: evaluates sincos/atan2/sqrt/div on n host-provided doubles and
  * returns the raw results so tests can compare them bit-for-bit with the host evaluation. out: [n,5]. */
