@@ -39,20 +39,24 @@ struct __align__(16) DrvLds {
   // dynamic bodies (lane l = body l): home location of the state
   double px[DRV_NB], py[DRV_NB], vx[DRV_NB], vy[DRV_NB], ang[DRV_NB], w[DRV_NB], vbx[DRV_NB], vby[DRV_NB], wb[DRV_NB];
   double minv[DRV_NB], iinv[DRV_NB];
-  double rc[16], rs[16], rotAng[16];  // cars: cos/sin of rotAng (recomputed only when the angle changes)
-  // cars
-  double dirx[16], diry[16], prevx[16], prevy[16], goalx[16], goaly[16];
-  double cosRel0[16];  // dm_cos(road0.dirAngle - rotAng), cached with rc/rs.  (Road 1 has dirAngle 0: dm_cos(0 - a) is dm_cos(a) = rc bit for
+  // cars.  (Every per-car array has DRV_MAXA rows: a lane that is no car reads row DRV_MAXA - 1, see `ci` in drv_light_substep.)
+  double rc[DRV_MAXA], rs[DRV_MAXA], rotAng[DRV_MAXA];  // cos/sin of rotAng (recomputed only when the angle changes)
+  double dirx[DRV_MAXA], diry[DRV_MAXA], prevx[DRV_MAXA], prevy[DRV_MAXA], goalx[DRV_MAXA], goaly[DRV_MAXA];
+  double cosRel0[DRV_MAXA];  // dm_cos(road0.dirAngle - rotAng), cached with rc/rs.  (Road 1 has dirAngle 0: dm_cos(0 - a) is dm_cos(a) = rc bit for
                        // bit - dm_sincos negates fn and r exactly with its argument, the cosine kernel is even and the quadrant cases pair up)
-  double dprev[16];                 // |prevPos - goal|
-  double cmass[16], cpower[16], chx[16], chy[16];  // per-car constants (Car.py:9-12) copied out of constant memory
+  double dprev[DRV_MAXA];           // |prevPos - goal|
+  double cmass[DRV_MAXA], cpower[DRV_MAXA], chx[DRV_MAXA], chy[DRV_MAXA];  // per-car constants (Car.py:9-12) copied out of constant memory
   double aabb[DRV_MAXA][4];
+  // The four world corners of every car, in box_world's order: written by the position update of drv_light_substep together with
+  // aabb (same condition: a frozen car keeps its corners), read by the pair tests of the contact path.  Like aabb it is valid from
+  // the first substep of a launch on and is not part of the state.
+  V2 cv[DRV_MAXA][4];
   int flags[DRV_NB], moving[DRV_NB];
   double ox[DRV_MAXO], oy[DRV_MAXO];
   // contact cache slots (lane s = slot s)
   int s_pair[DRV_NS], s_meta[DRV_NS], s_hash0[DRV_NS], s_hash1[DRV_NS];
   double s_jn0[DRV_NS], s_jt0[DRV_NS], s_jn1[DRV_NS], s_jt1[DRV_NS];
-  double rewAcc[16], posAcc[16];  // the step's reward / positive-reward accumulators of the cars (:252-254): in LDS, not carried
+  double rewAcc[DRV_MAXA], posAcc[DRV_MAXA];  // the step's reward / positive-reward accumulators of the cars (:252-254): in LDS, not carried
                                   // through the substep loop in registers (two doubles less to save around every call)
   // Per-lane values the step carries from substep to substep live HERE, not in the kernel's registers: whatever the kernel holds in
   // VGPRs across the call of the solver (124 VGPRs) is spilled around it, 256 B of scratch per register and call.
@@ -220,18 +224,37 @@ struct EdgeW {
   int ah, bh;
 };
 
-// A box by its parameters.  The narrowphase derives vertices and normals from these on demand (same arithmetic as
-// box_world) instead of holding two expanded boxes (64 doubles) in registers, which spilled to scratch.
-struct BoxP {
-  V2 p;
-  double c, s, hx, hy;
+// A box as the pair tests see it: its four world corners and its rotation.  The corners are never computed here.  A car's are the
+// ones its position update stored (L.cv: box_world's arithmetic on the position, rotation and half extents the tile holds now - a
+// frozen car has not changed any of them since).  A static box has rotation (1, 0), so box_world's corner is
+//   x = fma(1, lx, fma(-0, ly, px)) = lx + px        y = fma(0, lx, fma(1, ly, py)) = ly + py
+// bit for bit, one add per component (as for the static boxes' AABB in drv_light_substep).  x: -0 * ly is a zero, px plus a zero is
+// px but for the sign of a zero, which the sum with lx != 0 does not see.  y: 0 * lx is a zero, and ly + py plus a zero is ly + py:
+// a sum that is zero is +0 (ly != 0, so it came from an exact cancellation), and +0 plus a zero of either sign is +0.
+// Normals are derived from the rotation on demand.
+struct BoxC {
+  V2 v[4], vq;  // the corners in box_world's order; corner q of the lane's quad role once more (loaded, not selected out of v)
+  double c, s;
 };
-DE_DEV V2 boxp_vertex(const BoxP& b, int i) {
-  const double lx = (i == 1 || i == 2) ? b.hx : -b.hx;
-  const double ly = (i >= 2) ? b.hy : -b.hy;
-  return v2(dms_xform_x(b.c, b.s, lx, ly, b.p.x), dms_xform_y(b.c, b.s, lx, ly, b.p.y));
+DE_DEV void boxc_car(const DrvLds& L, int i, int q, BoxC& b) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) b.v[k] = L.cv[i][k];
+  b.vq = L.cv[i][q];
+  b.c = L.rc[i]; b.s = L.rs[i];
 }
-DE_DEV V2 boxp_normal(const BoxP& b, int i) {
+DE_DEV void boxc_static(V2 p, double hx, double hy, int q, BoxC& b) {
+  const double x0 = -hx + p.x, x1 = hx + p.x, y0 = -hy + p.y, y1 = hy + p.y;
+  b.v[0] = v2(x0, y0); b.v[1] = v2(x1, y0); b.v[2] = v2(x1, y1); b.v[3] = v2(x0, y1);
+  b.vq = v2((q == 1 || q == 2) ? x1 : x0, (q >= 2) ? y1 : y0);
+  b.c = 1.0; b.s = 0.0;
+}
+DE_DEV V2 boxc_vertex(const BoxC& b, int i) {
+  // (all four read first, then selects of VALUES: a conditional over the members becomes a select of addresses, which keeps the
+  // box in scratch memory)
+  const V2 v0 = b.v[0], v1 = b.v[1], v2_ = b.v[2], v3 = b.v[3];
+  return v2(i == 0 ? v0.x : (i == 1 ? v1.x : (i == 2 ? v2_.x : v3.x)), i == 0 ? v0.y : (i == 1 ? v1.y : (i == 2 ? v2_.y : v3.y)));
+}
+DE_DEV V2 boxc_normal(const BoxC& b, int i) {
   const double nx = (i == 0) ? -1.0 : ((i == 2) ? 1.0 : 0.0);
   const double ny = (i == 1) ? -1.0 : ((i == 3) ? 1.0 : 0.0);
   return v2(b.c * nx - b.s * ny, b.s * nx + b.c * ny);
@@ -247,6 +270,7 @@ template <int S> DE_DEV double quad_bcast(double x) {
   hi = __builtin_amdgcn_update_dpp(hi, hi, S * 0x55, 0xF, 0xF, false);
   return __hiloint2double(hi, lo);
 }
+template <int S> DE_DEV int quad_bcast_i(int x) { return __builtin_amdgcn_update_dpp(x, x, S * 0x55, 0xF, 0xF, false); }
 // for (i = 0..3) if (v_i > best) { best = v_i; idx = i; }   starting from best = -inf, idx = 0
 DE_DEV void quad_argmax_first(double v, double& best, int& idx) {
   best = -INFINITY; idx = 0;
@@ -257,64 +281,62 @@ DE_DEV void quad_argmax_first(double v, double& best, int& idx) {
   m = quad_bcast<3>(v); if (m > best) { best = m; idx = 3; }
 }
 
-DE_DEV int poly_support_index(const BoxP& p, V2 n, int q) {
+DE_DEV int poly_support_index(const BoxC& p, V2 n) {
   double mx;
   int index;
-  quad_argmax_first(vdot_f(boxp_vertex(p, q), n), mx, index);
+  quad_argmax_first(vdot_f(p.vq, n), mx, index);
   return index;
 }
 
-DE_DEV EdgeW support_edge_poly(const BoxP& p, int slot, V2 n, int q) {
-  int i1 = poly_support_index(p, n, q);
-  int i0 = (i1 + 3) & 3;
-  int i2 = (i1 + 1) & 3;
-  int h = slot * 4;
-  V2 n1 = boxp_normal(p, i1), n2 = boxp_normal(p, i2);
+// The edge in front of the support corner i1 (i0 -> i1, normal i1) or the one behind it (i1 -> i2, normal i2): either way edge k
+// runs from corner k - 1 to corner k.
+DE_DEV EdgeW support_edge_poly(const BoxC& p, int slot, V2 n) {
+  const int i1 = poly_support_index(p, n);
+  const int i2 = (i1 + 1) & 3;
+  const int h = slot * 4;
+  const V2 n1 = boxc_normal(p, i1), n2 = boxc_normal(p, i2);
+  const bool front = vdot(n, n1) > vdot(n, n2);
+  const int ib = front ? i1 : i2, ia = (ib + 3) & 3;
   EdgeW e;
-  V2 vm = boxp_vertex(p, i1);
-  if (vdot(n, n1) > vdot(n, n2)) {
-    e.ap = boxp_vertex(p, i0); e.ah = h + i0; e.bp = vm; e.bh = h + i1; e.n = n1;
-  } else {
-    e.ap = vm; e.ah = h + i1; e.bp = boxp_vertex(p, i2); e.bh = h + i2; e.n = n2;
-  }
+  e.ap = boxc_vertex(p, ia); e.ah = h + ia; e.bp = boxc_vertex(p, ib); e.bh = h + ib; e.n = v2(front ? n1.x : n2.x, front ? n1.y : n2.y);
   return e;
 }
 
 DE_DEV int hash_pair(int a, int b) { return 1 + ((a << 8) | b); }
 
-DE_DEV void contact_points(const EdgeW& e1, const EdgeW& e2, V2 n, Contacts& out) {  // radius 0 edges
-  double d_e1_a = vcross(e1.ap, n), d_e1_b = vcross(e1.bp, n);
-  double d_e2_a = vcross(e2.ap, n), d_e2_b = vcross(e2.bp, n);
-  double e1_denom = 1.0 / (d_e1_b - d_e1_a + DE_DBL_MIN);
-  double e2_denom = 1.0 / (d_e2_b - d_e2_a + DE_DBL_MIN);
+// cpCollide's ContactPoints for two edges of radius 0.  Its two candidate contacts are independent of each other and so are its two
+// reciprocals, and a lone wave pays per instruction, not per lane: ONE instruction stream evaluates the first candidate and e1's
+// reciprocal on the even lanes of the quad, the second candidate and e2's reciprocal on the odd lanes (the operands that differ are
+// selected per lane).  The reciprocals and the second candidate's outcome then come from lanes 0 and 1 by DPP; the first candidate
+// is the lane's own, which holds on the even lanes - and only lane 0 of a quad speaks for the pair.  Both candidates are assembled
+// in ContactPoints' order: the first one first.  No branch in here: every lane of the quad is there for the DPP reads.
+DE_DEV void contact_points(const EdgeW& e1, const EdgeW& e2, V2 n, int q, Contacts& out) {
+  const bool odd = (q & 1) != 0;
+  const double d_e1_a = vcross(e1.ap, n), d_e1_b = vcross(e1.bp, n);
+  const double d_e2_a = vcross(e2.ap, n), d_e2_b = vcross(e2.bp, n);
+  const double denom = 1.0 / ((odd ? d_e2_b : d_e1_b) - (odd ? d_e2_a : d_e1_a) + DE_DBL_MIN);
+  const double e1_denom = quad_bcast<0>(denom), e2_denom = quad_bcast<1>(denom);
+  // first candidate: (d_e2_b - d_e1_a) * e1_denom, (d_e1_a - d_e2_a) * e2_denom, ids (e1.a, e2.b);  second: d_e2_a, d_e1_b, ids (e1.b, e2.a)
+  const V2 p1 = vadd(vmul(n, 0.0), vlerp(e1.ap, e1.bp, fclamp01_cp(((odd ? d_e2_a : d_e2_b) - d_e1_a) * e1_denom)));
+  const V2 p2 = vadd(vmul(n, -0.0), vlerp(e2.ap, e2.bp, fclamp01_cp(((odd ? d_e1_b : d_e1_a) - d_e2_a) * e2_denom)));
+  const int hit = vdot(vsub(p2, p1), n) <= 0.0 ? 1 : 0;
+  const bool hitA = quad_bcast_i<0>(hit) != 0, hitB = quad_bcast_i<1>(hit) != 0;
+  const V2 p1B = v2(quad_bcast<1>(p1.x), quad_bcast<1>(p1.y)), p2B = v2(quad_bcast<1>(p2.x), quad_bcast<1>(p2.y));
+  const int hA = hash_pair(e1.ah, e2.bh), hB = hash_pair(e1.bh, e2.ah);
   out.n = n;
-  out.count = 0;
-  {
-    V2 p1 = vadd(vmul(n, 0.0), vlerp(e1.ap, e1.bp, fclamp01_cp((d_e2_b - d_e1_a) * e1_denom)));
-    V2 p2 = vadd(vmul(n, -0.0), vlerp(e2.ap, e2.bp, fclamp01_cp((d_e1_a - d_e2_a) * e2_denom)));
-    double dist = vdot(vsub(p2, p1), n);
-    if (dist <= 0.0) { out.p1[0] = p1; out.p2[0] = p2; out.hash[0] = hash_pair(e1.ah, e2.bh); out.count = 1; }
-  }
-  {
-    V2 p1 = vadd(vmul(n, 0.0), vlerp(e1.ap, e1.bp, fclamp01_cp((d_e2_a - d_e1_a) * e1_denom)));
-    V2 p2 = vadd(vmul(n, -0.0), vlerp(e2.ap, e2.bp, fclamp01_cp((d_e1_b - d_e2_a) * e2_denom)));
-    double dist = vdot(vsub(p2, p1), n);
-    if (dist <= 0.0) {
-      int h = hash_pair(e1.bh, e2.ah);
-      if (out.count == 0) { out.p1[0] = p1; out.p2[0] = p2; out.hash[0] = h; }
-      else { out.p1[1] = p1; out.p2[1] = p2; out.hash[1] = h; }
-      out.count += 1;
-    }
-  }
+  out.count = (hitA ? 1 : 0) + (hitB ? 1 : 0);
+  out.p1[0] = v2(hitA ? p1.x : p1B.x, hitA ? p1.y : p1B.y); out.p2[0] = v2(hitA ? p2.x : p2B.x, hitA ? p2.y : p2B.y);
+  out.hash[0] = hitA ? hA : hB;
+  out.p1[1] = p1B; out.p2[1] = p2B; out.hash[1] = hB;  // (read only when both hit)
 }
 
-DE_DEV double sat_max_sep(const BoxP& a, const BoxP& b, int q, int& best) {
-  const V2 n = boxp_normal(a, q);
-  const double d0 = vdot_f(n, boxp_vertex(a, q));
+DE_DEV double sat_max_sep(const BoxC& a, const BoxC& b, int q, int& best) {
+  const V2 n = boxc_normal(a, q);
+  const double d0 = vdot_f(n, a.vq);
   double minv = INFINITY;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    double d = vdot_f(n, boxp_vertex(b, j)) - d0;
+    double d = vdot_f(n, b.v[j]) - d0;
     if (d < minv) minv = d;
   }
   double maxsep;
@@ -322,7 +344,7 @@ DE_DEV double sat_max_sep(const BoxP& a, const BoxP& b, int q, int& best) {
   return maxsep;
 }
 
-DE_DEV void poly_to_poly(const BoxP& p1, int slot1, const BoxP& p2, int slot2, int q, Contacts& out) {
+DE_DEV void poly_to_poly(const BoxC& p1, int slot1, const BoxC& p2, int slot2, int q, Contacts& out) {
   out.count = 0;
   int ia, ib;
   double sa = sat_max_sep(p1, p2, q, ia);
@@ -330,27 +352,28 @@ DE_DEV void poly_to_poly(const BoxP& p1, int slot1, const BoxP& p2, int slot2, i
   double sb = sat_max_sep(p2, p1, q, ib);
   if (sb > 0.0) return;
   V2 n;
-  if (sa >= sb) n = boxp_normal(p1, ia); else n = vneg(boxp_normal(p2, ib));
-  const EdgeW e1 = support_edge_poly(p1, slot1, n, q);
-  const EdgeW e2 = support_edge_poly(p2, slot2, vneg(n), q);
-  contact_points(e1, e2, n, out);
+  if (sa >= sb) n = boxc_normal(p1, ia); else n = vneg(boxc_normal(p2, ib));
+  const EdgeW e1 = support_edge_poly(p1, slot1, n);
+  const EdgeW e2 = support_edge_poly(p2, slot2, vneg(n));
+  contact_points(e1, e2, n, q, out);
 }
 
-DE_DEV void circle_to_poly(V2 c, double r, const BoxP& poly, int q, Contacts& out) {
+// (vp: corner q - 1 of the box, the start of the lane's edge)
+DE_DEV void circle_to_poly(V2 c, double r, const BoxC& poly, V2 vp, int q, Contacts& out) {
   out.count = 0;
   double maxsep;
   int best;
-  const V2 vq = boxp_vertex(poly, q);
-  quad_argmax_first(vdot(boxp_normal(poly, q), vsub(c, vq)), maxsep, best);
+  const V2 vq = poly.vq;
+  quad_argmax_first(vdot(boxc_normal(poly, q), vsub(c, vq)), maxsep, best);
   if (maxsep > r) return;
   if (maxsep <= 0.0) {
-    V2 fn = boxp_normal(poly, best);
+    V2 fn = boxc_normal(poly, best);
     V2 n = vneg(fn);
     V2 pb = vsub(c, vmul(fn, maxsep));
     out.n = n; out.p1[0] = vadd(c, vmul(n, r)); out.p2[0] = pb; out.hash[0] = 0; out.count = 1;
   } else {
     // lane q: closest point on edge (v[q-1], v[q]); then for (i = 0..3) if (dsq_i < bestd) take it
-    const V2 a = boxp_vertex(poly, (q + 3) & 3), b = vq;
+    const V2 a = vp, b = vq;
     const V2 d = vsub(b, a);
     const double t = fclamp01_cp(vdot(d, vsub(c, a)) / vlensq(d));
     const V2 pt = vadd(a, vmul(d, t));
@@ -365,7 +388,7 @@ DE_DEV void circle_to_poly(V2 c, double r, const BoxP& poly, int q, Contacts& ou
     if (bestd <= r * r) {
       double dist = dm_sqrt(bestd);
       V2 delta = vsub(bestp, c);
-      V2 n = (dist != 0.0) ? vmul(delta, 1.0 / dist) : vneg(boxp_normal(poly, best));
+      V2 n = (dist != 0.0) ? vmul(delta, 1.0 / dist) : vneg(boxc_normal(poly, best));
       out.n = n; out.p1[0] = vadd(c, vmul(n, r)); out.p2[0] = bestp; out.hash[0] = 0; out.count = 1;
     }
   }
@@ -547,7 +570,7 @@ DE_DEV void load_env(const DrvState& S, DrvLds& L, int e, int lane, int A, int n
     if (lane < A) { minv = 1.0 / DRV_BY_TYPE(carMass); iinv = 1.0 / DRV_BY_TYPE(carInertia); }
     else if (used) { minv = 1.0 / CarK::pedMass; iinv = 1.0 / CarK::pedInertia; }
     L.minv[lane] = minv; L.iinv[lane] = iinv;
-    if (lane < 16) { L.rc[lane] = 1.0; L.rs[lane] = 0.0; L.rotAng[lane] = 0.0; }
+    if (lane < DRV_MAXA) { L.rc[lane] = 1.0; L.rs[lane] = 0.0; L.rotAng[lane] = 0.0; }
     if (lane < A) {
       L.dirx[lane] = g_dirx; L.diry[lane] = g_diry;
       L.prevx[lane] = g_prevx; L.prevy[lane] = g_prevy; L.goalx[lane] = g_gx; L.goaly[lane] = g_gy;
@@ -1144,15 +1167,14 @@ DRV_PROF(nMath -= __builtin_amdgcn_s_memtime();)
     const int pr = isCand ? (int)L.clist[pass * 16 + (lane >> 2)] : 0xFFFF;
     if (isCand) {
       const int i = pr >> 8, j = pr & 0xFF;
-      BoxP b1;
-      b1.p = v2(L.px[i], L.py[i]); b1.c = L.rc[i]; b1.s = L.rs[i]; b1.hx = L.chx[i]; b1.hy = L.chy[i];
+      BoxC b1;
+      boxc_car(L, i, q, b1);
       if (j >= DRV_SLOT_PED && j < DRV_SLOT_OBST) {
-        circle_to_poly(v2(L.px[j], L.py[j]), DRV_PED_R, b1, q, ct);
+        circle_to_poly(v2(L.px[j], L.py[j]), DRV_PED_R, b1, L.cv[i][(q + 3) & 3], q, ct);
       } else {  // car or static box: one instance of the SAT + clipping code for both
-        BoxP b2;
-        b2.c = 1.0; b2.s = 0.0;
-        if (j < DRV_SLOT_PED) { b2.p = v2(L.px[j], L.py[j]); b2.c = L.rc[j]; b2.s = L.rs[j]; b2.hx = L.chx[j]; b2.hy = L.chy[j]; }
-        else { b2.p = static_pos(L, j); b2.hx = j >= DRV_SLOT_BLD ? DRV_BLD_HX : DRV_OBST_H; b2.hy = j >= DRV_SLOT_BLD ? DRV_BLD_HY : DRV_OBST_H; }
+        BoxC b2;
+        if (j < DRV_SLOT_PED) boxc_car(L, j, q, b2);
+        else boxc_static(static_pos(L, j), j >= DRV_SLOT_BLD ? DRV_BLD_HX : DRV_OBST_H, j >= DRV_SLOT_BLD ? DRV_BLD_HY : DRV_OBST_H, q, b2);
         poly_to_poly(b1, i, b2, j, q, ct);
       }
     }
@@ -1478,7 +1500,7 @@ DRV_PROF(const unsigned long long Q0 = __builtin_amdgcn_s_memtime();)
     //      LDS round trip, ~110 cycles, and the phases below would otherwise make a dozen of them one after the other).  Indices are
     //      clamped into the arrays, the values of lanes without the role are never used.  What this function changes before a later
     //      use (velocity, angle, rotation cache) is tracked in these registers.
-    const int bi = lane & (DRV_NB - 1), ci = lane & 15;
+    const int bi = lane & (DRV_NB - 1), ci = lane < DRV_MAXA ? lane : DRV_MAXA - 1;
     int f = L.flags[bi];
     double px = L.px[bi], py = L.py[bi], vx = L.vx[bi], vy = L.vy[bi], ang = L.ang[bi];
     const double w = L.w[bi];
@@ -1640,6 +1662,8 @@ DRV_PROF(const unsigned long long Q3 = __builtin_amdgcn_s_memtime();)
             l = fmin_cp(l, bw.v[k].x); r = fmax_cp(r, bw.v[k].x); b = fmin_cp(b, bw.v[k].y); t = fmax_cp(t, bw.v[k].y);
           }
           bl = l - 0.0; bb = b - 0.0; br = r + 0.0; bt = t + 0.0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) L.cv[lane][k] = bw.v[k];
           L.aabb[lane][0] = bl; L.aabb[lane][1] = bb; L.aabb[lane][2] = br; L.aabb[lane][3] = bt;
         } else {
           bl = L.aabb[lane][0]; bb = L.aabb[lane][1]; br = L.aabb[lane][2]; bt = L.aabb[lane][3];
@@ -1883,7 +1907,7 @@ DRV_PROF(if (lane < 8 && e < 4096) { g_dbgp[e * 8 + lane] = 0ull; g_dbgs[e * 8 +
     if (lane == 0) L.stepErr = anyBad ? DYNENV_ERRBIT_ACTION : 0;
   }
   int finishedAt = -1;  // elapsed time at which the last car finished in this step: the team reward (:252-254) follows from it
-  if (lane < 16) { L.rewAcc[lane] = 0.0; L.posAcc[lane] = 0.0; }
+  if (lane < DRV_MAXA) { L.rewAcc[lane] = 0.0; L.posAcc[lane] = 0.0; }
   bool aabbValid = false;
   // quiescent-shortcut state carried across launches: candidate mask of the previous substep (-1: unknown) and
   // whether every cached arbiter was inert when the contact path last ran
