@@ -8,7 +8,7 @@ from .vec_env import BatchedDynEnv, make_dyn_env
 from .arranger import GpuInOutArranger, groups_for
 
 __all__ = ["BatchedDynEnv", "make_dyn_env", "DynEnvType", "NoiseType", "ObservationType", "GpuInOutArranger", "GpuInputLayer",
-           "GpuEmbedInputLayer", "EmbedBlock", "GpuTemporalAttention", "groups_for"]
+           "GpuEmbedInputLayer", "EmbedBlock", "GpuTemporalAttention", "GpuRecurrentHead", "GpuFeatureExtractor", "groups_for"]
 
 
 def __getattr__(name):
@@ -18,4 +18,7 @@ def __getattr__(name):
     if name == "GpuTemporalAttention":
         from . import attention
         return attention.GpuTemporalAttention
+    if name in ("GpuRecurrentHead", "GpuFeatureExtractor"):
+        from . import recurrent
+        return getattr(recurrent, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -95,6 +95,10 @@ class Mha(C.Structure):  # dynenv_mha_t: device pointers of one nn.MultiheadAtte
     _fields_ = [(n, C.c_void_p) for n in ("in_w", "out_w", "bias_k", "bias_v", "in_b", "out_b")]
 
 
+class Rhead(C.Structure):  # dynenv_rhead_t: device pointers of the recurrent head; tr_w, w_ih and w_hh 16 bit, the rest float32
+    _fields_ = [(n, C.c_void_p) for n in ("tr_w", "tr_b", "tr_ln_w", "tr_ln_b", "w_ih", "w_hh", "b_ih", "b_hh", "ln_w", "ln_b")]
+
+
 vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
 
 # THE binding of include/dynenv.h: name -> (restype, argtypes), in the header's order of growth.  load() sets exactly these, so an entry
@@ -159,6 +163,7 @@ SIGNATURES = {
     "dynenv_arrange_embed_pad": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, i32, C.POINTER(EmbedBlock), i32, C.c_float, C.c_float,
                                            vp, i32, vp]),
     "dynenv_attend_pool": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, C.POINTER(Mha), C.POINTER(Mha), vp, vp, C.c_float, vp, vp, vp, vp]),
+    "dynenv_recurrent_head": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.POINTER(Rhead), C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -631,6 +631,46 @@ int dynenv_attend_pool(const void* padded_dev, int32_t padded_dtype, const int32
                        const float* ln_b_dev, float ln_eps, const float* conf_w_dev, const float* conf_b_dev, float* out_dev,
                        void* stream);
 
+/* ---- the recurrent head in ONE launch, where no gradient is wanted: the back half of the reference's DynEnvFeatureExtractor.forward
+ * (models.py:584-594, 610-616) - TransformNet = Sequential(Linear(F + X, F), LeakyReLU, LayerNorm(F)), the nn.LSTMCell(F, F) of
+ * LSTMLayer (models.py:16-95) on its persistent h and c, and the closing LayerNorm `bn` - with a per-environment reset of the state
+ * folded in.  The [P][4F] gate pre-activations never exist in memory.  A HOST struct of device pointers, in torch's layouts: the
+ * three matrices in the 16-bit type w_dtype (the operands of the matrix units), everything else float32. */
+typedef struct dynenv_rhead {
+  const void  *tr_w;                        /* [F][KP] TransformNet.0.weight in the 16-bit type, KP = F + X rounded up to a multiple of 32, columns from F + X on +0; unused when X == 0 */
+  const float *tr_b, *tr_ln_w, *tr_ln_b;    /* [F] TransformNet.0.bias, TransformNet.2.weight / .bias; unused when X == 0 */
+  const void  *w_ih, *w_hh;                 /* [4F][F] LSTM.cell.weight_ih / weight_hh, torch's gate order i, f, g, o (16-bit type) */
+  const float *b_ih, *b_hh;                 /* [4F] */
+  const float *ln_w, *ln_b;                 /* [F] the closing bn */
+} dynenv_rhead_t;
+/* dynenv_recurrent_head, one launch, capturable (a launch and nothing else: nothing is synchronised, allocated or copied; pointers
+ * and sizes are frozen by a capture, contents are read at replay).  P = E * A rows; row p belongs to environment p / A (the
+ * arranger's player order, and that of the reference's commented-out reset, models.py:45).  feat_dev [P][F] float32 (what
+ * dynenv_attend_pool wrote); ext_dev [P][X] float32, the reference's `position`, NULL exactly when X == 0; h_dev and c_dev [P][F]
+ * float32, read and written IN PLACE; out_dev [P][F] float32.  reset_env_dev is NULL or uint8 [E] - the dones_dev of a step is a
+ * valid mask, as for dynenv_reset_masked.  Per row, all non-matrix arithmetic in float32:
+ *   x = feat when X == 0 (the reference skips TransformNet when position is None, models.py:611-612; w->tr_* are then unused and may
+ *       be NULL), else x = LayerNorm(leaky(cat(feat, ext) W_tr^T + b_tr; slope); tr_ln, tr_eps);
+ *   where reset_env_dev != NULL and reset_env_dev[p / A] != 0, h and c are taken as +0.0 WITHOUT being read (they may hold anything,
+ *       NaN included); otherwise they are read;
+ *   g = x W_ih^T + b_ih + h W_hh^T + b_hh;  c' = sigmoid(g_f) c + sigmoid(g_i) tanh(g_g);  h' = sigmoid(g_o) tanh(c');
+ *   out = LayerNorm(h'; ln, ln_eps).
+ * h', c' and out are each written exactly once, every element of the P rows; a row's h and c are read completely before any byte of
+ * that row is written.
+ * Arithmetic: the three matrix products take 16-bit operands of w_dtype (DYNENV_ARR_BF16 / _F16) on the matrix units and accumulate
+ * in float32; cat(feat, ext), x and h are rounded to w_dtype only as operands: the state in memory stays float32, and
+ * c is never rounded.  Every sum has one fixed order: a row's result depends on that row, its environment's mask byte and the
+ * weights alone - not on p, on P or on the other rows - and the same call twice gives the same bits.  Inputs that are not finite
+ * are outside the contract, except the never-read state of a reset environment.
+ * Errors, DYNENV_ERR_ARG, all reported before a device is looked for: a NULL feat_dev, w, h_dev, c_dev, out_dev, or one of w's
+ * pointers of the cell and the closing LayerNorm (with X > 0: of the transform too); ext_dev NULL with X > 0 or non-NULL with
+ * X == 0; E, A or F < 1; X < 0; a dtype outside 0..2; feat_dev, h_dev, c_dev, out_dev or a weight buffer not 16-byte aligned;
+ * E * A > 2^30 (the launch limit).  Then what the kernel does not take: DYNENV_ARR_F32, an F other than 64 or 128, X > 32:
+ * DYNENV_ERR_UNSUPPORTED, also before the device. */
+int dynenv_recurrent_head(const float* feat_dev, const float* ext_dev, int32_t E, int32_t A, int32_t F, int32_t X, int32_t w_dtype,
+                          const dynenv_rhead_t* w, float slope, float tr_eps, float ln_eps, const uint8_t* reset_env_dev,
+                          float* h_dev, float* c_dev, float* out_dev, void* stream);
+
 
 /* Device self-test of the deterministic math header: evaluates sincos/atan2/sqrt/div on n host-provided doubles and
  * returns the raw results so tests can compare them bit-for-bit with the host evaluation. out: [n,5]. */
