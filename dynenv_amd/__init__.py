@@ -8,7 +8,7 @@ from .vec_env import BatchedDynEnv, make_dyn_env
 from .arranger import GpuInOutArranger, groups_for
 
 __all__ = ["BatchedDynEnv", "make_dyn_env", "DynEnvType", "NoiseType", "ObservationType", "GpuInOutArranger", "GpuInputLayer",
-           "GpuEmbedInputLayer", "EmbedBlock", "GpuTemporalAttention", "GpuRecurrentHead", "GpuFeatureExtractor", "groups_for"]
+           "GpuEmbedInputLayer", "EmbedBlock", "GpuTemporalAttention", "GpuRecurrentHead", "GpuFeatureExtractor", "GpuPolicyHead", "groups_for"]
 
 
 def __getattr__(name):
@@ -21,4 +21,7 @@ def __getattr__(name):
     if name in ("GpuRecurrentHead", "GpuFeatureExtractor"):
         from . import recurrent
         return getattr(recurrent, name)
+    if name == "GpuPolicyHead":
+        from . import policy
+        return policy.GpuPolicyHead
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

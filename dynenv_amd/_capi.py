@@ -99,6 +99,11 @@ class Rhead(C.Structure):  # dynenv_rhead_t: device pointers of the recurrent he
     _fields_ = [(n, C.c_void_p) for n in ("tr_w", "tr_b", "tr_ln_w", "tr_ln_b", "w_ih", "w_hh", "b_ih", "b_hh", "ln_w", "ln_b")]
 
 
+class Policy(C.Structure):  # dynenv_policy_t: device pointers of the policy head; actor_w and critic_w1 16 bit, the rest float32
+    _fields_ = [(n, C.c_void_p) for n in ("actor_w", "actor_b", "cont_scale", "cont_mean", "critic_w1", "critic_b1", "critic_ln_w", "critic_ln_b",
+                                          "critic_w2", "critic_b2")]
+
+
 vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
 
 # THE binding of include/dynenv.h: name -> (restype, argtypes), in the header's order of growth.  load() sets exactly these, so an entry
@@ -164,6 +169,8 @@ SIGNATURES = {
                                            vp, i32, vp]),
     "dynenv_attend_pool": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, C.POINTER(Mha), C.POINTER(Mha), vp, vp, C.c_float, vp, vp, vp, vp]),
     "dynenv_recurrent_head": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.POINTER(Rhead), C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+    "dynenv_policy_head": (C.c_int, [vp, vp, i32, i32, i32, i32, C.POINTER(Policy), C.POINTER(i32), i32, i32, i32, C.c_uint64, vp, C.c_uint64,
+                                     C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -1,0 +1,316 @@
+// policy_kernels.hip — the reference's policy head in one launch where no gradient is wanted: ActorLayer and CriticLayer
+// (DynEnv/models/actor_critic.py:161-242) on cat(features[0:2]) (actor_critic.py:88, never materialised), the softmax and the draw of
+// _calc_log_probs per discrete action group (actor_critic.py:125-140), and transformActions (DynEnv/utils/utils.py:20-39) of the drawn
+// actions (include/dynenv.h, dynenv_policy_head).  The logits never exist in memory.  Included at the very END of dynenv_capi.hip,
+// behind recurrent_kernels.hip: no kernel a step launches moves.  This file also holds the entry point's host code.
+//
+// Per row p:
+//   l = cat(feat0, feat1) W_actor^T + b            (32 rows: the N logits of the G groups, the C outputs of the Box block, +0)
+//   probs_g = softmax(l_g);  cont = (sigmoid(l) - 0.5) * scale + mean
+//   value = LayerNorm(leaky(cat W1^T + b1)) . w2 + b2
+//   u_g from Philox4x32-10 keyed by (seed; row_base + p, draw, purpose + g / 4);  action_g = #{j < n_g - 1: c_j <= u_g c_{n-1}}
+//
+// Work.  One workgroup of four waves per PH_ROWS = 64 rows = four strips of 16, recurrent_kernels.hip's shape: 16x16x32 MFMAs with
+// float32 accumulators in the orientation D^T = W X^T, so that a lane's accumulator holds four consecutive outputs of one row.  The
+// output tiles of 16 - K / 32 of the critic's Layer1, then the two of the actor - are dealt to the waves round robin (tile = wave +
+// 4 t); a wave computes its tiles for ALL FOUR strips, so every weight fragment it fetches (16 contiguous bytes per lane, from L2)
+// feeds four MFMAs and the workgroup streams the weights once per 64 rows.  The B operands come from the 64 rows in LDS, 16 bit wide.
+//   phase 0: cat(feat0, feat1) rounded into LDS row-major
+//   phase 1: the products; the actor's 32 outputs of every row into LDS (float32); the critic's LayerNorm and its dot product with
+//            Layer2.weight, the four waves' parts of every row's sums added in wave order
+//   phase 2: thread (row r, wave q) takes the groups g = q, q + 4 of row r: softmax in place in LDS, the cumulative sum, the draw,
+//            log_prob; and the Box output c = q
+//   phase 3: probs, actions and next_ext leave LDS as contiguous pieces of the 64 rows
+// Every sum has one fixed order and an MFMA's columns do not mix: a row's result depends on the row, the weights and its stream alone.
+// Rows at or behind P in the last workgroup are +0.0 in LDS and are never stored.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "dynenv.h"
+#include "dynenv_math.h"
+
+#define PH_BLOCK 256
+#define PH_WAVES (PH_BLOCK / 64)
+#define PH_STRIPS 4
+#define PH_ROWS (16 * PH_STRIPS)
+#define PH_LS 33   // floats per LDS row of the 32 actor outputs: a lane per row reads without bank conflicts
+
+// arr_u4, ArrBf16, ArrF16: arranger_cols_kernels.hip's.  atp_h, atp_f4, AtpMma, atp_ld16, atp_st4, atp_row_sum, atp_sum4: attention_kernels.hip's.
+// rh_ldf4, rh_sigmoid: recurrent_kernels.hip's.
+
+struct PhArgs {   // dynenv_policy_t by value, the outputs and the sizes
+  const float *feat0, *feat1;
+  const atp_h *actor_w, *w1;
+  const float *actor_b, *cont_scale, *cont_mean, *b1, *ln_w, *ln_b, *w2, *b2;
+  const unsigned long long* draw;
+  unsigned long long seed, row_base;
+  unsigned long long group_off;   // 8 bits per group: the first logit of group g
+  unsigned group_n;               // 4 bits per group: n_g - 1
+  int P, G, N, C, AD, discrete_turn;
+  float slope, eps;
+  int* actions;
+  double* cont;
+  float *probs, *logp, *value, *next_ext;
+};
+
+template <int K, class CV>
+__device__ __forceinline__ void ph_body(const PhArgs& a) {
+  constexpr int H = K / 2, CT = H / 16, T = CT + 2, TPW = (T + PH_WAVES - 1) / PH_WAVES, KS = K / 32;   // critic tiles, all tiles, tiles per wave, k steps
+  constexpr int XS = K + 8;                                                                              // elements per LDS row: 16 bytes of padding
+  __shared__ __attribute__((aligned(16))) atp_h xb[PH_ROWS * XS];
+  __shared__ float lg[PH_ROWS * PH_LS];
+  __shared__ float part[3 * PH_WAVES * PH_ROWS];
+  __shared__ int acts[PH_ROWS * 8];
+
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const int row0 = (int)blockIdx.x * PH_ROWS, P = a.P;
+  const int F = a.feat1 ? H : K;
+  const atp_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
+
+  // ---- phase 0: cat(feat0, feat1), rounded, into LDS
+  for (int i = tid; i < PH_ROWS * (K / 4); i += PH_BLOCK) {
+    const int r = i / (K / 4), col = 4 * (i % (K / 4)), p = row0 + r;
+    atp_f4 v = zero4;
+    if (p < P) v = col < F ? rh_ldf4(a.feat0 + (size_t)p * F + col) : rh_ldf4(a.feat1 + (size_t)p * F + (col - F));
+    atp_st4<CV>(xb + r * XS + col, v);
+  }
+  __syncthreads();
+
+  // ---- phase 1: this wave's tiles for all 64 rows
+  atp_f4 y[TPW][PH_STRIPS];
+  const atp_h* wrow[TPW];
+#pragma unroll
+  for (int t = 0; t < TPW; ++t) {
+    const int tile = wave + PH_WAVES * t;
+    atp_f4 b = zero4;
+    wrow[t] = a.w1;
+    if (tile < CT) {
+      b = rh_ldf4(a.b1 + 16 * tile + 4 * lq);
+      wrow[t] = a.w1 + (size_t)(16 * tile + lr) * K;
+    } else if (tile < T) {
+      b = rh_ldf4(a.actor_b + 16 * (tile - CT) + 4 * lq);
+      wrow[t] = a.actor_w + (size_t)(16 * (tile - CT) + lr) * K;
+    }
+#pragma unroll
+    for (int s = 0; s < PH_STRIPS; ++s) y[t][s] = b;
+  }
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    arr_u4 xf[PH_STRIPS];
+#pragma unroll
+    for (int s = 0; s < PH_STRIPS; ++s) xf[s] = atp_ld16(xb + (16 * s + lr) * XS + 32 * ks + 8 * lq);
+#pragma unroll
+    for (int t = 0; t < TPW; ++t)
+      if (wave + PH_WAVES * t < T) {
+        const arr_u4 w = atp_ld16(wrow[t] + 32 * ks + 8 * lq);
+#pragma unroll
+        for (int s = 0; s < PH_STRIPS; ++s) y[t][s] = AtpMma<CV>::mma(w, xf[s], y[t][s]);
+      }
+  }
+  // the actor's outputs into LDS; the critic's LeakyReLU
+#pragma unroll
+  for (int t = 0; t < TPW; ++t) {
+    const int tile = wave + PH_WAVES * t;
+    if (tile < CT) {
+#pragma unroll
+      for (int s = 0; s < PH_STRIPS; ++s) {
+        atp_f4& v = y[t][s];
+        v.x = v.x > 0.f ? v.x : v.x * a.slope; v.y = v.y > 0.f ? v.y : v.y * a.slope;
+        v.z = v.z > 0.f ? v.z : v.z * a.slope; v.w = v.w > 0.f ? v.w : v.w * a.slope;
+      }
+    } else if (tile < T) {
+#pragma unroll
+      for (int s = 0; s < PH_STRIPS; ++s) {
+        float* q = lg + (16 * s + lr) * PH_LS + 16 * (tile - CT) + 4 * lq;
+        q[0] = y[t][s].x; q[1] = y[t][s].y; q[2] = y[t][s].z; q[3] = y[t][s].w;
+      }
+    }
+  }
+  // torch's LayerNorm (biased variance, two passes) over the H critic features of a row, which lie in up to four waves, and the dot
+  // product with Layer2.weight: a wave without a critic tile adds +0
+  float mean[PH_STRIPS], rstd[PH_STRIPS];
+#pragma unroll
+  for (int s = 0; s < PH_STRIPS; ++s) {
+    float v = 0.f;
+#pragma unroll
+    for (int t = 0; t < TPW; ++t)
+      if (wave + PH_WAVES * t < CT) v += atp_sum4(y[t][s]);
+    v = atp_row_sum(v);
+    if (lq == 0) part[wave * PH_ROWS + 16 * s + lr] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < PH_STRIPS; ++s) {
+    const float* q = part + 16 * s + lr;
+    mean[s] = (((q[0] + q[PH_ROWS]) + q[2 * PH_ROWS]) + q[3 * PH_ROWS]) * (1.0f / H);
+  }
+  float* part2 = part + PH_WAVES * PH_ROWS;
+#pragma unroll
+  for (int s = 0; s < PH_STRIPS; ++s) {
+    float v = 0.f;
+#pragma unroll
+    for (int t = 0; t < TPW; ++t)
+      if (wave + PH_WAVES * t < CT) { const atp_f4 d = y[t][s] - mean[s]; v += atp_sum4(d * d); }
+    v = atp_row_sum(v);
+    if (lq == 0) part2[wave * PH_ROWS + 16 * s + lr] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < PH_STRIPS; ++s) {
+    const float* q = part2 + 16 * s + lr;
+    rstd[s] = 1.0f / sqrtf((((q[0] + q[PH_ROWS]) + q[2 * PH_ROWS]) + q[3 * PH_ROWS]) * (1.0f / H) + a.eps);
+  }
+  float* part3 = part + 2 * PH_WAVES * PH_ROWS;
+  {
+    float dot[PH_STRIPS] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) {
+      const int tile = wave + PH_WAVES * t;
+      if (tile < CT) {
+        const atp_f4 g = rh_ldf4(a.ln_w + 16 * tile + 4 * lq), b = rh_ldf4(a.ln_b + 16 * tile + 4 * lq), w2 = rh_ldf4(a.w2 + 16 * tile + 4 * lq);
+#pragma unroll
+        for (int s = 0; s < PH_STRIPS; ++s) dot[s] += atp_sum4(((y[t][s] - mean[s]) * rstd[s] * g + b) * w2);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < PH_STRIPS; ++s) {
+      const float v = atp_row_sum(dot[s]);
+      if (lq == 0) part3[wave * PH_ROWS + 16 * s + lr] = v;
+    }
+  }
+  __syncthreads();   // (the actor's outputs in lg are complete too)
+  if (tid < PH_ROWS && row0 + tid < P) {
+    const float* q = part3 + tid;
+    a.value[row0 + tid] = (((q[0] + q[PH_ROWS]) + q[2 * PH_ROWS]) + q[3 * PH_ROWS]) + a.b2[0];
+  }
+
+  // ---- phase 2: row r's groups g = q, q + 4 and its Box output c = q, by thread (r, q); q is the wave, so a group's size is uniform
+  {
+    const int r = lane, q = wave, p = row0 + r;
+    float* L = lg + r * PH_LS;
+    const unsigned long long draw = a.draw ? a.draw[0] : 0ull, row = a.row_base + (unsigned long long)p;
+    for (int g = q; g < a.G; g += PH_WAVES) {
+      const int off = (int)((a.group_off >> (8 * g)) & 255u), n = (int)((a.group_n >> (4 * g)) & 15u) + 1;
+      float m = L[off];
+      for (int j = 1; j < n; ++j) m = fmaxf(m, L[off + j]);
+      float sum = 0.f;
+      for (int j = 0; j < n; ++j) {
+        const float e = expf(L[off + j] - m);
+        L[off + j] = e;
+        sum += e;
+      }
+      float last = 0.f;   // c_{n-1}
+      for (int j = 0; j < n; ++j) {
+        const float pj = L[off + j] / sum;
+        L[off + j] = pj;
+        last += pj;
+      }
+      const dm_u32x4 w = dm_philox((uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)row, (uint32_t)draw, (uint32_t)(draw >> 32),
+                                   DYNENV_POLICY_RNG_PURPOSE + (uint32_t)(g >> 2));
+      const uint32_t word = q == 0 ? w.v[0] : q == 1 ? w.v[1] : q == 2 ? w.v[2] : w.v[3];
+      const float u = (float)(word >> 8) * 5.9604644775390625e-08f;   // 2^-24: exact
+      const float t = u * last;
+      float c = 0.f;
+      int act = 0;
+      for (int j = 0; j + 1 < n; ++j) {
+        c += L[off + j];
+        act += c <= t ? 1 : 0;
+      }
+      acts[r * 8 + g] = act;
+      if (p < P) {
+        const float eps32 = 1.1920928955078125e-07f;
+        const float pa = fminf(fmaxf(L[off + act], eps32), 1.0f - eps32);
+        a.logp[(size_t)p * a.G + g] = (float)log((double)pa);   // the float32 nearest to the logarithm: a host reproduces it bit for bit
+      }
+    }
+    if (q < a.C && p < P) {
+      const float v = (rh_sigmoid(L[a.N + q]) - 0.5f) * a.cont_scale[q] + a.cont_mean[q];
+      a.cont[(size_t)p * a.C + q] = (double)v;
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 3: the 64 rows' probs, actions and next_ext are contiguous in memory
+  const int rows = min(PH_ROWS, P - row0);
+  for (int i = tid; i < rows * a.N; i += PH_BLOCK) a.probs[(size_t)row0 * a.N + i] = lg[(i / a.N) * PH_LS + i % a.N];
+  const int AD = a.AD;
+  for (int i = tid; i < rows * AD; i += PH_BLOCK) {
+    const int r = i / AD, k = i % AD;
+    const int v = k < a.G ? acts[r * 8 + k] : 0;
+    a.actions[(size_t)row0 * AD + i] = v;
+    if (a.next_ext) {   // utils.py:20-39, as its in-place assignments run
+      int e = v;
+      if (AD == 4) {
+        const int a0 = acts[r * 8];
+        if (k == 0) e = v < 3 ? 0 : v == 3 ? 1 : v == 4 ? -1 : v;
+        else if (k == 1) e = v == 2 ? -1 : v;
+        else if (k == 2) e = (a0 == 1 || a0 == 2) ? -1 : 0;   // sides: 2 -> 1, then every 1 -> -1
+        else if (a.discrete_turn) e = v - 3;
+      } else if (k < 2) {
+        e = v - 1;
+      }
+      a.next_ext[(size_t)row0 * AD + i] = (float)e;
+    }
+  }
+}
+
+#define PH_KERNEL(NAME, K, CV) \
+  extern "C" __global__ void __launch_bounds__(PH_BLOCK) NAME(PhArgs a) { ph_body<K, CV>(a); }
+PH_KERNEL(ph_64_bf16_kernel, 64, ArrBf16)
+PH_KERNEL(ph_64_f16_kernel, 64, ArrF16)
+PH_KERNEL(ph_128_bf16_kernel, 128, ArrBf16)
+PH_KERNEL(ph_128_f16_kernel, 128, ArrF16)
+PH_KERNEL(ph_256_bf16_kernel, 256, ArrBf16)
+PH_KERNEL(ph_256_f16_kernel, 256, ArrF16)
+
+// ---- the entry point.  Argument errors first, then what the kernel does not take, both before a device is looked for; one launch and
+// nothing else: nothing is synchronised, allocated or copied, so the call may be captured.
+extern "C" int dynenv_policy_head(const float* feat0_dev, const float* feat1_dev, int32_t E, int32_t A, int32_t F, int32_t w_dtype,
+                                  const dynenv_policy_t* w, const int32_t* nvec, int32_t G, int32_t C, int32_t action_cols, uint64_t seed,
+                                  const uint64_t* draw_dev, uint64_t row_base, float slope, float ln_eps, int32_t discrete_turn,
+                                  int32_t* actions_dev, double* cont_dev, float* probs_dev, float* logp_dev, float* value_dev,
+                                  float* next_ext_dev, void* stream) {
+  if (!feat0_dev || !w || !nvec || !actions_dev || !probs_dev || !logp_dev || !value_dev) return fail(DYNENV_ERR_ARG, "null argument");
+  if (!w->actor_w || !w->actor_b || !w->critic_w1 || !w->critic_b1 || !w->critic_ln_w || !w->critic_ln_b || !w->critic_w2 || !w->critic_b2)
+    return fail(DYNENV_ERR_ARG, "policy head: the actor and the critic have all eight of their pointers");
+  if (E < 1 || A < 1 || F < 1) return fail(DYNENV_ERR_ARG, "policy head: bad shape");
+  if (G < 1 || G > DYNENV_POLICY_MAX_GROUPS || C < 0 || C > DYNENV_POLICY_MAX_CONT) return fail(DYNENV_ERR_ARG, "policy head: G is 1..8 and C 0..4");
+  int N = 0;
+  unsigned long long group_off = 0;
+  unsigned group_n = 0;
+  for (int g = 0; g < G; ++g) {
+    if (nvec[g] < 1 || nvec[g] > 16) return fail(DYNENV_ERR_ARG, "policy head: a group has 1..16 actions");
+    group_off |= (unsigned long long)N << (8 * g);
+    group_n |= (unsigned)(nvec[g] - 1) << (4 * g);
+    N += nvec[g];
+  }
+  if (N + C > DYNENV_POLICY_ROWS) return fail(DYNENV_ERR_ARG, "policy head: N + C is at most 32");
+  if (action_cols < G || action_cols > 8) return fail(DYNENV_ERR_ARG, "policy head: action_cols is G..8");
+  if ((C > 0) != (cont_dev != nullptr)) return fail(DYNENV_ERR_ARG, "policy head: cont_dev is NULL exactly when C == 0");
+  if (C > 0 && (!w->cont_scale || !w->cont_mean)) return fail(DYNENV_ERR_ARG, "policy head: C > 0 takes cont_scale and cont_mean");
+  if (w_dtype < DYNENV_ARR_F32 || w_dtype > DYNENV_ARR_F16) return fail(DYNENV_ERR_ARG, "policy head: unknown dtype (DYNENV_ARR_BF16 or _F16)");
+  const void* aligned[] = {feat0_dev, feat1_dev, w->actor_w, w->actor_b, w->critic_w1, w->critic_b1, w->critic_ln_w, w->critic_ln_b, w->critic_w2,
+                           actions_dev, cont_dev, probs_dev, logp_dev, value_dev, next_ext_dev};
+  for (const void* q : aligned)
+    if ((uintptr_t)q % 16) return fail(DYNENV_ERR_ARG, "policy head: buffers must be 16-byte aligned");
+  if ((uintptr_t)w->critic_b2 % 4 || (uintptr_t)w->cont_scale % 4 || (uintptr_t)w->cont_mean % 4 || (uintptr_t)draw_dev % 8)
+    return fail(DYNENV_ERR_ARG, "policy head: critic_b2, cont_scale and cont_mean are 4-byte, draw_dev 8-byte aligned");
+  if ((int64_t)E * A > (int64_t)1 << 30) return fail(DYNENV_ERR_ARG, "policy head: E * A too large for one launch");
+  if (w_dtype == DYNENV_ARR_F32) return fail(DYNENV_ERR_UNSUPPORTED, "policy head: the fused layer takes bf16 or fp16 operands");
+  if (F != 64 && F != 128) return fail(DYNENV_ERR_UNSUPPORTED, "policy head: the fused layer takes F = 64 or 128");
+  if (int rc = have_device()) return rc;
+  PhArgs k;
+  k.feat0 = feat0_dev; k.feat1 = feat1_dev;
+  k.actor_w = static_cast<const atp_h*>(w->actor_w); k.w1 = static_cast<const atp_h*>(w->critic_w1);
+  k.actor_b = w->actor_b; k.cont_scale = w->cont_scale; k.cont_mean = w->cont_mean; k.b1 = w->critic_b1; k.ln_w = w->critic_ln_w;
+  k.ln_b = w->critic_ln_b; k.w2 = w->critic_w2; k.b2 = w->critic_b2;
+  k.draw = reinterpret_cast<const unsigned long long*>(draw_dev); k.seed = seed; k.row_base = row_base; k.group_off = group_off; k.group_n = group_n;
+  k.P = E * A; k.G = G; k.N = N; k.C = C; k.AD = action_cols; k.discrete_turn = discrete_turn != 0;
+  k.slope = slope; k.eps = ln_eps;
+  k.actions = actions_dev; k.cont = cont_dev; k.probs = probs_dev; k.logp = logp_dev; k.value = value_dev; k.next_ext = next_ext_dev;
+  static decltype(&ph_64_bf16_kernel) const kernels[3][2] = {{ph_64_bf16_kernel, ph_64_f16_kernel}, {ph_128_bf16_kernel, ph_128_f16_kernel},
+                                                              {ph_256_bf16_kernel, ph_256_f16_kernel}};
+  const int Kc = feat1_dev ? 2 * F : F;
+  hipLaunchKernelGGL(kernels[Kc == 64 ? 0 : Kc == 128 ? 1 : 2][w_dtype == DYNENV_ARR_F16], dim3((unsigned)((k.P + PH_ROWS - 1) / PH_ROWS)), dim3(PH_BLOCK), 0,
+                     (hipStream_t)stream, k);
+  return launched();
+}

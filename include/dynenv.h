@@ -671,6 +671,64 @@ int dynenv_recurrent_head(const float* feat_dev, const float* ext_dev, int32_t E
                           const dynenv_rhead_t* w, float slope, float tr_eps, float ln_eps, const uint8_t* reset_env_dev,
                           float* h_dev, float* c_dev, float* out_dev, void* stream);
 
+/* ---- the policy head in ONE launch, where no gradient is wanted: the reference's ActorLayer and CriticLayer
+ * (DynEnv/models/actor_critic.py:161-242) on cat(features[0:2], dim=1) (actor_critic.py:88), the softmax and the draw of
+ * _calc_log_probs for every discrete action group (actor_critic.py:125-140, the rollout of DynEnv/models/train.py:251-266), and
+ * transformActions (DynEnv/utils/utils.py:20-39) of the drawn actions.  Neither the concatenated feature nor the logits exist in
+ * memory.  A HOST struct of device pointers, in torch's layouts: the two matrices in the 16-bit type w_dtype (the operands of the
+ * matrix units), everything else float32. */
+#define DYNENV_POLICY_ROWS 32         /* the rows of the actor's matrix: N + C of them are used */
+#define DYNENV_POLICY_MAX_GROUPS 8    /* G: the discrete action groups */
+#define DYNENV_POLICY_MAX_CONT 4      /* C: the outputs of a Box block */
+#define DYNENV_POLICY_RNG_PURPOSE 16u /* counter word 3 of the draw is this + g / 4; the step kernels' purposes (dynenv_math.h) are 1..9 */
+typedef struct dynenv_policy {
+  const void  *actor_w;                                /* [32][K] every actor.blocks.*.Layer*.weight in the order of ActorLayer.forward's flattened list: the N = sum n_g logits of the G groups, then the C outputs of the Box block; rows from N + C on +0 (16-bit type) */
+  const float *actor_b;                                /* [32] the biases in the same order, +0 from N + C on */
+  const float *cont_scale, *cont_mean;                 /* [C] ActorBlock.scale / .means; unused when C == 0 */
+  const void  *critic_w1;                              /* [K/2][K] critic.blocks.Layer1.weight (16-bit type) */
+  const float *critic_b1, *critic_ln_w, *critic_ln_b;  /* [K/2] Layer1.bias, bn.weight / .bias */
+  const float *critic_w2, *critic_b2;                  /* [K/2] Layer2.weight, [1] Layer2.bias */
+} dynenv_policy_t;
+/* dynenv_policy_head, one launch, capturable (a launch and nothing else: nothing is synchronised, allocated or copied; pointers
+ * and sizes are frozen by a capture, contents are read at replay).  P = E * A rows; row p belongs to environment p / A.  feat0_dev
+ * [P][F] float32 and feat1_dev NULL or [P][F] float32: the input of a row is cat(feat0, feat1) of width K = F or 2F.  nvec is a
+ * HOST array of the G group sizes n_g, N = sum n_g; C the width of the Box block; action_cols = AD the width of an action row, G <=
+ * AD <= 8.  Per row p, all non-matrix arithmetic in float32 (actor_critic.py:204-213, 230-242):
+ *   l = cat(feat0, feat1) W_actor^T + b;  probs_g = softmax(l_g) for every group;  cont = (sigmoid(l) - 0.5) * scale + mean for the
+ *       Box block's outputs;
+ *   value = LayerNorm(leaky(cat(feat0, feat1) W1^T + b1; slope); bn, ln_eps) . w2 + b2;
+ *   the draw: w = dm_philox(lo32(seed), hi32(seed), lo32(row_base + p), lo32(draw), hi32(draw), DYNENV_POLICY_RNG_PURPOSE + g / 4)
+ *       (include/dynenv_math.h: Philox4x32-10, the first two words the key), draw = draw_dev[0], or 0 where draw_dev is NULL (const
+ *       uint64 [1] on the device: read at replay); the word of group g is w.v[g % 4] and u = (float)(word >> 8) * 2^-24, which is exact;
+ *   the sample, in float32: c_j = c_{j-1} + probs_g[j] summed left to right, t = u * c_{n-1} (one rounding), action_g = the number
+ *       of j in 0..n_g-2 with c_j <= t: an action of probability 0 is never drawn and the result is always inside the group;
+ *   logp_g = log(clamp(probs_g[action_g], eps32, 1 - eps32)), eps32 = 2^-23, what Categorical(probs).log_prob computes - evaluated in
+ *       double and rounded once, so it is the float32 nearest to the logarithm and a host reproduces it bit for bit;
+ *   next_ext = transformActions(actions, discrete_turn) as float32 - the reference's function as its in-place assignments run, not a
+ *       tidied one: with AD == 4 column 0 maps 0, 1, 2 -> 0, 3 -> 1, 4 -> -1, column 1 maps 2 -> -1, column 2 is the `sides` of column
+ *       0 and maps BOTH 1 and 2 to -1 (2 -> 1, then every 1 -> -1) and the rest to 0, column 3 is lowered by 3 where discrete_turn !=
+ *       0; with any other AD columns 0 and 1 are lowered by 1.
+ * Outputs, EVERY element of each written exactly once: actions_dev int32 [P][AD] - [E][A][AD], what dynenv_step reads - with columns
+ * G..AD-1 written 0 (RoboCup with allowHeadTurn: [5, 3, 3] and one Box output, AD = 4; dynenv_step_head ignores column 3); cont_dev
+ * double [P][C], NULL exactly when C == 0 (with C == 1 the head_dev of dynenv_step_head); probs_dev float32 [P][N]; logp_dev float32
+ * [P][G]; value_dev float32 [P]; next_ext_dev NULL or float32 [P][AD].
+ * Arithmetic: the two matrix products take 16-bit operands of w_dtype (DYNENV_ARR_BF16 / _F16) on the matrix units and accumulate in
+ * float32; biases, softmax, sigmoid, LayerNorm and the cumulative sums are float32.  Every sum has one fixed order: a row's result
+ * depends on that row, the weights and (seed, draw, row_base + p) alone - not on p's place in the launch, on P or on the other rows
+ * (shards of a batch pass their first row as row_base) - and the same call twice gives the same bits.  Inputs that are not finite
+ * are outside the contract.
+ * Errors, DYNENV_ERR_ARG, all reported before a device is looked for: a NULL feat0_dev, w, nvec, actions_dev, probs_dev, logp_dev or
+ * value_dev, or one of w's eight pointers of the actor and the critic (with C > 0: cont_scale and cont_mean too); cont_dev NULL with
+ * C > 0 or non-NULL with C == 0; E, A or F < 1; G outside 1..8, an n_g outside 1..16, C outside 0..4, N + C > 32, AD outside G..8; a
+ * dtype outside 0..2; feat0_dev, feat1_dev, an output or a weight buffer not 16-byte aligned (critic_b2, cont_scale, cont_mean:
+ * 4-byte; draw_dev: 8-byte); E * A > 2^30 (the launch limit).  Then what the kernel does not take: DYNENV_ARR_F32, an F other than
+ * 64 or 128: DYNENV_ERR_UNSUPPORTED, also before the device. */
+int dynenv_policy_head(const float* feat0_dev, const float* feat1_dev, int32_t E, int32_t A, int32_t F, int32_t w_dtype,
+                       const dynenv_policy_t* w, const int32_t* nvec, int32_t G, int32_t C, int32_t action_cols, uint64_t seed,
+                       const uint64_t* draw_dev, uint64_t row_base, float slope, float ln_eps, int32_t discrete_turn,
+                       int32_t* actions_dev, double* cont_dev, float* probs_dev, float* logp_dev, float* value_dev,
+                       float* next_ext_dev, void* stream);
+
 
 /* Device self-test of the deterministic math header: evaluates sincos/atan2/sqrt/div on n host-provided doubles and
  * returns the raw results so tests can compare them bit-for-bit with the host evaluation. out: [n,5]. */
