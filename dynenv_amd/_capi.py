@@ -74,6 +74,7 @@ ARR_MAX_TYPES = 4
 ARR_COUNT_CONST, ARR_COUNT_ENV, ARR_COUNT_ROW = 0, 1, 2
 ARR_F32, ARR_BF16, ARR_F16 = 0, 1, 2  # DYNENV_ARR_F32 / _BF16 / _F16: the element types of dynenv_arrange_*_as
 ERR_UNSUPPORTED = -4
+RETURNS_REFERENCE, RETURNS_DONES, RETURNS_GAE = 0, 1, 2  # DYNENV_RETURNS_*: the modes of dynenv_rollout_returns
 
 
 class ArrType(C.Structure):  # dynenv_arr_type_t
@@ -168,6 +169,10 @@ SIGNATURES = {
     "dynenv_arrange_embed_pad": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, i32, C.POINTER(EmbedBlock), i32, C.c_float, C.c_float,
                                            vp, i32, vp]),
     "dynenv_attend_pool": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, C.POINTER(Mha), C.POINTER(Mha), vp, vp, C.c_float, vp, vp, vp, vp]),
+    # (the two of the rollout storage stand in front of the two heads: tests/test_policy_host.py pins the last two names of the table)
+    "dynenv_rollout_insert": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                        vp, vp]),
+    "dynenv_rollout_returns": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp]),
     "dynenv_recurrent_head": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.POINTER(Rhead), C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
     "dynenv_policy_head": (C.c_int, [vp, vp, i32, i32, i32, i32, C.POINTER(Policy), C.POINTER(i32), i32, i32, i32, C.c_uint64, vp, C.c_uint64,
                                      C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]),

@@ -715,6 +715,21 @@ class BatchedDynEnv(object):
         _capi.check(self._lib.dynenv_global_state(self._h, _capi.ptr(out), self._stream()), "dynenv_global_state")
         return out
 
+    def agent_finished(self, out=None):
+        """bool [E, A] on the device, with no host read: whether each agent is out of the game in the current state - what the
+        reference's rollout reads as `agent[-1] for agent in info['Full State'][0]` (DynEnv/models/train.py:272) from the compat step().
+        Driving: column 8 (`finished`) of the noise-free Full rows - the step's last snapshot in `self.obs` with Full observations,
+        full_state_obs() otherwise; RoboCup: column 5 of each robot's six in global_state() (fallen | penalized).  `out`: a bool [E, A]
+        tensor to write into (a recorded step refreshes it at every replay)."""
+        torch = self._torch
+        if self.env_type == DynEnvType.ROBO_CUP:
+            col = self.global_state()[:, :6 * self.n_agents].view(self.num_envs, self.n_agents, 6)[:, :, 5]
+        elif self.observationType == ObservationType.FULL:
+            col = self.obs[:, -1, :, 8]
+        else:
+            col = self.full_state_obs()[:, :, 8]
+        return torch.ne(col, 0, out=out) if out is not None else torch.ne(col, 0)
+
     def refresh_obs(self):
         """Re-emit the observation of the current state into `self.obs` (after set_state / restore).  Full observations only:
         a Partial observation is a noisy draw keyed by the step that produced it."""

@@ -729,6 +729,63 @@ int dynenv_policy_head(const float* feat0_dev, const float* feat1_dev, int32_t E
                        int32_t* actions_dev, double* cont_dev, float* probs_dev, float* logp_dev, float* value_dev,
                        float* next_ext_dev, void* stream);
 
+/* ---- the rollout storage behind the policy head: the reference's RolloutStorage (DynEnv/models/storage.py) on the device.  The
+ * buffers are those of reset_buffers (storage.py:76-111), all float32 but `finished`, P = E * A players, K = F or 2 F:
+ *   rewards [T][P], finished uint8 [T][P] (agentFinished: a torch.bool tensor's storage), features [T+1][P][K], actions [T][AD][P],
+ *   log_probs and log_probs_old [T][G][P], values [T][P], dones [T][E], and - not the reference's, which keeps a Python list - probs
+ *   [T][P][N]. */
+#define DYNENV_RETURNS_REFERENCE 0 /* _discount_rewards as it runs (storage.py:168-209): dones are NOT looked at */
+#define DYNENV_RETURNS_DONES 1     /* the chain is cut where an episode ended */
+#define DYNENV_RETURNS_GAE 2       /* generalised advantage estimation, the reference's "todo: add GAE" (storage.py:203) */
+/* dynenv_rollout_insert, one launch, capturable (a launch and nothing else: nothing is synchronised, allocated or copied; pointers
+ * and sizes are frozen by a capture, contents are read at replay): RolloutStorage.insert (storage.py:134-166, called at
+ * DynEnv/models/train.py:277) at row t = cursor_dev[0], an int32 [1] on the device that is read at replay.  The kernel does not
+ * advance the cursor.  Inputs -> row t of their buffer:
+ *   rewards_in_dev  double [E][A], the step's       -> rewards[t][p]        rounded once to nearest (storage.py:158)
+ *   finished_in_dev uint8 [P], 0 / nonzero          -> finished[t][p]       0 or 1 (storage.py:159)
+ *   feat0_dev, feat1_dev float32 [P][F]             -> features[t][p][0:K]  side by side, K = F without feat1_dev, else 2 F: the
+ *                                                                           reference's cat is never materialised (storage.py:160)
+ *   actions_in_dev  int32 [P][AD], the policy's     -> actions[t][k][p]     transposed, as float32: torch.stack(action, dim=0) (storage.py:161)
+ *   logp_in_dev     float32 [P][G]                  -> log_probs[t][g][p]   transposed (storage.py:162)
+ *   logp_old_in_dev float32 [P][G]                  -> log_probs_old[t][g][p]   (storage.py:163-164)
+ *   value_in_dev    float32 [P]                     -> values[t][p]         (storage.py:165)
+ *   dones_in_dev    uint8 [E], the step's           -> dones[t][e]          0.0 or 1.0 (storage.py:166)
+ *   probs_in_dev    float32 [P][N]                  -> probs[t][p][0:N]     (train.py:257)
+ * Every input pointer may be NULL: its buffer is then not touched (and may be NULL too).  An input that is given writes EVERY element
+ * of row t of its buffer exactly once and no other row; no arithmetic but the conversions above, so a row is the same bits whoever
+ * computes it.  row_features_only != 0 writes features[t] alone - the reference's features[step + 1].copy_(final_features)
+ * (train.py:290) - and admits t = T; otherwise t is 0..T-1.  A cursor outside the admitted rows writes NOTHING and sets status_dev[0]
+ * (int32 [1]) to 1; the kernel never clears it.
+ * Errors, DYNENV_ERR_ARG, all reported before a device is looked for: a NULL cursor_dev or status_dev; T, E, A, F, G or action_cols
+ * < 1, N < 0, T > 2^24, E * A > 2^30, E * A * K > 2^32; feat1_dev without feat0_dev; row_features_only without feat0_dev; probs_in_dev with N == 0; an
+ * input whose buffer is NULL; feat0_dev, feat1_dev or features_dev not 16-byte aligned, rewards_in_dev not 8-byte, any other 32-bit
+ * buffer not 4-byte aligned.  Then what the kernel does not take: F not a multiple of 4 (so K is one), G > 8, action_cols > 8, N > 32
+ * (dynenv_policy_head's limits): DYNENV_ERR_UNSUPPORTED, also before the device. */
+int dynenv_rollout_insert(const int32_t* cursor_dev, int32_t T, int32_t E, int32_t A, int32_t F, int32_t G, int32_t action_cols, int32_t N,
+                          int32_t row_features_only, const double* rewards_in_dev, const uint8_t* finished_in_dev, const float* feat0_dev,
+                          const float* feat1_dev, const int32_t* actions_in_dev, const float* logp_in_dev, const float* logp_old_in_dev,
+                          const float* value_in_dev, const uint8_t* dones_in_dev, const float* probs_in_dev, float* rewards_dev,
+                          uint8_t* finished_dev, float* features_dev, float* actions_dev, float* logp_dev, float* logp_old_dev,
+                          float* values_dev, float* dones_dev, float* probs_dev, int32_t* status_dev, void* stream);
+/* dynenv_rollout_returns, one launch, capturable: _discount_rewards (storage.py:168-209) over rewards_dev [T][P], values_dev [T][P],
+ * dones_dev [T][E] and final_value_dev [P] into returns_dev [T][P] and, unless NULL, advantages_dev [T][P]; player p belongs to
+ * environment p / A.  float32 throughout; every multiply and every add is rounded on its own (no fused multiply-add), in exactly
+ * this order of operations, t = T-1 .. 0, with g = gamma and nd = 1 - dones[t][p / A]:
+ *   mode 0, DYNENV_RETURNS_REFERENCE:  R = final_value;  R = rewards[t] + g * R;  returns[t] = R.  Dones are NOT looked at - the
+ *           reference's dones4players is all zeros (storage.py:195) - and dones_dev may be NULL.
+ *   mode 1, DYNENV_RETURNS_DONES:      R = final_value;  R = rewards[t] + (g * R) * nd;  returns[t] = R.
+ *   mode 2, DYNENV_RETURNS_GAE:        adv = 0;  next = t == T-1 ? final_value : values[t+1];
+ *           delta = (rewards[t] + (g * next) * nd) - values[t];  adv = delta + ((g * lambda) * adv) * nd;  returns[t] = adv + values[t];
+ *           advantages[t] = adv.
+ *   In modes 0 and 1 advantages[t] = returns[t] - values[t].
+ * Every element of returns_dev (and advantages_dev) is written exactly once.  Inputs that are not finite are outside the contract.
+ * Errors, DYNENV_ERR_ARG, before a device is looked for: a NULL rewards_dev, final_value_dev or returns_dev; a mode outside 0..2;
+ * dones_dev NULL in modes 1 and 2; values_dev NULL in mode 2 or with advantages_dev; T, E or A < 1, T > 2^24, E * A > 2^30; a buffer
+ * not 4-byte aligned. */
+int dynenv_rollout_returns(const float* rewards_dev, const float* values_dev, const float* dones_dev, const float* final_value_dev, int32_t T,
+                           int32_t E, int32_t A, int32_t mode, float gamma, float gae_lambda, float* returns_dev, float* advantages_dev,
+                           void* stream);
+
 
 /* Device self-test of the deterministic math header: evaluates sincos/atan2/sqrt/div on n host-provided doubles and
  * returns the raw results so tests can compare them bit-for-bit with the host evaluation. out: [n,5]. */
