@@ -75,6 +75,7 @@ struct __align__(16) DrvLds {
     DrvMailbox mb;
     DrvObsStage ob;
   } u;
+DRV_PROF(int profEnv;)  // the environment this block steps (not the block's index under SIMD isolation): the row of the stage profiles
 };
 
 // One tile per workgroup (= one wavefront = one environment).  File scope so that the out-of-line contact path
@@ -174,8 +175,10 @@ DE_DEV void velocity_update(DrvLds& L, int lane, bool isCar, bool isPed) {
   else apply_friction(vx, vy, w, m, fr, rfr, 0.0);
   L.vx[lane] = vx; L.vy[lane] = vy; L.w[lane] = w;
 }
-// The same as a leaf function, for the substeps without a solve (fast path, replay): inlined into the kernel's substep loop, its
-// friction coefficients - 64-bit literals - are hoisted out of the loop into registers that are then saved around every call.
+// The same as a leaf function, for the one substep without a solve that is decided in the contact path (its light-mode replay; the
+// fast, quiescent and steady-replay substeps apply this arithmetic inside drv_light_substep, to the registers it holds): inlined
+// into the kernel's substep loop, its friction coefficients - 64-bit literals - are hoisted out of the loop into registers that are
+// then saved around every call.
 DE_OOL void velocity_update_ool(int nCarPed) {
   const int lane = lane_id(), A = uniform_i(nCarPed) & 0xFF, nPed = uniform_i(nCarPed) >> 8;
   velocity_update(g_L, lane, lane < A, lane >= DRV_SLOT_PED && lane < DRV_SLOT_PED + nPed);
@@ -866,8 +869,9 @@ DRV_PROF(__device__ unsigned long long g_dbgr[16];)
 DRV_PROF(__device__ unsigned long long g_dbgl[4096 * 8];)  // stages of drv_light_substep, summed over the step's substeps
 DRV_PROF(__device__ unsigned long long g_dbgs[4096 * 8];)  // stages of the slot update (between narrowphase and prestep), summed over the step's calls
 DRV_PROF(DE_DEV int prof_any(int v) { const uint64_t m = wave_ballot(v != 0); return m ? bcast_i(v, __builtin_ctzll(m)) : 0; })
-// Which half of a substep is out of line: the COMMON part (game logic, position update, broadphase: drv_light_substep, a leaf
-// with nothing to save) is a function; the contact path is inlined into the kernel, which as the outermost frame never saves a
+// Which half of a substep is out of line: the COMMON part (game logic, position update, broadphase, the choice of the path and, where
+// nothing is to solve, the velocity update: drv_light_substep, a leaf with nothing to save) is a function; the contact path is
+// inlined into the kernel, which as the outermost frame never saves a
 // register (round 1 had it the other way round and paid the save / restore of 47 callee-saved VGPRs per call: 3/4 of that
 // kernel's HBM traffic).  Its solver is a set of functions again (drv_prestep_solve ...), all leaves, entered with nothing of the
 // contact cache live.
@@ -1058,7 +1062,7 @@ DRV_PROF(profMode = wave_ballot(!biasOnly) == 0ull ? 3 : 4;)
       // the general sweeps are a function of their own (drv_solve_general_split), and the kernel calls it: this function returns here
       // with what the sweeps and the verdicts need (a function that calls saves its return address through a VGPR that it stores to
       // and reloads from scratch right in front of EVERY return, and keeps 16 values in scratch across the call)
-DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + blockIdx.x * 8; const unsigned long long P3 = __builtin_amdgcn_s_memtime(); d[2] += P1 - P0; d[3] += (P2 - P1) + ((P3 - P2) << 32); })
+DRV_PROF(if (lane == 0 && g_L.profEnv < 4096) { unsigned long long* d = g_dbgp + g_L.profEnv * 8; const unsigned long long P3 = __builtin_amdgcn_s_memtime(); d[2] += P1 - P0; d[3] += (P2 - P1) + ((P3 - P2) << 32); })
       const int bits3 = (restIn ? B3_REST_IN : 0) | (bias[0] == 0.0 ? B3_BIAS0_ZERO : 0) | (bias[1] == 0.0 ? B3_BIAS1_ZERO : 0);
       DrvSolveRet r;
       r[0] = nMass[0]; r[1] = nMass[1]; r[2] = bias[0]; r[3] = bias[1]; r[4] = bounce[0]; r[5] = bounce[1];
@@ -1070,7 +1074,7 @@ DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + 
   }
 DRV_PROF(const unsigned long long P3 = __builtin_amdgcn_s_memtime();)
   const int bits = drv_slot_verdicts(lane, pk, a_pair, restIn, bias[0] == 0.0, bias[1] == 0.0, jn[0], jn[1], jt[0], jt[1], jBias[0], jBias[1], false);
-DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + blockIdx.x * 8; const unsigned long long P4 = __builtin_amdgcn_s_memtime(); d[2] += (P1 - P0) + ((P4 - P3) << 32); d[3] += (P2 - P1) + ((P3 - P2) << 32); })
+DRV_PROF(if (lane == 0 && g_L.profEnv < 4096) { unsigned long long* d = g_dbgp + g_L.profEnv * 8; const unsigned long long P4 = __builtin_amdgcn_s_memtime(); d[2] += (P1 - P0) + ((P4 - P3) << 32); d[3] += (P2 - P1) + ((P3 - P2) << 32); })
   DrvSolveRet r;  // (only the low word of [11] means anything)
   r[11] = drv_pack2(bits DRV_PROF(| (prof_any(profMode) << SOLVE_PROF_SH)), 0);
   return r;
@@ -1222,7 +1226,7 @@ DRV_PROF(nMath += __builtin_amdgcn_s_memtime();)
     __syncthreads();
   }
   __syncthreads();
-DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgl + blockIdx.x * 8; d[6] += (N1 - T0) + (nMath << 32); d[7] += __builtin_amdgcn_s_memtime() - N1 - nMath; })
+DRV_PROF(if (lane == 0 && g_L.profEnv < 4096) { unsigned long long* d = g_dbgl + g_L.profEnv * 8; d[6] += (N1 - T0) + (nMath << 32); d[7] += __builtin_amdgcn_s_memtime() - N1 - nMath; })
   if (mode == 0 && wave_ballot(lightBad) == 0ull) { lightOk = true; break; }
   }
   if (lightOk) {
@@ -1424,7 +1428,7 @@ DRV_PROF(const unsigned long long U4 = __builtin_amdgcn_s_memtime();)
   }
 
 DRV_PROF(const unsigned long long T2 = __builtin_amdgcn_s_memtime();)
-DRV_PROF(if (lane == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgs + blockIdx.x * 8; d[0] += U1 - T1; d[1] += U2 - U1; d[2] += U3 - U2; d[3] += U4 - U3; d[4] += T2 - U4; })
+DRV_PROF(if (lane == 0 && g_L.profEnv < 4096) { unsigned long long* d = g_dbgs + g_L.profEnv * 8; d[0] += U1 - T1; d[1] += U2 - U1; d[2] += U3 - U2; d[3] += U4 - U3; d[4] += T2 - U4; })
   // everything per-slot from here on - prestep, solve, the steady / inert verdicts and the slot record - happens inside the
   // function: nothing of the contact cache stays live in this frame across the call
   const int pkArg = pk_pack(a_state, a_count, a_age, touched, freeMe, hashSame, prevInert, skipped, slotOcc, active);
@@ -1444,13 +1448,13 @@ DRV_PROF(const unsigned long long S0 = __builtin_amdgcn_s_memtime();)
                                                      sv[6], sv[7], sv[8], sv[9], __double2loint(sv[10]), __double2hiint(sv[10]), (solveBits >> SR_BITS3_SH) & 7);
 DRV_PROF(const unsigned long long S1 = __builtin_amdgcn_s_memtime();)
       solveBits = drv_split_verdicts(fresh_lane(), sr.pk, sr.pair, sr.bits, sr.jn0, sr.jn1, sr.jb0, sr.jb1, sr.jt0, sr.jt1) DRV_PROF(| (4 << SOLVE_PROF_SH));
-DRV_PROF(if (fresh_lane() == 0 && blockIdx.x < 4096) { unsigned long long* d = g_dbgp + blockIdx.x * 8; d[3] += (S1 - S0) << 32; d[2] += (__builtin_amdgcn_s_memtime() - S1) << 32; })
+DRV_PROF(if (fresh_lane() == 0 && g_L.profEnv < 4096) { unsigned long long* d = g_dbgp + g_L.profEnv * 8; d[3] += (S1 - S0) << 32; d[2] += (__builtin_amdgcn_s_memtime() - S1) << 32; })
     }
   }
   occ &= ~freeMask;
 DRV_PROF(const unsigned long long T3 = T2, T4 = T2, T5 = __builtin_amdgcn_s_memtime(); const int profModeW = (uniform_i(solveBits) >> SOLVE_PROF_SH) & 7;)
-DRV_PROF(if (lane == 0 && blockIdx.x < 4096) {
-  unsigned long long* d = g_dbgp + blockIdx.x * 8;
+DRV_PROF(if (lane == 0 && g_L.profEnv < 4096) {
+  unsigned long long* d = g_dbgp + g_L.profEnv * 8;
   d[0] += T1 - T0; d[1] += T2 - T1; d[2] += T3 - T2; d[3] += T4 - T3; d[4] += T5 - T4;
   d[5] += 1ull + (light ? (1ull << 16) : 0ull);
   d[6] += (unsigned long long)(maxLevel + 1) + ((unsigned long long)(maxLevel + 1) << (12 * profModeW));
@@ -1477,8 +1481,12 @@ DE_OOL int drv_partial_obs_fused(PvIn in, uint64_t seed, int A, int* envi, int e
 #ifndef DRV_FUSED_AGENTS
 #define DRV_FUSED_AGENTS 10 /* without a forecast: agent passes a light environment runs in the step launch */
 #endif
-enum { LR_MOVING = 1, LR_REMOVED = 2, LR_CAND_CHANGED = 4 };  // DrvLightRet.bits
-enum { LS_VB_VALID = 1, LS_AABB_VALID = 2 };                 // drv_light_substep's stateBits
+// DrvLightRet.bits, every one wave-uniform.  LR_PREV_ALLFIN: every car was finished and not crashed in the flags as loaded at ENTRY,
+// i.e. at the end of the previous substep, callbacks included (the kernel's bookkeeping of that substep, read off the batch this one
+// loads anyway).  LR_FAST / LR_QUIET / LR_REPLAY: the substep solves nothing and which kind it is; the velocity update is done then.
+enum { LR_PREV_ALLFIN = 1, LR_FAST = 2, LR_QUIET = 4, LR_REPLAY = 8, LR_CAND_CHANGED = 16, LR_ANY_MOVING = 32, LR_STEADY_OK = 64, LR_ANY_DIRTY = 128 };
+// drv_light_substep's stateBits: the kernel's wave-uniform state the decision fast / quiescent / steady replay reads
+enum { LS_VB_VALID = 1, LS_AABB_VALID = 2, LS_OCC = 4, LS_INERT = 8, LS_STEADY = 16 };
 struct DrvLightRet {
   int cand, dirty, bits;
 };
@@ -1503,13 +1511,18 @@ DRV_PROF(const unsigned long long Q0 = __builtin_amdgcn_s_memtime();)
     const int bi = lane & (DRV_NB - 1), ci = lane < DRV_MAXA ? lane : DRV_MAXA - 1;
     int f = L.flags[bi];
     double px = L.px[bi], py = L.py[bi], vx = L.vx[bi], vy = L.vy[bi], ang = L.ang[bi];
-    const double w = L.w[bi];
-    const double vbx = vbValid ? L.vbx[bi] : 0.0, vby = vbValid ? L.vby[bi] : 0.0, wb = vbValid ? L.wb[bi] : 0.0;
+    double w = L.w[bi];
+    // (loaded with the batch whatever vbValid says - a wave-uniform branch around each load cost more than the load - and selected)
+    const double l_vbx = L.vbx[bi], l_vby = L.vby[bi], l_wb = L.wb[bi];
+    const double cmass = L.cmass[ci];
     double rcv = L.rc[ci], rsv = L.rs[ci], rotAngv = L.rotAng[ci], cosRel0v = L.cosRel0[ci];
     const double goalx = L.goalx[ci], goaly = L.goaly[ci], dprev = L.dprev[ci], chx = L.chx[ci], chy = L.chy[ci];
     double rew = L.rewAcc[ci], posrew = L.posAcc[ci];
     int moving = L.moving[bi];
+    const double vbx = vbValid ? l_vbx : 0.0, vby = vbValid ? l_vby : 0.0, wb = vbValid ? l_wb : 0.0;
     if (!isBody) { f = 0; px = 0.0; py = 0.0; vx = 0.0; vy = 0.0; }
+    // bookkeeping :280-287 of the PREVIOUS substep, before tick touches f
+    const bool prevAllFin = wave_ballot(isCar && !(CARF_FIN(f) && !CARF_CRASHED(f))) == 0ull;
     // ---- common prefix of cars and pedestrians, ONE instruction stream for both (the two roles sit on different lanes of the
     //      wave: what each does on its own is executed one after the other): after processAction, the lane classification of the
     //      position - min over the two roads of Road.isPointOnRoad - with the car's cached cos(road - angle) or, for a pedestrian
@@ -1584,8 +1597,7 @@ DRV_PROF(const unsigned long long Q2 = __builtin_amdgcn_s_memtime();)
       }
       f = CARF_SET_LP(f, lp);
       if (px >= DRV_W + 50.0 || px <= -50.0 || py >= DRV_H + 50.0 || py <= -50.0) { vx = 0.0; vy = 0.0; }  // prevPos == pos here
-      L.flags[lane] = f;
-      L.vx[lane] = vx; L.vy[lane] = vy;
+      L.flags[lane] = f;  // (vx, vy: stored once, at the end)
       L.rewAcc[lane] = rew; L.posAcc[lane] = posrew;
 DRV_PROF(asm volatile("" ::: "memory");)
     } else if (isPed) {
@@ -1629,7 +1641,6 @@ DRV_PROF(asm volatile("" ::: "memory");)
         }
         L.moving[lane] = moving;
         L.flags[lane] = PEDF_PACK(PEDF_ROAD(f), side, 0, crossing, beginc, PEDF_SPEED(f));
-        L.vx[lane] = vx; L.vy[lane] = vy;
       }
     }
 
@@ -1711,14 +1722,39 @@ DRV_PROF(const unsigned long long Q4 = __builtin_amdgcn_s_memtime();)
       removed = lastCand < 0 || (lastCand & ~cand) != 0;
     }
   L.lastCand[lane] = cand;
-DRV_PROF(if (lane == 0 && blockIdx.x < 4096) {
-  unsigned long long* d = g_dbgl + blockIdx.x * 8;
+  // ======== which path the substep takes (the kernel's comments at the substep loop say why each is exact) ==========
+  const bool occAny = (uniform_i(stateBits) & LS_OCC) != 0, inertAll = (uniform_i(stateBits) & LS_INERT) != 0, steadyAll = (uniform_i(stateBits) & LS_STEADY) != 0;
+  const bool candChanged = wave_ballot(cand != lastCand) != 0ull, anyMoving = wave_ballot(candMoving) != 0ull;
+  if (candChanged && lane == 0) L.clistN = -1;  // the contact path's candidate list belongs to other masks now
+  const bool fast = wave_ballot(cand != 0) == 0ull && !occAny;
+  const bool quiescent = inertAll && !candChanged && !anyMoving;
+  const bool steadyOk = !quiescent && steadyAll && wave_ballot(removed) == 0ull;
+  const bool anyDirty = wave_ballot(dirty != 0) != 0ull;
+  const bool replay = !fast && steadyOk && !anyDirty;
+  // Nothing to solve: the substep ends here with the velocity update (velocity_update's arithmetic) on the registers that hold what
+  // tick / the FSM left - a pedestrian's dead bit is not one the FSM changes, a replay's L.vb* stay as they are.
+  if (isBody) {
+    if (fast || quiescent || replay) {
+      double m, fr, rfr;
+      bool dflt = false;
+      if (isCar) { m = cmass; fr = CARF_FRIC(f) ? 5e-4 : 5e-5; rfr = CARF_FRIC(f) ? 2e-5 : 1e-5; }
+      else { m = CarK::pedMass; fr = 5e-2; rfr = 2e-4; dflt = !PEDF_DEAD(f); }
+      if (dflt) { vx = vx * 1.0 + (0.0 + 0.0) * DE_DT; vy = vy * 1.0 + (0.0 + 0.0) * DE_DT; w = w * 1.0 + 0.0; }
+      else apply_friction(vx, vy, w, m, fr, rfr, 0.0);
+      L.w[lane] = w;
+    }
+    L.vx[lane] = vx; L.vy[lane] = vy;  // (a dead pedestrian on the way to the contact path: what it loaded)
+  }
+DRV_PROF(if (lane == 0 && g_L.profEnv < 4096) {
+  unsigned long long* d = g_dbgl + g_L.profEnv * 8;
   const unsigned long long Q5 = __builtin_amdgcn_s_memtime();
   if (it == 0) { for (int k = 0; k < 8; ++k) d[k] = 0ull; }
   d[0] += Q1 - Q0; d[1] += Q2 - Q1; d[2] += Q3 - Q2; d[3] += Q4 - Q3; d[4] += Q5 - Q4; d[5] += Q5 - Q0;
 })
   DrvLightRet ret;
-  ret.cand = cand; ret.dirty = dirty; ret.bits = (candMoving ? LR_MOVING : 0) | (removed ? LR_REMOVED : 0) | (cand != lastCand ? LR_CAND_CHANGED : 0);
+  ret.cand = cand; ret.dirty = dirty;
+  ret.bits = (prevAllFin ? LR_PREV_ALLFIN : 0) | (fast ? LR_FAST : 0) | (quiescent && !fast ? LR_QUIET : 0) | (replay && !quiescent ? LR_REPLAY : 0) |
+             (candChanged ? LR_CAND_CHANGED : 0) | (anyMoving ? LR_ANY_MOVING : 0) | (steadyOk ? LR_STEADY_OK : 0) | (anyDirty ? LR_ANY_DIRTY : 0);
   return ret;
 }
 // ------------------------------------------------------------------------------------------------
@@ -1873,7 +1909,7 @@ DRV_PROF(const unsigned long long KS = isoT0;)
     if ((S.iso_on == 1 || S.iso_on == 2) && lane == 0) __atomic_store_n(&S.iso_done[e], tick, __ATOMIC_RELAXED);
     return;
   }
-DRV_PROF(if (lane < 8 && e < 4096) { g_dbgp[e * 8 + lane] = 0ull; g_dbgs[e * 8 + lane] = 0ull; })
+DRV_PROF(if (lane == 0) L.profEnv = e; if (lane < 8 && e < 4096) { g_dbgp[e * 8 + lane] = 0ull; g_dbgs[e * 8 + lane] = 0ull; })
   const int A = S.A;
   int* envi = S.envi + (size_t)e * EI_COUNT;
   int elapsed = uniform_i(envi[EI_ELAPSED]);
@@ -1936,41 +1972,46 @@ DRV_PROF(const unsigned long long K0 = __builtin_amdgcn_s_memtime(); unsigned lo
 DRV_PROF(const unsigned long long A0 = __builtin_amdgcn_s_memtime();)
     // ======== phase 1a: car game logic (processAction at substep 0, tick) ===================================
     const DrvLightRet lr = drv_light_substep(it, lane, A, nPed, nObst, elapsed, (uint32_t)S.seed, (uint32_t)(S.seed >> 32), genv, episode,
-                                             (vbValid ? LS_VB_VALID : 0) | (aabbValid ? LS_AABB_VALID : 0));
+                                             (vbValid ? LS_VB_VALID : 0) | (aabbValid ? LS_AABB_VALID : 0) | (occ != 0ull ? LS_OCC : 0) |
+                                             (inertAll ? LS_INERT : 0) | (steadyAll ? LS_STEADY : 0));
     const int cand = lr.cand, dirty = lr.dirty;
-    const bool candMoving = (lr.bits & LR_MOVING) != 0, removed = (lr.bits & LR_REMOVED) != 0;
+    const int lb = uniform_i(lr.bits);
     aabbValid = true;
+    // ======== bookkeeping :280-287 of the previous substep: read off the flags this substep's batch loaded (after that substep's
+    // callbacks), applied with the elapsed time it ended at.  (Substep 0's entry is the state before the step: EI_ALLFIN has it.)
+    if (it > 0 && !allFinished && (lb & LR_PREV_ALLFIN)) {
+      allFinished = 1;
+      finishedAt = elapsed;
+    }
 DRV_PROF(const unsigned long long A1 = A0;)
-    const uint64_t anyCand = wave_ballot(cand != 0);
+    // The paths of a substep, decided in drv_light_substep over the values it computes (LR_*):
+    // Fast: no candidate pair and an empty contact cache.
     // Quiescent contact set: same candidate pairs as in the previous substep, every body in them exactly at rest and
     // every cached arbiter inert (zero bias, zero accumulated impulse, not first contact).  Then narrowphase, arbiter
     // update, warm start and all 10 solver iterations are exact no-ops (DESIGN.md "quiescent shortcut") and only the
     // velocity update remains.
-    const bool candChanged = wave_ballot((lr.bits & LR_CAND_CHANGED) != 0) != 0ull, anyMoving = wave_ballot(candMoving) != 0ull;
-    if (candChanged && lane == 0) L.clistN = -1;  // the contact path's candidate list belongs to other masks now
-    const bool quiescent = inertAll && !candChanged && !anyMoving;
     // Steady replay: the contact path of the previous substep reported every slot steady, the candidate set is the
     // same and every body in it is frozen => this substep's contact path would read the same inputs and reproduce the
     // same outputs: slots unchanged, velocities stay zero, bias velocities equal to the saved ones.
     // If some pairs are dirty, the contact path first tests only those ("light" mode) and falls back to the full path
     // when one of them touches or owns a slot.
-    const bool steadyOk = !quiescent && steadyAll && wave_ballot(removed) == 0ull;
-    const bool anyDirty = wave_ballot(dirty != 0) != 0ull;
-    bool replay = steadyOk && !anyDirty;
+    // On all three the velocity update is done already: the substep made one call.
+    const bool fast = (lb & LR_FAST) != 0, quiescent = (lb & LR_QUIET) != 0, replay = (lb & LR_REPLAY) != 0;
     // (a light-mode attempt that fails is paid on top of the full path, and what made it fail - a moving car leaning on a
     // resting pile - persists: after a failure the rest of the step goes straight to the full path.  Both give the same result.)
-    const bool light = steadyOk && anyDirty && !lightOff;
-    if (!(anyCand == 0ull && occ == 0ull) && !quiescent && !replay) cntA += candChanged ? DRV_CNT(EI_N_WHY_CAND) : anyMoving ? DRV_CNT(EI_N_WHY_MOVING) : DRV_CNT(EI_N_WHY_INERT);
+    const bool light = (lb & LR_STEADY_OK) && (lb & LR_ANY_DIRTY) && !lightOff;
+    if (!fast && !quiescent && !replay) cntA += (lb & LR_CAND_CHANGED) ? DRV_CNT(EI_N_WHY_CAND) : (lb & LR_ANY_MOVING) ? DRV_CNT(EI_N_WHY_MOVING) : DRV_CNT(EI_N_WHY_INERT);
 
 DRV_PROF(const unsigned long long A2 = __builtin_amdgcn_s_memtime(); bool tookContact = false;)
-    cntA += (anyCand == 0ull && occ == 0ull) ? DRV_CNT(EI_N_FAST) : quiescent ? DRV_CNT(EI_N_QUIET) : replay ? DRV_CNT(EI_N_STEADY) : DRV_CNT(EI_N_CONTACT);
+    cntA += fast ? DRV_CNT(EI_N_FAST) : quiescent ? DRV_CNT(EI_N_QUIET) : replay ? DRV_CNT(EI_N_STEADY) : DRV_CNT(EI_N_CONTACT);
     cntB += (unsigned)__popcll(occ);
-    if ((anyCand == 0ull && occ == 0ull) || quiescent) {
-      // ---------- fast path: nothing touches and the contact cache is empty (or quiescent): velocity update only
-      velocity_update_ool(A | (nPed << 8));
-      if (anyCand == 0ull && occ == 0ull) steadyAll = false;
+    if (fast || quiescent) {
+      // ---------- fast path: nothing touches and the contact cache is empty (or quiescent)
+      if (fast) steadyAll = false;
       vbValid = false;  // nothing was solved: the next position update sees zero bias velocities
-    } else if (!replay) {
+    } else if (replay) {
+      vbValid = true;  // L.vb* still hold the bias velocities of the solve being replayed
+    } else {
       // ---------- contact path: narrowphase -> contact cache -> callbacks -> prestep -> friction -> solver
 DRV_PROF(tookContact = true;)
       __builtin_amdgcn_s_setprio(3);  // an environment on the contact path is on the launch's critical path: issue it first
@@ -1978,31 +2019,28 @@ DRV_PROF(tookContact = true;)
       lane = fresh_lane();
       if (wave_ballot((cr.err & CRET_OVERFLOW) != 0) != 0ull && lane == 0) L.stepErr |= DYNENV_ERRBIT_OVERFLOW;
       if (light && !(uniform_i(cr.err >> CRET_LIGHT_REPLAY_SH) & 1)) lightOff = true;
-      if (uniform_i(cr.err >> CRET_LIGHT_REPLAY_SH) & 1) {  // light mode: no dirty pair touches => replay
-        replay = true; cntB = (unsigned)uniform_i((int)(cntB + (1u << 8)));
+      if (uniform_i(cr.err >> CRET_LIGHT_REPLAY_SH) & 1) {  // light mode: no dirty pair touches => replay, the L.vb* as they are
+        cntB = (unsigned)uniform_i((int)(cntB + (1u << 8)));
+        velocity_update_ool(A | (nPed << 8));
       } else {
         cntB = (unsigned)uniform_i((int)(cntB + ((unsigned)(uniform_i(cr.err >> CRET_SPLIT_SH) & 1) << 12)));
         occ = uniform_u64(cr.occ);
         inertAll = (uniform_i(cr.err >> CRET_INERT_SH) & 1) != 0;
         steadyAll = (uniform_i(cr.err >> CRET_STEADY_SH) & 1) != 0;
-        vbValid = true;
       }
-    }
-    if (replay) {  // L.vb* still hold the bias velocities of the solve being replayed
-      velocity_update_ool(A | (nPed << 8));
       vbValid = true;
     }
-    __syncthreads();
-    if (!PARTIAL) lane = fresh_lane();  // (on every path: the copy of the loop's top is not kept across the calls above; seen in the ISA -
-                                        //  the Partial kernel then stores the register that carries its scalar values instead)
-
+    // (no barrier: the block is one wave and the hardware completes a wave's LDS operations in order; the empty asm keeps the compiler
+    //  from moving the next substep's - or the epilogue's - loads in front of what this one stored)
+    asm volatile("" ::: "memory");
 DRV_PROF(const unsigned long long A3 = __builtin_amdgcn_s_memtime(); tPh1 += A1 - A0; tBroad += A2 - A1; if (tookContact) tCont += A3 - A2; else tFast += A3 - A2;)
-    // ======== bookkeeping :280-287 =========================================================================
     elapsed += 1;
+  }
+  lane = fresh_lane();
+  {  // bookkeeping of the tenth substep: the one read of the flags that is left
     bool notDone = false;
-    if (isCar) { int f = L.flags[lane]; notDone = !(CARF_FIN(f) && !CARF_CRASHED(f)); }
-    const bool allFin = wave_ballot(notDone) == 0ull;
-    if (!allFinished && allFin) {
+    if (lane < A) { const int f = L.flags[lane]; notDone = !(CARF_FIN(f) && !CARF_CRASHED(f)); }
+    if (!allFinished && wave_ballot(notDone) == 0ull) {
       allFinished = 1;
       finishedAt = elapsed;
     }
