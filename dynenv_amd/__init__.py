@@ -8,7 +8,7 @@ from .vec_env import BatchedDynEnv, make_dyn_env
 from .arranger import GpuInOutArranger, groups_for
 
 __all__ = ["BatchedDynEnv", "make_dyn_env", "DynEnvType", "NoiseType", "ObservationType", "GpuInOutArranger", "GpuInputLayer",
-           "GpuEmbedInputLayer", "EmbedBlock", "GpuTemporalAttention", "GpuRecurrentHead", "GpuFeatureExtractor", "GpuPolicyHead", "GpuRolloutStorage", "GpuRollout", "groups_for"]
+           "GpuEmbedInputLayer", "EmbedBlock", "GpuTemporalAttention", "GpuRecurrentHead", "GpuFeatureExtractor", "GpuPolicyHead", "GpuRolloutStorage", "GpuRollout", "GpuICM", "groups_for"]
 
 
 def __getattr__(name):
@@ -27,4 +27,7 @@ def __getattr__(name):
     if name in ("GpuRolloutStorage", "GpuRollout"):
         from . import rollout
         return getattr(rollout, name)
+    if name == "GpuICM":
+        from . import icm
+        return icm.GpuICM
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

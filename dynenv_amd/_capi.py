@@ -105,6 +105,10 @@ class Policy(C.Structure):  # dynenv_policy_t: device pointers of the policy hea
                                           "critic_w2", "critic_b2")]
 
 
+class Icm(C.Structure):  # dynenv_icm_t: device pointers of the curiosity module; fwd_w1, fwd_w2 and inv_w 16 bit, the rest float32
+    _fields_ = [(n, C.c_void_p) for n in ("fwd_w1", "fwd_w1_act", "fwd_b1", "fwd_w2", "fwd_b2", "inv_w", "inv_b")]
+
+
 vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
 
 # THE binding of include/dynenv.h: name -> (restype, argtypes), in the header's order of growth.  load() sets exactly these, so an entry
@@ -169,10 +173,12 @@ SIGNATURES = {
     "dynenv_arrange_embed_pad": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(ArrType), i32, vp, i32, C.POINTER(EmbedBlock), i32, C.c_float, C.c_float,
                                            vp, i32, vp]),
     "dynenv_attend_pool": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, C.POINTER(Mha), C.POINTER(Mha), vp, vp, C.c_float, vp, vp, vp, vp]),
-    # (the two of the rollout storage stand in front of the two heads: tests/test_policy_host.py pins the last two names of the table)
+    # (the two of the rollout storage and the curiosity module's stand in front of the two heads: tests/test_policy_host.py pins the last
+    # two names of the table)
     "dynenv_rollout_insert": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                         vp, vp]),
     "dynenv_rollout_returns": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp]),
+    "dynenv_icm_losses": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), i32, i32, C.POINTER(Icm), C.c_float, vp, vp, vp, vp, vp]),
     "dynenv_recurrent_head": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.POINTER(Rhead), C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
     "dynenv_policy_head": (C.c_int, [vp, vp, i32, i32, i32, i32, C.POINTER(Policy), C.POINTER(i32), i32, i32, i32, C.c_uint64, vp, C.c_uint64,
                                      C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]),

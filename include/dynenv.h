@@ -786,6 +786,56 @@ int dynenv_rollout_returns(const float* rewards_dev, const float* values_dev, co
                            int32_t E, int32_t A, int32_t mode, float gamma, float gae_lambda, float* returns_dev, float* advantages_dev,
                            void* stream);
 
+/* ---- the curiosity module over a stored rollout, where no gradient is wanted: the reference's ICMNet (DynEnv/models/icm.py) - the
+ * forward net of ICMDynamics on cat(f_t, one_hot(a_t)) (icm.py:112-146, 218-226), its inverse net, an ActorLayer, on cat(f_t, f_{t+1})
+ * (icm.py:228-238), and the terms of _calc_loss (icm.py:77-109) - on the buffers of the rollout storage above.  Neither the one-hot
+ * (icm.py:167-179: a Python loop with one host read per action), the two cats, the hidden layer, the prediction nor the logits exist
+ * in memory.  A HOST struct of device pointers: the three matrices in the 16-bit type w_dtype (the operands of the matrix units),
+ * everything else float32.  H = 140 is the forward net's hidden width (icm.py:124), H' = 160 its padded size: the rows of fwd_w1 and
+ * the columns of fwd_w2 from H on are +0, as are fwd_b1 and the columns of fwd_w1_act from H on; N = sum n_g. */
+#define DYNENV_ICM_HIDDEN 140     /* H: ForwardNet.fc_hidden */
+#define DYNENV_ICM_HIDDEN_PAD 160 /* H': H rounded up to the 32 elements of a k step of the second product */
+typedef struct dynenv_icm {
+  const void  *fwd_w1;     /* [160][K] the first K columns of pred_net.fwd_net.fc1.weight, rows from 140 on +0 (16-bit type) */
+  const float *fwd_w1_act; /* [N][160] the N one-hot columns of fc1.weight, transposed: row start_g + a is what action a of group g adds; columns from 140 on +0 */
+  const float *fwd_b1;     /* [160] fc1.bias, +0 from 140 on */
+  const void  *fwd_w2;     /* [K][160] pred_net.fwd_net.fc2.weight, columns from 140 on +0 (16-bit type) */
+  const float *fwd_b2;     /* [K] fc2.bias */
+  const void  *inv_w;      /* [32][2K] every pred_net.inv_net.blocks.*.Layer.*.weight in the order of ActorLayer.forward's flattened list; rows from N on +0, as in dynenv_policy_t's actor_w (16-bit type) */
+  const float *inv_b;      /* [32] the biases in the same order, +0 from N on */
+} dynenv_icm_t;
+/* dynenv_icm_losses, two launches, capturable (launches and nothing else: nothing is synchronised, allocated or copied; pointers and
+ * sizes are frozen by a capture, contents are read at replay).  features_dev float32 [T+1][P][K], actions_dev float32 [T][AD][P] and
+ * finished_dev uint8 [T][P] are the storage's buffers (finished_dev NULL: nobody finished); nvec is a HOST array of the G group sizes
+ * n_g, start_g = n_0 + .. + n_{g-1}; action_cols = AD, G <= AD <= 8: only the action columns 0..G-1 are read.  An action value is
+ * rounded to the nearest integer and clamped into 0..n_g-1 for addressing; a value that had to be clamped ORs bit 0 into status_dev[0]
+ * (int32 [1], or NULL), which the kernel never clears - the reference raises an IndexError there.  Per row (t, p), all non-matrix
+ * arithmetic in float32, f_t = features[t][p]:
+ *   hid  = leaky(f_t W1[:, :K]^T + b1 + sum_g W1_act[start_g + a_g]; slope)   - the one-hot's product is a gather, added in group order
+ *   pred = hid W2^T + b2;   curiosity[t][p] = (sum_k (pred_k - f_{t+1,k})^2) / K   - the error against the float32 f_{t+1}
+ *   l    = cat(f_t, f_{t+1}) W_inv^T + b_inv;   inverse_ce[t][g][p] = logsumexp(l_g) - l_g[a_g]   - max-subtracted: (m + log(sum_j
+ *          exp(l_j - m))) - l_a, which is exactly 0 for a group of one action
+ * curiosity_dev float32 [T][P] is F.mse_loss(pred, next, reduction="none").mean(-1), the intrinsic-reward signal of the ICM paper;
+ * inverse_ce_dev float32 [T][G][P] is F.cross_entropy(..., reduction="none") per group, in log_probs' layout.  EVERY element of both is
+ * written exactly once, finished rows included: the mask belongs to the losses.
+ * losses_dev float32 [3] or NULL: when given, a second launch reduces the two under the mask = !finished, n = the number of its true
+ * entries, into { sum_mask curiosity / n,  (sum_g sum_mask inverse_ce_g) / (n G),  (float) n } - ICMNet._calc_loss's forward and
+ * inverse losses (icm.py:91, 98-100) before their coefficients, which are the caller's business.  It accumulates in double, in one fixed
+ * order, and rounds once; the first two are +0 where n == 0 (the reference's early return, icm.py:80-86).
+ * Arithmetic: the three matrix products take 16-bit operands of w_dtype (DYNENV_ARR_BF16 / _F16) on the matrix units and accumulate
+ * in float32 - the hidden layer is rounded to w_dtype between the two products of the forward net; biases, the gather, the LeakyReLU,
+ * the squared error and the logsumexp are float32.  Every sum has one fixed order: a row's result depends on features[t][p],
+ * features[t+1][p], actions[t][:, p] and the weights alone - not on its place in the launch, on T, on P or on its neighbours - and
+ * the same call twice gives the same bits.  Inputs that are not finite are outside the contract.
+ * Errors, DYNENV_ERR_ARG, all reported before a device is looked for: a NULL features_dev, actions_dev, nvec, w, curiosity_dev or
+ * inverse_ce_dev, or one of w's seven pointers; T, P or K < 1; G outside 1..8, an n_g outside 1..16, N > 32, AD outside G..8; a dtype
+ * outside 0..2; features_dev, actions_dev, finished_dev, an output or a weight buffer not 16-byte aligned (losses_dev, status_dev:
+ * 4-byte); (T + 1) * P > 2^30 (the launch limit).  Then what the kernel does not take: DYNENV_ARR_F32, a K other than 64, 128 or
+ * 256: DYNENV_ERR_UNSUPPORTED, also before the device. */
+int dynenv_icm_losses(const float* features_dev, const float* actions_dev, const uint8_t* finished_dev, int32_t T, int32_t P, int32_t K,
+                      int32_t action_cols, const int32_t* nvec, int32_t G, int32_t w_dtype, const dynenv_icm_t* w, float slope,
+                      float* curiosity_dev, float* inverse_ce_dev, float* losses_dev, int32_t* status_dev, void* stream);
+
 
 /* Device self-test of the deterministic math header: evaluates sincos/atan2/sqrt/div on n host-provided doubles and
  * returns the raw results so tests can compare them bit-for-bit with the host evaluation. out: [n,5]. */
