@@ -105,6 +105,14 @@ class Policy(C.Structure):  # dynenv_policy_t: device pointers of the policy hea
                                           "critic_w2", "critic_b2")]
 
 
+class IcmBwd(C.Structure):  # dynenv_icm_bwd_t: the transposed 16-bit copies the backward's products read
+    _fields_ = [(n, C.c_void_p) for n in ("fwd_w2_t", "fwd_w1_t", "inv_w_t")]
+
+
+class IcmGrad(C.Structure):  # dynenv_icm_grad_t: float32 device pointers of the seven gradients, in the packed operands' layouts
+    _fields_ = [(n, C.c_void_p) for n in ("d_fwd_w1", "d_fwd_w1_act", "d_fwd_b1", "d_fwd_w2", "d_fwd_b2", "d_inv_w", "d_inv_b")]
+
+
 class Icm(C.Structure):  # dynenv_icm_t: device pointers of the curiosity module; fwd_w1, fwd_w2 and inv_w 16 bit, the rest float32
     _fields_ = [(n, C.c_void_p) for n in ("fwd_w1", "fwd_w1_act", "fwd_b1", "fwd_w2", "fwd_b2", "inv_w", "inv_b")]
 
@@ -179,6 +187,9 @@ SIGNATURES = {
                                         vp, vp]),
     "dynenv_rollout_returns": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp]),
     "dynenv_icm_losses": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), i32, i32, C.POINTER(Icm), C.c_float, vp, vp, vp, vp, vp]),
+    "dynenv_icm_backward_workspace": (C.c_int, [i32, i32, C.POINTER(C.c_uint64)]),
+    "dynenv_icm_backward": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), i32, i32, C.POINTER(Icm), C.c_float, vp, vp, C.POINTER(IcmBwd),
+                                      C.POINTER(IcmGrad), vp, vp, C.c_uint64, vp, vp]),
     "dynenv_recurrent_head": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.POINTER(Rhead), C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
     "dynenv_policy_head": (C.c_int, [vp, vp, i32, i32, i32, i32, C.POINTER(Policy), C.POINTER(i32), i32, i32, i32, C.c_uint64, vp, C.c_uint64,
                                      C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]),

@@ -11,6 +11,7 @@ from . import _capi
 HIDDEN, HIDDEN_PAD = 140, 160   # DYNENV_ICM_HIDDEN, DYNENV_ICM_HIDDEN_PAD
 MAX_ROWS, MAX_GROUPS, MAX_GROUP, MAX_COLS = 32, 8, 16, 8   # the kernel's limits (include/dynenv.h)
 FUSED_K = (64, 128, 256)
+FUSED_BACKWARD_K = (64, 128)   # what dynenv_icm_backward takes: at 256 the weight gradients do not fit the register file
 
 ICMLosses = collections.namedtuple("ICMLosses", ["loss", "inverse", "forward", "long_horizon_forward"])
 
@@ -139,6 +140,13 @@ def _classes():
                        refreshed IN PLACE (fixed pointers, torch ops on the stream) when a parameter's version changes.
               "torch (fallback: why)"  where no gradient is wanted but the kernel does not take the call - loss_attention=True and
                        DYNENV_ICM_FUSED=0 in the environment among the reasons.  Nothing is raised.
+              "fused (backward)"  only with fused_backward=True, when gradients are enabled and an input or a parameter requires
+                       one: the losses are the "fused" route's, bit for bit, behind a torch.autograd.Function, and loss.backward()
+                       is ONE call of dynenv_icm_backward (csrc/icm_backward_kernels.hip), which recomputes the forward per row from
+                       the saved inputs - nothing else is saved - and fills the .grad of exactly pred_net.* and, where wanted, of
+                       `features`.  The "fused" route's conditions, K of 64 or 128; otherwise "torch (fallback: why)", differentiable
+                       as the torch route is.  Gradient and workspace buffers are the module's, at fixed addresses; the transposed
+                       packed copies the kernel reads are refreshed with the others.  Not twice differentiable.
             The routes differ by the rounding of the matrix products' operands to w_dtype.
 
             Deliberate differences from the reference.
@@ -150,7 +158,7 @@ def _classes():
               * A clamped action raises nothing: it sets the status bit."""
 
             def __init__(self, feature_size, groups, rollout_size, forward_coeff=1e-2, icm_beta=1e-2, long_horizon_coeff=0.0, loss_attention=False,
-                         w_dtype=torch.bfloat16, device=None):
+                         w_dtype=torch.bfloat16, device=None, fused_backward=False):
                 super().__init__()
                 self.feature_size, self.rollout_size = int(feature_size), int(rollout_size)
                 blocks = _blocks(groups)
@@ -170,8 +178,10 @@ def _classes():
                 self.register_buffer("_starts", torch.tensor(starts, dtype=torch.int64, device=device), persistent=False)
                 self.register_buffer("_last", torch.tensor(self.groups, dtype=torch.int64, device=device) - 1, persistent=False)
                 self.register_buffer("status", torch.zeros(1, dtype=torch.int32, device=device), persistent=False)
+                self.fused_backward = bool(fused_backward)
                 self._route = None
                 self._packed = None
+                self._bwd = None
 
             @property
             def last_route(self):
@@ -261,15 +271,21 @@ def _classes():
                         return "parameters that are not float32 and on %s" % (dev,)
                 return None
 
-            def _weights(self, dev):
-                """the packed operands of dynenv_icm_t, made once per device and refreshed in place when a parameter changed"""
+            def _params(self):
+                """the parameters of pred_net in the order the fused backward returns their gradients"""
+                fwd = self.pred_net.fwd_net
+                return [fwd.fc1.weight, fwd.fc1.bias, fwd.fc2.weight, fwd.fc2.bias] + [q for l in self._linears() for q in (l.weight, l.bias)]
+
+            def _weights(self, dev, backward=False):
+                """the packed operands of dynenv_icm_t, made once per device and refreshed in place when a parameter changed; with
+                `backward` (and from then on) the transposed copies of dynenv_icm_bwd_t too, refreshed in the same pass"""
                 K, N, dt = self.feature_size, sum(self.groups), self.w_dtype
                 fwd, lin = self.pred_net.fwd_net, self._linears()
                 params = [fwd.fc1.weight, fwd.fc1.bias, fwd.fc2.weight, fwd.fc2.bias] + [q for l in lin for q in (l.weight, l.bias)]
                 key = tuple((p.data_ptr(), p._version) for p in params)
                 pk = self._packed
+                z = lambda shape, d: torch.zeros(shape, dtype=d, device=dev)   # noqa: E731
                 if pk is None or pk["dev"] != dev or pk["dt"] != dt:
-                    z = lambda shape, d: torch.zeros(shape, dtype=d, device=dev)   # noqa: E731
                     pk = dict(dev=dev, dt=dt, key=None, w1=z((HIDDEN_PAD, K), dt), w1_act=z((N, HIDDEN_PAD), torch.float32), b1=z((HIDDEN_PAD,), torch.float32),
                               w2=z((K, HIDDEN_PAD), dt), b2=z((K,), torch.float32), inv_w=z((MAX_ROWS, 2 * K), dt), inv_b=z((MAX_ROWS,), torch.float32))
                     c = _capi.Icm()
@@ -277,7 +293,13 @@ def _classes():
                     c.inv_w, c.inv_b = pk["inv_w"].data_ptr(), pk["inv_b"].data_ptr()
                     pk["struct"] = c
                     self._packed = pk
-                if pk["key"] != key:
+                fresh = backward and "struct_t" not in pk
+                if fresh:
+                    pk.update(w2_t=z((HIDDEN_PAD, K), dt), w1_t=z((K, HIDDEN_PAD), dt), inv_w_t=z((2 * K, MAX_ROWS), dt))
+                    c = _capi.IcmBwd()
+                    c.fwd_w2_t, c.fwd_w1_t, c.inv_w_t = (pk[k].data_ptr() for k in ("w2_t", "w1_t", "inv_w_t"))
+                    pk["struct_t"] = c
+                if pk["key"] != key or fresh:
                     with torch.no_grad():
                         w1 = fwd.fc1.weight.detach()
                         pk["w1"][:HIDDEN].copy_(w1[:, :K])
@@ -287,13 +309,17 @@ def _classes():
                         pk["b2"].copy_(fwd.fc2.bias.detach())
                         pk["inv_w"][:N].copy_(torch.cat([l.weight.detach() for l in lin], dim=0))
                         pk["inv_b"][:N].copy_(torch.cat([l.bias.detach() for l in lin], dim=0))
+                        if "struct_t" in pk:
+                            pk["w2_t"].copy_(pk["w2"].t())
+                            pk["w1_t"].copy_(pk["w1"].t())
+                            pk["inv_w_t"].copy_(pk["inv_w"].t())
                     pk["key"] = key
                 return pk
 
-            def _fused(self, features, actions, agent_finished, want_losses):
+            def _fused(self, features, actions, agent_finished, want_losses, backward=False):
                 T, P, K = features.shape[0] - 1, features.shape[1], features.shape[2]
                 G, dev = len(self.groups), features.device
-                pk = self._weights(dev)
+                pk = self._weights(dev, backward)
                 curiosity = torch.empty((T, P), dtype=torch.float32, device=dev)
                 ce = torch.empty((T, G, P), dtype=torch.float32, device=dev)
                 losses = torch.empty((3,), dtype=torch.float32, device=dev) if want_losses else None
@@ -307,6 +333,65 @@ def _classes():
                                                       stream), "dynenv_icm_losses")
                 return curiosity, ce, losses
 
+            # ---- the fused backward
+            def _no_fused_backward(self, features, actions, agent_finished):
+                """why dynenv_icm_backward does not take this call, or None"""
+                why = self._not_fusable(features, actions, agent_finished)
+                if why is None and self.feature_size not in FUSED_BACKWARD_K:
+                    why = "K = %d: the fused backward takes 64 or 128" % self.feature_size
+                return why
+
+            def _backward_buffers(self, dev, P):
+                """the seven gradients in the packed layouts and the workspace: the module's, at fixed addresses (the workspace
+                grows with P up to its bound, dynenv.h)"""
+                K, N = self.feature_size, sum(self.groups)
+                need = C.c_uint64(0)
+                _capi.check(_capi.load().dynenv_icm_backward_workspace(P, K, C.byref(need)), "dynenv_icm_backward_workspace")
+                b = self._bwd
+                if b is None or b["dev"] != dev:
+                    e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+                    b = dict(dev=dev, w1=e(HIDDEN_PAD, K), act=e(N, HIDDEN_PAD), b1=e(HIDDEN_PAD), w2=e(K, HIDDEN_PAD), b2=e(K), inv_w=e(MAX_ROWS, 2 * K),
+                             inv_b=e(MAX_ROWS), ws=None)
+                    c = _capi.IcmGrad()
+                    c.d_fwd_w1, c.d_fwd_w1_act, c.d_fwd_b1, c.d_fwd_w2, c.d_fwd_b2 = (b[k].data_ptr() for k in ("w1", "act", "b1", "w2", "b2"))
+                    c.d_inv_w, c.d_inv_b = b["inv_w"].data_ptr(), b["inv_b"].data_ptr()
+                    b["struct"] = c
+                    self._bwd = b
+                if b["ws"] is None or b["ws"].numel() < need.value:
+                    b["ws"] = torch.empty((need.value,), dtype=torch.uint8, device=dev)
+                return b
+
+            def _fused_backward(self, features, actions, agent_finished, losses, upstream, want_features, wanted):
+                """one call of dynenv_icm_backward -> (d_features or None, the gradients of _params() where `wanted`, else None)"""
+                T, P, K = features.shape[0] - 1, features.shape[1], features.shape[2]
+                G, dev, pk = len(self.groups), features.device, self._packed
+                b = self._backward_buffers(dev, P)
+                d_features = torch.empty_like(features) if want_features else None
+                nvec = (C.c_int32 * G)(*self.groups)
+                lib, p = _capi.load(), _capi.ptr
+                with torch.cuda.device(dev):
+                    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                    _capi.check(lib.dynenv_icm_backward(p(features), p(actions), p(agent_finished), T, P, K, actions.shape[1], nvec, G,
+                                                        _capi.ARR_BF16 if self.w_dtype == torch.bfloat16 else _capi.ARR_F16, C.byref(pk["struct"]),
+                                                        float(self.pred_net.fwd_net.relu.negative_slope), p(losses), p(upstream), C.byref(pk["struct_t"]),
+                                                        C.byref(b["struct"]), p(d_features), p(b["ws"]), b["ws"].numel(), p(self.status), stream),
+                                "dynenv_icm_backward")
+                starts, sizes = [sum(self.groups[:g]) for g in range(G)], self.groups   # (host ints: nothing is read from the device)
+                out =[torch.cat((b["w1"][:HIDDEN, :K], b["act"][:, :HIDDEN].t()), dim=1), b["b1"][:HIDDEN].clone(), b["w2"][:, :HIDDEN].clone(), b["b2"].clone()]
+                for s0, n in zip(starts, sizes):
+                    out += [b["inv_w"][s0:s0 + n].clone(), b["inv_b"][s0:s0 + n].clone()]
+                return d_features, [g if w else None for g, w in zip(out, wanted)]
+
+            def _forward_fused_backward(self, features, actions, agent_finished, long_horizon):
+                losses = _function().apply(self, features, actions, agent_finished, *self._params())
+                fwd, inv = self.forward_coeff * losses[0], self.icm_beta * losses[1]
+                with torch.no_grad():
+                    if long_horizon:
+                        lh = self._long_horizon(features.detach(), self._one_hot(self._indices(actions), features.dtype), losses[2] > 0)
+                    else:
+                        lh = torch.zeros((), dtype=torch.float32, device=features.device)
+                return ICMLosses(inv + fwd, inv, fwd, lh)
+
             def _check(self, features, actions, agent_finished):
                 G, K = len(self.groups), self.feature_size
                 assert features.dim() == 3 and features.shape[0] >= 2 and features.shape[2] == K, "features is [T + 1, P, %d]" % K
@@ -319,6 +404,12 @@ def _classes():
                 self._check(features, actions, agent_finished)
                 if torch.is_grad_enabled() and (features.requires_grad or any(p.requires_grad for p in self.parameters())):
                     self._route = "torch"
+                    if self.fused_backward:
+                        why = self._no_fused_backward(features, actions, agent_finished)
+                        if why is None:
+                            self._route = "fused (backward)"
+                            return self._forward_fused_backward(features, actions, agent_finished, long_horizon)
+                        self._route = "torch (fallback: %s)" % why
                     return self._forward_torch(features, actions, agent_finished, long_horizon)
                 with torch.no_grad():
                     why = self._not_fusable(features, actions, agent_finished)
@@ -346,6 +437,32 @@ def _classes():
                     self._route = "torch (fallback: %s)" % why
                     se, ce, _ = self._rows_torch(features, self._indices(actions))
                     return se.mean(-1).float(), torch.stack(ce, dim=1).float()
+
+        def _function():
+            if "fn" not in _lazy:
+                class IcmLossesFunction(torch.autograd.Function):
+                    """losses [3] = { forward_mean, inverse_mean, n } by dynenv_icm_losses; the gradient by dynenv_icm_backward.  Saved: the
+                    inputs and `losses`, nothing else.  The upstream gradient [3] arrives as a device tensor and goes to the kernel as it is:
+                    its elements 0 and 1 are s_f and s_i."""
+
+                    @staticmethod
+                    def forward(ctx, module, features, actions, agent_finished, *params):
+                        with torch.no_grad():
+                            _, _, losses = module._fused(features.detach(), actions, agent_finished, True, backward=True)
+                        ctx.module = module
+                        ctx.save_for_backward(features, actions, agent_finished, losses)
+                        return losses
+
+                    @staticmethod
+                    @torch.autograd.function.once_differentiable
+                    def backward(ctx, grad):
+                        features, actions, agent_finished, losses = ctx.saved_tensors
+                        need = ctx.needs_input_grad
+                        upstream = grad.to(torch.float32).contiguous()
+                        d_features, grads = ctx.module._fused_backward(features.detach(), actions, agent_finished, losses, upstream, need[1], need[4:])
+                        return (None, d_features, None, None) + tuple(grads)
+                _lazy["fn"] = IcmLossesFunction
+            return _lazy["fn"]
 
         for cls in (ForwardNet, AttentionNet, ICMDynamics, LongHorizonCuriosityLoss, LongHorizonForwardNet, GpuICM):
             cls.__qualname__ = cls.__name__

@@ -836,6 +836,72 @@ int dynenv_icm_losses(const float* features_dev, const float* actions_dev, const
                       int32_t action_cols, const int32_t* nvec, int32_t G, int32_t w_dtype, const dynenv_icm_t* w, float slope,
                       float* curiosity_dev, float* inverse_ce_dev, float* losses_dev, int32_t* status_dev, void* stream);
 
+/* ---- the backward of those two losses: the gradients of forward_mean and inverse_mean (losses_dev[0] and [1] above; ICMNet._calc_loss,
+ * icm.py:77-109, through ICMDynamics.forward, icm.py:207-240) with respect to the seven packed operands of dynenv_icm_t and to the
+ * features.  The forward saves NOTHING for it: the backward recomputes the hidden layer, the prediction and the logits per row from
+ * the features, and neither they, the one-hot, the two cats nor a gradient of any of them exists in memory.
+ * dynenv_icm_bwd_t: a second HOST struct of device pointers, the transposed copies in w_dtype that the three transposed products read
+ * (an operand of the matrix units is contiguous along the contraction); the caller keeps them in step with dynenv_icm_t. */
+typedef struct dynenv_icm_bwd {
+  const void *fwd_w2_t; /* [160][K] fwd_w2 transposed, rows from 140 on +0: dh = W2^T e contracts over the K outputs (16-bit type) */
+  const void *fwd_w1_t; /* [K][160] fwd_w1 transposed, columns from 140 on +0: dfeatures[t] takes W1[:, :K]^T dh, contracted over the hidden units (16-bit type) */
+  const void *inv_w_t;  /* [2K][32] inv_w transposed, columns from N on +0: rows 0..K-1 give dfeatures[t], rows K..2K-1 dfeatures[t+1], contracted over the logits (16-bit type) */
+} dynenv_icm_bwd_t;
+/* dynenv_icm_grad_t: a HOST struct of float32 device pointers, the outputs, in the layouts of the forward's packed operands. */
+typedef struct dynenv_icm_grad {
+  float *d_fwd_w1;     /* [160][K]; rows from 140 on +0 */
+  float *d_fwd_w1_act; /* [N][160]; columns from 140 on +0 */
+  float *d_fwd_b1;     /* [160]; +0 from 140 on */
+  float *d_fwd_w2;     /* [K][160]; columns from 140 on +0 */
+  float *d_fwd_b2;     /* [K] */
+  float *d_inv_w;      /* [32][2K]; rows from N on +0 */
+  float *d_inv_b;      /* [32]; +0 from N on */
+} dynenv_icm_grad_t;
+/* The most workgroups the row kernel runs: the grid is persistent and capped, a workgroup keeps its partial weight gradients in
+ * registers across the blocks of 32 players it walks and writes ONE slice of the workspace. */
+#define DYNENV_ICM_BWD_MAX_WORKGROUPS 256
+/* dynenv_icm_backward_workspace: host only, touches no device.  *bytes = min(ceil(P / 32), 256) * (385 K + 5312) * 4: at most
+ * 256 * (385 K + 5312) * 4 bytes whatever P and T are - 30 670 848 at K = 64 and 55 902 208 at K = 128.  DYNENV_ERR_ARG: bytes NULL,
+ * P or K < 1; DYNENV_ERR_UNSUPPORTED: a K other than 64 or 128. */
+int dynenv_icm_backward_workspace(int32_t P, int32_t K, uint64_t* bytes);
+/* dynenv_icm_backward, two launches, capturable (launches and nothing else: nothing is synchronised, allocated or copied; pointers and
+ * sizes are frozen by a capture, contents are read at replay).  features_dev .. slope are dynenv_icm_losses' arguments, unchanged, and w
+ * is the forward's struct.  count_dev is the forward's losses_dev: n is read from its element 2 on the device.  upstream_dev float32
+ * [2] = { s_f, s_i } = { dL/dforward_mean, dL/dinverse_mean } on the device.  With alpha = 2 s_f / (n K), beta = s_i / (n G), per
+ * ACTIVE row (t, p) (finished[t][p] == 0), in the notation of dynenv_icm_losses, f = features[t][p], f' = features[t+1][p],
+ * e = pred - f':
+ *   dh = (W2^T e) * leaky'(h_pre), leaky' = 1 where h_pre > 0 and slope elsewhere (h_pre == 0 included: torch's LeakyReLU backward)
+ *   q  = cat_g(softmax(l_g) - onehot(a_g)), exactly 0 for a group of one action
+ *   d_fwd_w2 = alpha sum e h^T,  d_fwd_b2 = alpha sum e,  d_fwd_w1 = alpha sum dh f^T,  d_fwd_b1 = alpha sum dh,
+ *   d_fwd_w1_act[start_g + a_g] += alpha dh for every g,  d_inv_w = beta sum q cat(f, f')^T,  d_inv_b = beta sum q
+ *   d_features[t][p] += alpha W1[:, :K]^T dh + beta W_inv[:, :K]^T q;   d_features[t+1][p] += -alpha e + beta W_inv[:, K:]^T q
+ * the sums over the active rows only; an inactive row contributes nothing; with n == 0 every gradient is +0.
+ * Outputs: EVERY element of the seven buffers of grad is written exactly once per call and nothing is accumulated into; the padding
+ * is zero.  d_features_dev float32 [T+1][P][K], or NULL where the features want no gradient (the seven are then the same bits): every
+ * element is written exactly once, a (t, p) that no active row touches is +0.  A clamped action ORs bit 0 into status_dev[0] (or NULL)
+ * and takes the nearest action's gradients.
+ * workspace_dev: workspace_bytes >= what dynenv_icm_backward_workspace(P, K) gives, 16-byte aligned, contents irrelevant before and
+ * after the call.
+ * Arithmetic: the three recomputed products, the three transposed ones and the four weight-gradient products (the scatter-add into
+ * d_fwd_w1_act is the product onehot^T dh) take 16-bit operands of w_dtype on the matrix units and accumulate in float32; biases, the
+ * gather, the LeakyReLU and its derivative, the softmax, e, the bias gradients and -alpha e are float32.  NO quantity that carries
+ * 1 / n, s_f or s_i is ever rounded to 16 bits: the products run on the unscaled e, dh and q, and alpha and beta are applied in float32
+ * behind them - scaling upstream by a power of two scales every output by it exactly.  Every sum has one fixed order and there is no
+ * floating-point atomic: the same call twice gives the same bits.  A row of d_features depends on that player's features and
+ * actions, the weights, n and upstream alone - not on P, on its place in the launch or on its neighbours.  The weight gradients are
+ * added per workgroup, then over the workgroups' slices in workgroup order by the second launch: their summation order depends on P
+ * (through the grid) and on nothing else.  Inputs that are not finite are outside the contract.
+ * Errors, DYNENV_ERR_ARG, all reported before a device is looked for: a NULL features_dev, actions_dev, nvec, w, count_dev,
+ * upstream_dev, wt, grad or workspace_dev, or one of the 7 + 3 + 7 pointers in the structs; T, P or K < 1; G outside 1..8, an n_g
+ * outside 1..16, N > 32, AD outside G..8; a dtype outside 0..2; a buffer not 16-byte aligned (count_dev, upstream_dev, status_dev:
+ * 4-byte); (T + 1) * P > 2^30; a workspace that is too small.  Then what the kernel does not take: DYNENV_ARR_F32, a K other than 64
+ * or 128 (at K = 256 the weight gradients' accumulators, 384 float32 per lane, do not fit the register file beside the working set):
+ * DYNENV_ERR_UNSUPPORTED, also before the device. */
+int dynenv_icm_backward(const float* features_dev, const float* actions_dev, const uint8_t* finished_dev, int32_t T, int32_t P, int32_t K,
+                        int32_t action_cols, const int32_t* nvec, int32_t G, int32_t w_dtype, const dynenv_icm_t* w, float slope,
+                        const float* count_dev, const float* upstream_dev, const dynenv_icm_bwd_t* wt, const dynenv_icm_grad_t* grad,
+                        float* d_features_dev, void* workspace_dev, uint64_t workspace_bytes, int32_t* status_dev, void* stream);
+
 
 /* Device self-test of the deterministic math header: evaluates sincos/atan2/sqrt/div on n host-provided doubles and
  * returns the raw results so tests can compare them bit-for-bit with the host evaluation. out: [n,5]. */
