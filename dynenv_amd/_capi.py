@@ -105,6 +105,15 @@ class Policy(C.Structure):  # dynenv_policy_t: device pointers of the policy hea
                                           "critic_w2", "critic_b2")]
 
 
+class PolicyBwd(C.Structure):  # dynenv_policy_bwd_t: the transposed bf16 copies the products of dynenv_policy_eval_backward read
+    _fields_ = [(n, C.c_void_p) for n in ("actor_w_t", "critic_w1_t", "actor_w_t_lo", "critic_w1_t_lo")]
+
+
+class PolicyGrad(C.Structure):  # dynenv_policy_grad_t: float32 device pointers of the eight gradients, in the packed operands' layouts
+    _fields_ = [(n, C.c_void_p) for n in ("d_actor_w", "d_actor_b", "d_critic_w1", "d_critic_b1", "d_critic_ln_w", "d_critic_ln_b", "d_critic_w2",
+                                          "d_critic_b2")]
+
+
 class IcmBwd(C.Structure):  # dynenv_icm_bwd_t: the transposed 16-bit copies the backward's products read
     _fields_ = [(n, C.c_void_p) for n in ("fwd_w2_t", "fwd_w1_t", "inv_w_t")]
 
@@ -190,6 +199,10 @@ SIGNATURES = {
     "dynenv_icm_backward_workspace": (C.c_int, [i32, i32, C.POINTER(C.c_uint64)]),
     "dynenv_icm_backward": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), i32, i32, C.POINTER(Icm), C.c_float, vp, vp, C.POINTER(IcmBwd),
                                       C.POINTER(IcmGrad), vp, vp, C.c_uint64, vp, vp]),
+    "dynenv_policy_eval": (C.c_int, [vp, vp, i32, i32, i32, i32, C.POINTER(Policy), C.POINTER(i32), i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+    "dynenv_policy_eval_backward_workspace": (C.c_int, [i32, i32, C.POINTER(C.c_uint64)]),
+    "dynenv_policy_eval_backward": (C.c_int, [vp, vp, i32, i32, i32, i32, C.POINTER(Policy), C.POINTER(i32), i32, i32, C.c_float, C.c_float, vp, vp, vp,
+                                              C.POINTER(PolicyBwd), C.POINTER(PolicyGrad), vp, vp, C.c_uint64, vp, vp]),
     "dynenv_recurrent_head": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.POINTER(Rhead), C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
     "dynenv_policy_head": (C.c_int, [vp, vp, i32, i32, i32, i32, C.POINTER(Policy), C.POINTER(i32), i32, i32, i32, C.c_uint64, vp, C.c_uint64,
                                      C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]),

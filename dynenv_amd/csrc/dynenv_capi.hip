@@ -737,5 +737,6 @@ int dynenv_math_probe(int32_t unit, const double* in_host, int32_t n, double* ou
 #include "rollout_kernels.hip"          /* (with its entry points: dynenv_rollout_insert, dynenv_rollout_returns) */
 #include "icm_kernels.hip"              /* (with its entry point: dynenv_icm_losses) */
 #include "icm_backward_kernels.hip"     /* (with its entry points: dynenv_icm_backward, dynenv_icm_backward_workspace) */
+#include "policy_eval_kernels.hip"      /* (with its entry points: dynenv_policy_eval, dynenv_policy_eval_backward, dynenv_policy_eval_backward_workspace) */
 // this unit's math probe: every routine of include/dynenv_math.h as compiled here (-O3), the row of include/dynenv_math_probe.h
 extern "C" __global__ void __launch_bounds__(64) rc_math_probe_kernel(const double* in, int n, double* out) { dm_probe_wave(in, n, out); }

@@ -50,19 +50,29 @@ struct PhArgs {   // dynenv_policy_t by value, the outputs and the sizes
   int* actions;
   double* cont;
   float *probs, *logp, *value, *next_ext;
+  // dynenv_policy_eval (policy_eval_kernels.hip): the stored actions [T][AD][ev_P] stand where the draw stood, P = T * ev_P rows
+  const float* ev_actions;
+  int ev_P;
+  int* status;
 };
 
-template <int K, class CV>
-__device__ __forceinline__ void ph_body(const PhArgs& a) {
-  constexpr int H = K / 2, CT = H / 16, T = CT + 2, TPW = (T + PH_WAVES - 1) / PH_WAVES, KS = K / 32;   // critic tiles, all tiles, tiles per wave, k steps
-  constexpr int XS = K + 8;                                                                              // elements per LDS row: 16 bytes of padding
-  __shared__ __attribute__((aligned(16))) atp_h xb[PH_ROWS * XS];
-  __shared__ float lg[PH_ROWS * PH_LS];
-  __shared__ float part[3 * PH_WAVES * PH_ROWS];
-  __shared__ int acts[PH_ROWS * 8];
+#define PH_TS (PH_ROWS + 8)   // elements per LDS row of the transposed copy of the 64 rows: 16 bytes of padding
+template <int K> struct PhShape {   // critic tiles, all tiles, tiles per wave, k steps; elements per LDS row: 16 bytes of padding
+  static constexpr int H = K / 2, CT = H / 16, T = CT + 2, TPW = (T + PH_WAVES - 1) / PH_WAVES, KS = K / 32, XS = K + 8;
+};
 
+// Phases 0 and 1 of the rows row0 .. row0 + 63: what dynenv_policy_head, dynenv_policy_eval and the recomputation of
+// dynenv_policy_eval_backward share, so that the three give a row the same bits.  Leaves the logits in lg, the critic's hidden layer
+// behind its LeakyReLU in y (the tiles wave + 4 t below CT), its LayerNorm's mean and 1 / std per strip, and the four waves' parts of
+// every row's dot product with Layer2.weight in part + 2 * PH_WAVES * PH_ROWS, behind a barrier.  With TR the rows also go into xt,
+// transposed and rounded to bf16 (the operand of the weight gradients; xtl, unless NULL, takes the bf16 rounding of what that rounding
+// left), and bit 4 (t PH_STRIPS + s) + i of pos says h_pre > 0.
+template <int K, class CV, bool TR>
+__device__ __forceinline__ void ph_forward(const PhArgs& a, int row0, atp_h* xb, atp_h* xt, atp_h* xtl, float* lg, float* part,
+                                           atp_f4 (&y)[PhShape<K>::TPW][PH_STRIPS], float (&mean)[PH_STRIPS], float (&rstd)[PH_STRIPS], unsigned& pos) {
+  constexpr int H = PhShape<K>::H, CT = PhShape<K>::CT, T = PhShape<K>::T, TPW = PhShape<K>::TPW, KS = PhShape<K>::KS, XS = PhShape<K>::XS;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lq = lane >> 4;
-  const int row0 = (int)blockIdx.x * PH_ROWS, P = a.P;
+  const int P = a.P;
   const int F = a.feat1 ? H : K;
   const atp_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
@@ -72,11 +82,21 @@ __device__ __forceinline__ void ph_body(const PhArgs& a) {
     atp_f4 v = zero4;
     if (p < P) v = col < F ? rh_ldf4(a.feat0 + (size_t)p * F + col) : rh_ldf4(a.feat1 + (size_t)p * F + (col - F));
     atp_st4<CV>(xb + r * XS + col, v);
+    if constexpr (TR) {
+      const unsigned lo = ArrBf16::pack(v.x, v.y), hi = ArrBf16::pack(v.z, v.w);
+      atp_h* t = xt + col * PH_TS + r;
+      t[0] = (atp_h)(lo & 0xffffu); t[PH_TS] = (atp_h)(lo >> 16); t[2 * PH_TS] = (atp_h)(hi & 0xffffu); t[3 * PH_TS] = (atp_h)(hi >> 16);
+      if (xtl) {   // what the rounding to bf16 left, rounded to bf16: xt + xtl holds 16 significant bits of the row
+        const arr_f2 w0 = ArrBf16::widen(lo), w1 = ArrBf16::widen(hi);
+        const unsigned l0 = ArrBf16::pack(v.x - w0.x, v.y - w0.y), l1 = ArrBf16::pack(v.z - w1.x, v.w - w1.y);
+        atp_h* u = xtl + col * PH_TS + r;
+        u[0] = (atp_h)(l0 & 0xffffu); u[PH_TS] = (atp_h)(l0 >> 16); u[2 * PH_TS] = (atp_h)(l1 & 0xffffu); u[3 * PH_TS] = (atp_h)(l1 >> 16);
+      }
+    }
   }
   __syncthreads();
 
   // ---- phase 1: this wave's tiles for all 64 rows
-  atp_f4 y[TPW][PH_STRIPS];
   const atp_h* wrow[TPW];
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
@@ -114,6 +134,8 @@ __device__ __forceinline__ void ph_body(const PhArgs& a) {
 #pragma unroll
       for (int s = 0; s < PH_STRIPS; ++s) {
         atp_f4& v = y[t][s];
+        if constexpr (TR)
+          pos |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u)) << (4 * (t * PH_STRIPS + s));
         v.x = v.x > 0.f ? v.x : v.x * a.slope; v.y = v.y > 0.f ? v.y : v.y * a.slope;
         v.z = v.z > 0.f ? v.z : v.z * a.slope; v.w = v.w > 0.f ? v.w : v.w * a.slope;
       }
@@ -127,7 +149,6 @@ __device__ __forceinline__ void ph_body(const PhArgs& a) {
   }
   // torch's LayerNorm (biased variance, two passes) over the H critic features of a row, which lie in up to four waves, and the dot
   // product with Layer2.weight: a wave without a critic tile adds +0
-  float mean[PH_STRIPS], rstd[PH_STRIPS];
 #pragma unroll
   for (int s = 0; s < PH_STRIPS; ++s) {
     float v = 0.f;
@@ -178,8 +199,54 @@ __device__ __forceinline__ void ph_body(const PhArgs& a) {
     }
   }
   __syncthreads();   // (the actor's outputs in lg are complete too)
+}
+
+// softmax of the n logits at L[off ..], in place -> c_{n-1}: the probabilities added left to right
+__device__ __forceinline__ float ph_softmax(float* L, int off, int n) {
+  float m = L[off];
+  for (int j = 1; j < n; ++j) m = fmaxf(m, L[off + j]);
+  float sum = 0.f;
+  for (int j = 0; j < n; ++j) {
+    const float e = expf(L[off + j] - m);
+    L[off + j] = e;
+    sum += e;
+  }
+  float last = 0.f;
+  for (int j = 0; j < n; ++j) {
+    const float pj = L[off + j] / sum;
+    L[off + j] = pj;
+    last += pj;
+  }
+  return last;
+}
+
+// a stored action of group g (n_g - 1 = last) for row p = t ev_P + pp: rounded to the nearest integer and clamped into the group
+__device__ __forceinline__ int ph_stored_action(const PhArgs& a, int p, int g, int last, bool& clamped) {
+  const int t = p / a.ev_P, pp = p - t * a.ev_P;
+  const float v = rintf(a.ev_actions[((size_t)t * a.AD + g) * a.ev_P + pp]);
+  const bool ok = v >= 0.f && v <= (float)last;
+  clamped |= !ok;
+  return ok ? (int)v : v > (float)last ? last : 0;
+}
+
+// EVAL: dynenv_policy_eval - the stored action in place of the draw, log_probs in the storage's layout [T][G][ev_P], probs optional,
+// no actions, cont or next_ext.
+template <int K, class CV, bool EVAL>
+__device__ __forceinline__ void ph_body(const PhArgs& a) {
+  constexpr int TPW = PhShape<K>::TPW, XS = PhShape<K>::XS;
+  __shared__ __attribute__((aligned(16))) atp_h xb[PH_ROWS * XS];
+  __shared__ float lg[PH_ROWS * PH_LS];
+  __shared__ float part[3 * PH_WAVES * PH_ROWS];
+  __shared__ int acts[PH_ROWS * 8];
+
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = (int)blockIdx.x * PH_ROWS, P = a.P;
+  atp_f4 y[TPW][PH_STRIPS];
+  float mean[PH_STRIPS], rstd[PH_STRIPS];
+  unsigned pos = 0;
+  ph_forward<K, CV, false>(a, row0, xb, nullptr, nullptr, lg, part, y, mean, rstd, pos);
   if (tid < PH_ROWS && row0 + tid < P) {
-    const float* q = part3 + tid;
+    const float* q = part + 2 * PH_WAVES * PH_ROWS + tid;
     a.value[row0 + tid] = (((q[0] + q[PH_ROWS]) + q[2 * PH_ROWS]) + q[3 * PH_ROWS]) + a.b2[0];
   }
 
@@ -187,42 +254,40 @@ __device__ __forceinline__ void ph_body(const PhArgs& a) {
   {
     const int r = lane, q = wave, p = row0 + r;
     float* L = lg + r * PH_LS;
-    const unsigned long long draw = a.draw ? a.draw[0] : 0ull, row = a.row_base + (unsigned long long)p;
+    const unsigned long long draw = !EVAL && a.draw ? a.draw[0] : 0ull, row = a.row_base + (unsigned long long)p;
+    bool clamped = false;
     for (int g = q; g < a.G; g += PH_WAVES) {
       const int off = (int)((a.group_off >> (8 * g)) & 255u), n = (int)((a.group_n >> (4 * g)) & 15u) + 1;
-      float m = L[off];
-      for (int j = 1; j < n; ++j) m = fmaxf(m, L[off + j]);
-      float sum = 0.f;
-      for (int j = 0; j < n; ++j) {
-        const float e = expf(L[off + j] - m);
-        L[off + j] = e;
-        sum += e;
-      }
-      float last = 0.f;   // c_{n-1}
-      for (int j = 0; j < n; ++j) {
-        const float pj = L[off + j] / sum;
-        L[off + j] = pj;
-        last += pj;
-      }
-      const dm_u32x4 w = dm_philox((uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)row, (uint32_t)draw, (uint32_t)(draw >> 32),
-                                   DYNENV_POLICY_RNG_PURPOSE + (uint32_t)(g >> 2));
-      const uint32_t word = q == 0 ? w.v[0] : q == 1 ? w.v[1] : q == 2 ? w.v[2] : w.v[3];
-      const float u = (float)(word >> 8) * 5.9604644775390625e-08f;   // 2^-24: exact
-      const float t = u * last;
-      float c = 0.f;
+      const float last = ph_softmax(L, off, n);   // c_{n-1}
       int act = 0;
-      for (int j = 0; j + 1 < n; ++j) {
-        c += L[off + j];
-        act += c <= t ? 1 : 0;
+      if constexpr (EVAL) {
+        if (p < P) act = ph_stored_action(a, p, g, n - 1, clamped);
+      } else {
+        const dm_u32x4 w = dm_philox((uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)row, (uint32_t)draw, (uint32_t)(draw >> 32),
+                                     DYNENV_POLICY_RNG_PURPOSE + (uint32_t)(g >> 2));
+        const uint32_t word = q == 0 ? w.v[0] : q == 1 ? w.v[1] : q == 2 ? w.v[2] : w.v[3];
+        const float u = (float)(word >> 8) * 5.9604644775390625e-08f;   // 2^-24: exact
+        const float t = u * last;
+        float c = 0.f;
+        for (int j = 0; j + 1 < n; ++j) {
+          c += L[off + j];
+          act += c <= t ? 1 : 0;
+        }
+        acts[r * 8 + g] = act;
       }
-      acts[r * 8 + g] = act;
       if (p < P) {
         const float eps32 = 1.1920928955078125e-07f;
         const float pa = fminf(fmaxf(L[off + act], eps32), 1.0f - eps32);
-        a.logp[(size_t)p * a.G + g] = (float)log((double)pa);   // the float32 nearest to the logarithm: a host reproduces it bit for bit
+        size_t at = (size_t)p * a.G + g;
+        if constexpr (EVAL) {
+          const int t = p / a.ev_P;
+          at = ((size_t)t * a.G + g) * a.ev_P + (p - t * a.ev_P);
+        }
+        a.logp[at] = (float)log((double)pa);   // the float32 nearest to the logarithm: a host reproduces it bit for bit
       }
     }
-    if (q < a.C && p < P) {
+    if (EVAL && clamped && a.status) atomicOr(a.status, 1);
+    if (!EVAL && q < a.C && p < P) {
       const float v = (rh_sigmoid(L[a.N + q]) - 0.5f) * a.cont_scale[q] + a.cont_mean[q];
       a.cont[(size_t)p * a.C + q] = (double)v;
     }
@@ -231,7 +296,9 @@ __device__ __forceinline__ void ph_body(const PhArgs& a) {
 
   // ---- phase 3: the 64 rows' probs, actions and next_ext are contiguous in memory
   const int rows = min(PH_ROWS, P - row0);
-  for (int i = tid; i < rows * a.N; i += PH_BLOCK) a.probs[(size_t)row0 * a.N + i] = lg[(i / a.N) * PH_LS + i % a.N];
+  if (!EVAL || a.probs)
+    for (int i = tid; i < rows * a.N; i += PH_BLOCK) a.probs[(size_t)row0 * a.N + i] = lg[(i / a.N) * PH_LS + i % a.N];
+  if (EVAL) return;
   const int AD = a.AD;
   for (int i = tid; i < rows * AD; i += PH_BLOCK) {
     const int r = i / AD, k = i % AD;
@@ -254,7 +321,7 @@ __device__ __forceinline__ void ph_body(const PhArgs& a) {
 }
 
 #define PH_KERNEL(NAME, K, CV) \
-  extern "C" __global__ void __launch_bounds__(PH_BLOCK) NAME(PhArgs a) { ph_body<K, CV>(a); }
+  extern "C" __global__ void __launch_bounds__(PH_BLOCK) NAME(PhArgs a) { ph_body<K, CV, false>(a); }
 PH_KERNEL(ph_64_bf16_kernel, 64, ArrBf16)
 PH_KERNEL(ph_64_f16_kernel, 64, ArrF16)
 PH_KERNEL(ph_128_bf16_kernel, 128, ArrBf16)
@@ -307,6 +374,7 @@ extern "C" int dynenv_policy_head(const float* feat0_dev, const float* feat1_dev
   k.P = E * A; k.G = G; k.N = N; k.C = C; k.AD = action_cols; k.discrete_turn = discrete_turn != 0;
   k.slope = slope; k.eps = ln_eps;
   k.actions = actions_dev; k.cont = cont_dev; k.probs = probs_dev; k.logp = logp_dev; k.value = value_dev; k.next_ext = next_ext_dev;
+  k.ev_actions = nullptr; k.ev_P = 0; k.status = nullptr;
   static decltype(&ph_64_bf16_kernel) const kernels[3][2] = {{ph_64_bf16_kernel, ph_64_f16_kernel}, {ph_128_bf16_kernel, ph_128_f16_kernel},
                                                               {ph_256_bf16_kernel, ph_256_f16_kernel}};
   const int Kc = feat1_dev ? 2 * F : F;

@@ -13,7 +13,11 @@ M32 = 0xFFFFFFFF
 RNG_PURPOSE = 16   # DYNENV_POLICY_RNG_PURPOSE
 MAX_ROWS, MAX_GROUPS, MAX_GROUP, MAX_CONT, MAX_COLS = 32, 8, 16, 4, 8   # the kernel's limits (include/dynenv.h)
 
+EVAL_K = (64, 128)                            # what dynenv_policy_eval and its backward take
+EVAL_ROWS, EVAL_MAX_WORKGROUPS = 64, 256     # DYNENV_POLICY_EVAL_ROWS, DYNENV_POLICY_EVAL_MAX_WORKGROUPS: the backward's blocks and its grid's cap
+
 PolicyAct = collections.namedtuple("PolicyAct", ["actions", "head", "log_probs", "probs", "value", "next_ext"])
+PolicyEval = collections.namedtuple("PolicyEval", ["log_probs", "probs", "values"])
 
 
 def transform_actions(actions, discrete_turn=False):
@@ -178,9 +182,26 @@ def _classes():
               "torch (fallback: ...)"  where no gradient is wanted but the kernel does not take the call - DYNENV_POLICY_FUSED=0 in
                        the environment among the reasons.  Nothing is raised.
             The routes differ only by the rounding of the probabilities (16-bit operands on the matrix units, float32 accumulation,
-            against float32 throughout)."""
+            against float32 throughout).
 
-            def __init__(self, feature_size, action_space, operand_dtype=torch.bfloat16, seed=0, device=None, discrete_turn=False):
+            evaluate(features, actions, want_probs=True) -> PolicyEval(log_probs [T, G, P], probs [T, P, N], values [T, P]) over a STORED
+            rollout: features float32 [T, P, K] (storage.features[:-1]), actions float32 [T, AD, P] (storage.actions), the outputs in
+            the storage's layouts - what GpuRolloutStorage.a2c_loss(evaluation=...) takes, so that a rollout collected by a replayed
+            graph (which carries no history) trains the actor and the critic.  Per row the statement is act()'s with the stored action
+            in place of the draw (include/dynenv.h, dynenv_policy_eval); an action outside its group is clamped to the nearest one and
+            ORs bit 0 into `eval_status` (int32 [1], the module's; GpuICM's convention).  Only the discrete groups are evaluated: a
+            head with a Box block takes the torch route and the Box block's parameters receive no gradient (the reference's loss gives
+            them none either: its softmax over one output is the constant 1).  want_probs=False leaves probs None - a loss that takes
+            its action_probs from elsewhere does not pay for [T, P, N] twice.  `last_eval_route` names the route the latest call took:
+              "torch"  a gradient is wanted (the default then): torch operations, float32 throughout, differentiable.
+              "fused"  no gradient is wanted and the kernel takes the call: one launch of dynenv_policy_eval - dynenv_policy_head's
+                       device function, so for the actions act() drew from the same rows and weights the bits are act()'s.
+              "fused (backward)"  fused_backward=True and a gradient wanted: the fused forward behind a torch.autograd.Function;
+                       loss.backward() is ONE call of dynenv_policy_eval_backward (csrc/policy_eval_kernels.hip), which recomputes the
+                       forward per row: nothing is saved but the inputs.  K of 64 or 128.
+              "torch (fallback: why)"  otherwise - DYNENV_POLICY_FUSED=0, another K and a Box block among the reasons.  Nothing is raised."""
+
+            def __init__(self, feature_size, action_space, operand_dtype=torch.bfloat16, seed=0, device=None, discrete_turn=False, fused_backward=False):
                 super().__init__()
                 self.feature_size = int(feature_size)
                 self.operand_dtype = operand_dtype
@@ -197,11 +218,19 @@ def _classes():
                 self.action_cols = len(self.nvec) + self.n_cont
                 self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
                 self.register_buffer("_draw", torch.zeros(1, dtype=torch.int64, device=device), persistent=False)
-                self._route = None
+                self.register_buffer("eval_status", torch.zeros(1, dtype=torch.int32, device=device), persistent=False)
+                self.register_buffer("_last", torch.tensor(self.nvec, dtype=torch.int64, device=device) - 1, persistent=False)
+                self.fused_backward = bool(fused_backward)
+                self._route = self._eval_route = None
+                self._packed = self._bwd = None
 
             @property
             def last_route(self):
                 return self._route
+
+            @property
+            def last_eval_route(self):
+                return self._eval_route
 
             def reseed(self, seed, draw=0):
                 self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -323,6 +352,211 @@ def _classes():
                                                        _capi.ptr(next_ext), stream), "dynenv_policy_head")
                 head = None if cont is None else (cont.view(P) if NC == 1 else cont)
                 return PolicyAct(actions, head, logp, list(torch.split(probs, self.nvec, dim=1)), value, next_ext)
+
+            # ---- evaluate: the head over a stored rollout
+            def _eval_indices(self, actions):
+                """actions [T, AD, P] -> int64 [T, G, P] inside the groups; a value that had to be clamped sets the status bit"""
+                G = len(self.nvec)
+                with torch.no_grad():
+                    v = actions[:, :G].detach().round()
+                    last = self._last.to(v.dtype).view(1, G, 1)
+                    ok = (v >= 0) & (v <= last)
+                    idx = torch.where(ok, v, torch.where(v > last, last, torch.zeros_like(v))).long()
+                    self.eval_status.bitwise_or_((~ok).any().to(torch.int32))
+                return idx
+
+            def _eval_torch(self, features, actions, want_probs):
+                G = len(self.nvec)
+                idx = self._eval_indices(actions)
+                policies, value = self.forward(features)
+                wide = lambda x: x.float() if x.dtype in (torch.bfloat16, torch.float16) else x   # noqa: E731
+                probs = [torch.softmax(wide(l), dim=-1) for l in policies[:G]]
+                logp = []
+                eps = torch.finfo(torch.float32).eps   # (float32's in every type: the statement of dynenv_policy_eval)
+                for g, p in enumerate(probs):   # Categorical(probs).log_prob: the clamp of probs_to_logits
+                    logp.append(torch.log(p.gather(2, idx[:, g].unsqueeze(-1)).squeeze(-1).clamp(eps, 1 - eps)))
+                return PolicyEval(torch.stack(logp, dim=1), torch.cat(probs, dim=2) if want_probs else None, wide(value).squeeze(-1))
+
+            def _no_eval_fused(self, features, actions, backward):
+                """why dynenv_policy_eval (and, with `backward`, dynenv_policy_eval_backward) does not take this call, or None"""
+                K, G = self.feature_size, len(self.nvec)
+                if os.environ.get("DYNENV_POLICY_FUSED", "") == "0":
+                    return "DYNENV_POLICY_FUSED=0"
+                if self.n_cont:
+                    return "a Box block"
+                if K not in EVAL_K:
+                    return "K = %d, not 64 or 128" % K
+                if G > MAX_GROUPS or max(self.nvec) > MAX_GROUP or sum(self.nvec) > MAX_ROWS or actions.shape[1] > MAX_COLS:
+                    return "an action space beyond %d groups of %d, %d rows or %d columns" % (MAX_GROUPS, MAX_GROUP, MAX_ROWS, MAX_COLS)
+                if not features.is_cuda:
+                    return "features that are not on the device"
+                dev = features.device
+                for name, t in (("features", features), ("actions", actions)):
+                    if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.data_ptr() % 16:
+                        return "%s that is not float32, contiguous, 16-byte aligned and on %s" % (name, dev)
+                if features.shape[0] * features.shape[1] > 1 << 30:
+                    return "more than 2^30 rows"
+                for p in self._eval_params() + [self.eval_status]:
+                    if (p.dtype != torch.float32 and p is not self.eval_status) or p.device != dev:
+                        return "parameters that are not float32 and on %s" % (dev,)
+                return None
+
+            def _eval_params(self):
+                """the parameters of the discrete groups and of the critic in the order the fused backward returns their gradients"""
+                blk = self.critic.blocks
+                return [q for l in self._linears()[:len(self.nvec)] for q in (l.weight, l.bias)] + \
+                       [blk.Layer1.weight, blk.Layer1.bias, blk.bn.weight, blk.bn.bias, blk.Layer2.weight, blk.Layer2.bias]
+
+            def _eval_weights(self, dev, backward=False):
+                """the packed operands of dynenv_policy_t, made once per device and refreshed in place when a parameter changed; with
+                `backward` (and from then on) the transposed bf16 copies of dynenv_policy_bwd_t too, refreshed in the same pass"""
+                K, N, dt = self.feature_size, sum(self.nvec), self.operand_dtype
+                lin, blk = self._linears()[:len(self.nvec)], self.critic.blocks
+                params = self._eval_params()
+                key = tuple((p.data_ptr(), p._version) for p in params)
+                pk = self._packed
+                z = lambda shape, d: torch.zeros(shape, dtype=d, device=dev)   # noqa: E731
+                if pk is None or pk["dev"] != dev or pk["dt"] != dt:
+                    pk = dict(dev=dev, dt=dt, key=None, aw=z((MAX_ROWS, K), dt), ab=z((MAX_ROWS,), torch.float32), w1=z((K // 2, K), dt))
+                    self._packed = pk
+                fresh = backward and "aw_t" not in pk
+                if fresh:
+                    pk.update(aw_t=z((K, MAX_ROWS), torch.bfloat16), w1_t=z((K, K // 2), torch.bfloat16), aw_t_lo=z((K, MAX_ROWS), torch.bfloat16),
+                              w1_t_lo=z((K, K // 2), torch.bfloat16))   # (the second halves: read with float16 operands only)
+                    c = _capi.PolicyBwd()
+                    c.actor_w_t, c.critic_w1_t, c.actor_w_t_lo, c.critic_w1_t_lo = (pk[k].data_ptr() for k in ("aw_t", "w1_t", "aw_t_lo", "w1_t_lo"))
+                    pk["struct_t"] = c
+                if pk["key"] != key or fresh:
+                    with torch.no_grad():
+                        pk["aw"][:N].copy_(torch.cat([l.weight.detach() for l in lin], dim=0))
+                        pk["ab"][:N].copy_(torch.cat([l.bias.detach() for l in lin], dim=0))
+                        pk["w1"].copy_(blk.Layer1.weight.detach())
+                        if "aw_t" in pk:
+                            for name, w in (("aw_t", torch.cat([l.weight.detach() for l in lin], dim=0).t()), ("w1_t", blk.Layer1.weight.detach().t())):
+                                hi = pk[name][:, :w.shape[1]]
+                                hi.copy_(w)
+                                pk[name + "_lo"][:, :w.shape[1]].copy_(w - hi.float())
+                    pk["key"] = key
+                w = _capi.Policy()   # (the float32 operands are the parameters themselves: their pointers are read at every call)
+                w.actor_w, w.actor_b, w.critic_w1 = pk["aw"].data_ptr(), pk["ab"].data_ptr(), pk["w1"].data_ptr()
+                w.critic_b1, w.critic_ln_w, w.critic_ln_b = blk.Layer1.bias.data_ptr(), blk.bn.weight.data_ptr(), blk.bn.bias.data_ptr()
+                w.critic_w2, w.critic_b2 = blk.Layer2.weight.data_ptr(), blk.Layer2.bias.data_ptr()
+                pk["struct"] = w
+                return pk
+
+            def _eval_fused(self, features, actions, want_probs, backward=False):
+                T, P, K = features.shape
+                G, N, dev, blk = len(self.nvec), sum(self.nvec), features.device, self.critic.blocks
+                pk = self._eval_weights(dev, backward)
+                logp = torch.empty((T, G, P), dtype=torch.float32, device=dev)
+                probs = torch.empty((T, P, N), dtype=torch.float32, device=dev) if want_probs else None
+                values = torch.empty((T, P), dtype=torch.float32, device=dev)
+                nvec = (C.c_int32 * G)(*self.nvec)
+                lib, p = _capi.load(), _capi.ptr
+                with torch.cuda.device(dev):
+                    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                    _capi.check(lib.dynenv_policy_eval(p(features), p(actions), T, P, K, _capi.ARR_BF16 if self.operand_dtype == torch.bfloat16 else _capi.ARR_F16,
+                                                       C.byref(pk["struct"]), nvec, G, actions.shape[1], float(blk.relu.negative_slope), float(blk.bn.eps),
+                                                       p(logp), p(probs), p(values), p(self.eval_status), stream), "dynenv_policy_eval")
+                return logp, probs, values
+
+            def _eval_backward_buffers(self, dev, rows):
+                """the eight gradients in the packed layouts and the workspace: the module's, at fixed addresses (the workspace grows
+                with the rows up to its bound, dynenv.h)"""
+                K = self.feature_size
+                need = C.c_uint64(0)
+                _capi.check(_capi.load().dynenv_policy_eval_backward_workspace(rows, K, C.byref(need)), "dynenv_policy_eval_backward_workspace")
+                b = self._bwd
+                if b is None or b["dev"] != dev:
+                    e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+                    b = dict(dev=dev, aw=e(MAX_ROWS, K), ab=e(MAX_ROWS), w1=e(K // 2, K), b1=e(K // 2), lnw=e(K // 2), lnb=e(K // 2), w2=e(K // 2), b2=e(1),
+                             ws=None)
+                    c = _capi.PolicyGrad()
+                    c.d_actor_w, c.d_actor_b, c.d_critic_w1, c.d_critic_b1 = (b[k].data_ptr() for k in ("aw", "ab", "w1", "b1"))
+                    c.d_critic_ln_w, c.d_critic_ln_b, c.d_critic_w2, c.d_critic_b2 = (b[k].data_ptr() for k in ("lnw", "lnb", "w2", "b2"))
+                    b["struct"] = c
+                    self._bwd = b
+                if b["ws"] is None or b["ws"].numel() < need.value:
+                    b["ws"] = torch.empty((need.value,), dtype=torch.uint8, device=dev)
+                return b
+
+            def _eval_fused_backward(self, features, actions, d_logp, d_probs, d_values, want_features, wanted):
+                """one call of dynenv_policy_eval_backward -> (d_features or None, the gradients of _eval_params() where `wanted`, else None)"""
+                T, P, K = features.shape
+                G, dev, blk = len(self.nvec), features.device, self.critic.blocks
+                pk = self._eval_weights(dev, True)
+                b = self._eval_backward_buffers(dev, T * P)
+                d_features = torch.empty_like(features) if want_features else None
+                nvec = (C.c_int32 * G)(*self.nvec)
+                lib, p = _capi.load(), _capi.ptr
+                with torch.cuda.device(dev):
+                    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                    _capi.check(lib.dynenv_policy_eval_backward(p(features), p(actions), T, P, K, _capi.ARR_BF16 if self.operand_dtype == torch.bfloat16 else _capi.ARR_F16,
+                                                                C.byref(pk["struct"]), nvec, G, actions.shape[1], float(blk.relu.negative_slope), float(blk.bn.eps),
+                                                                p(d_logp), p(d_probs), p(d_values), C.byref(pk["struct_t"]), C.byref(b["struct"]), p(d_features),
+                                                                p(b["ws"]), b["ws"].numel(), p(self.eval_status), stream), "dynenv_policy_eval_backward")
+                out, s0 = [], 0
+                for n in self.nvec:   # (host ints: nothing is read from the device)
+                    out += [b["aw"][s0:s0 + n].clone(), b["ab"][s0:s0 + n].clone()]
+                    s0 += n
+                out += [b["w1"].clone(), b["b1"].clone(), b["lnw"].clone(), b["lnb"].clone(), b["w2"].view(1, -1).clone(), b["b2"].clone()]
+                return d_features, [g if w else None for g, w in zip(out, wanted)]
+
+            def evaluate(self, features, actions, want_probs=True):
+                K, G = self.feature_size, len(self.nvec)
+                assert features.dim() == 3 and features.shape[2] == K, "features is [T, P, %d]" % K
+                T, P = features.shape[0], features.shape[1]
+                assert actions.dim() == 3 and actions.shape[0] == T and actions.shape[1] >= G and actions.shape[2] == P, \
+                    "actions is [%d, AD >= %d, %d]" % (T, G, P)
+                if torch.is_grad_enabled() and (features.requires_grad or any(p.requires_grad for p in self.parameters())):
+                    self._eval_route = "torch"
+                    if self.fused_backward:
+                        why = self._no_eval_fused(features, actions, True)
+                        if why is None:
+                            self._eval_route = "fused (backward)"
+                            out = _eval_function().apply(self, features, actions, bool(want_probs), *self._eval_params())
+                            return PolicyEval(out[0], out[2] if want_probs else None, out[1])
+                        self._eval_route = "torch (fallback: %s)" % why
+                    return self._eval_torch(features, actions, want_probs)
+                with torch.no_grad():
+                    why = self._no_eval_fused(features, actions, False)
+                    if why is not None:
+                        self._eval_route = "torch (fallback: %s)" % why
+                        return self._eval_torch(features, actions, want_probs)
+                    self._eval_route = "fused"
+                    logp, probs, values = self._eval_fused(features, actions, want_probs)
+                    return PolicyEval(logp, probs, values)
+
+        def _eval_function():
+            if "fn" not in _lazy:
+                class PolicyEvalFunction(torch.autograd.Function):
+                    """(log_probs, values[, probs]) by dynenv_policy_eval; the gradient by dynenv_policy_eval_backward.  Saved: the inputs,
+                    nothing else.  The upstream gradients arrive as device tensors and go to the kernel as they are; one that is missing
+                    (an output the loss did not use) is zeros - for probs: NULL."""
+
+                    @staticmethod
+                    def forward(ctx, module, features, actions, want_probs, *params):
+                        with torch.no_grad():
+                            logp, probs, values = module._eval_fused(features.detach(), actions, want_probs, backward=True)
+                        ctx.module = module
+                        ctx.save_for_backward(features, actions)
+                        ctx.set_materialize_grads(False)
+                        return (logp, values, probs) if want_probs else (logp, values)
+
+                    @staticmethod
+                    @torch.autograd.function.once_differentiable
+                    def backward(ctx, d_logp, d_values, d_probs=None):
+                        features, actions = ctx.saved_tensors
+                        need = ctx.needs_input_grad
+                        T, P, _ = features.shape
+                        f32 = lambda g, shape: torch.zeros(shape, dtype=torch.float32, device=features.device) if g is None \
+                            else g.to(torch.float32).contiguous()   # noqa: E731
+                        d_logp, d_values = f32(d_logp, (T, len(ctx.module.nvec), P)), f32(d_values, (T, P))
+                        d_probs = None if d_probs is None else d_probs.to(torch.float32).contiguous()
+                        d_features, grads = ctx.module._eval_fused_backward(features.detach(), actions, d_logp, d_probs, d_values, need[1], need[4:])
+                        return (None, d_features, None, None) + tuple(grads)
+                _lazy["fn"] = PolicyEvalFunction
+            return _lazy["fn"]
 
         for cls in (ActorBlock, ActorLayer, CriticBlock, CriticLayer, GpuPolicyHead):
             cls.__qualname__ = cls.__name__

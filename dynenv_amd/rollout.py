@@ -285,35 +285,41 @@ class GpuRolloutStorage(object):
                                                    float(np.float32(gae_lambda)), p(ret), p(adv), stream), "dynenv_rollout_returns")
         return ret, adv
 
-    def _ppo_loss(self, advantage, delta=1e-8):
+    def _ppo_loss(self, advantage, log_probs, delta=1e-8):
         """storage.py:264-290 as it runs: `+ delta` stands outside the exp, and the minimum is returned with the sign it has"""
         import torch
         r_theta = torch.stack([torch.exp(log_prob - old_log_prob) + delta for log_prob, old_log_prob in
-                               zip(self.log_probs.permute(1, 0, 2), self.log_probs_old.permute(1, 0, 2))])
+                               zip(log_probs.permute(1, 0, 2), self.log_probs_old.permute(1, 0, 2))])
         r_theta_clipped = torch.clamp(r_theta, 1 - self.ppo_clip, 1 + self.ppo_clip)
         ppo_loss, _ = torch.min(torch.stack((r_theta * advantage.detach(), r_theta_clipped * advantage.detach())), dim=0)
         return ppo_loss.mean()
 
-    def a2c_loss(self, final_values, action_probs=None, value_coeff=0.5, entropy_coeff=0.1, discount=0.99, mode="reference", gae_lambda=0.95):
+    def a2c_loss(self, final_values, action_probs=None, value_coeff=0.5, entropy_coeff=0.1, discount=0.99, mode="reference", gae_lambda=0.95,
+                 evaluation=None):
         """The reference's a2c_loss (storage.py:211-262) statement for statement in torch on the stored tensors - the function as it
         runs, not a tidied one.  The returns come from returns(): `advantage = returns - values` differentiates through `values` alone,
         as the reference's does; with mode "gae" the policy term is weighted by returns()'s advantages instead.  action_probs: the
         reference's list over the steps of the list of the G probability tensors [P, n_g], or None for the stored `probs`.
+        evaluation: a PolicyEval (GpuPolicyHead.evaluate on features[:-1] and actions) whose log_probs, values and probs stand where the
+        stored log_probs, values and probs stood in the loss's statements - a rollout collected by a replayed graph stores them without
+        a history, the evaluation carries one; returns() still reads the stored values, and the stored probs are not needed then.
         -> A2CLosses(loss, policy, value, entropy, temp_entropy, rewards): the reference's fields, `loss` their sum (prepare_losses) -
         as tensors on the storage's device, not Python floats: nothing is copied to the host - and the stored rewards."""
         import torch
         from torch.distributions import Categorical
+        log_probs, values, probs = (self.log_probs, self.values, self.probs) if evaluation is None else \
+            (evaluation.log_probs, evaluation.values, evaluation.probs)
         rewards, adv = self.returns(final_values, discount, mode, gae_lambda)
-        advantage = rewards - self.values
+        advantage = rewards - values
         weight = adv if mode == "gae" else advantage
         if self.use_ppo is False:
-            policy_loss = torch.stack([(-log_prob * weight.detach()).mean() for log_prob in self.log_probs.permute(1, 0, 2)]).mean()
+            policy_loss = torch.stack([(-log_prob * weight.detach()).mean() for log_prob in log_probs.permute(1, 0, 2)]).mean()
         else:
-            policy_loss = self._ppo_loss(weight)
+            policy_loss = self._ppo_loss(weight, log_probs)
         value_loss = advantage.pow(2).mean()
         if action_probs is None:
-            assert self.probs is not None, "a2c_loss(action_probs=None) takes the stored probs: make the storage with n_probs = sum(groups)"
-            action_probs = [p.contiguous() for p in torch.split(self.probs, list(self.groups), dim=2)]   # (the layout of the reference's stack)
+            assert probs is not None, "a2c_loss(action_probs=None) takes the stored probs (make the storage with n_probs = sum(groups)) or the evaluation's"
+            action_probs = [p.contiguous() for p in torch.split(probs, list(self.groups), dim=2)]   # (the layout of the reference's stack)
         else:
             action_probs = [torch.stack([action_probs[time][a] for time in range(self.rollout_size)]) for a in range(len(action_probs[0]))]
         temp_actions = [action_prob.mean(dim=0) for action_prob in action_probs]

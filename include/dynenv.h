@@ -902,6 +902,96 @@ int dynenv_icm_backward(const float* features_dev, const float* actions_dev, con
                         const float* count_dev, const float* upstream_dev, const dynenv_icm_bwd_t* wt, const dynenv_icm_grad_t* grad,
                         float* d_features_dev, void* workspace_dev, uint64_t workspace_bytes, int32_t* status_dev, void* stream);
 
+/* ---- the policy head over a STORED rollout, with its backward: what trains the actor and the critic from a rollout that was collected
+ * without a gradient (a replayed graph).  The loss between the two calls is the caller's: A2CNet's a2c_loss in torch
+ * (DynEnv/models/storage.py:211-262) on the three tensors dynenv_policy_eval returns.
+ * dynenv_policy_eval, one launch, capturable (a launch and nothing else).  features_dev float32 [T][P][K] - the storage's
+ * features[0..T-1] - and actions_dev float32 [T][AD][P] are the storage's buffers; w, nvec, G, w_dtype, slope and ln_eps are
+ * dynenv_policy_head's, action_cols = AD, G <= AD <= 8; there is no Box block (C = 0): actor_w and actor_b are +0 from row N on.  Per
+ * row (t, p) the statement is dynenv_policy_head's with the stored action in place of the draw, f = features[t][p]:
+ *   l = f W_actor^T + b;  probs_g = softmax(l_g);  a_g = actions[t][g][p], rounded to the nearest integer and clamped into 0..n_g-1 - a
+ *       value that had to be clamped ORs bit 0 into status_dev[0] (int32 [1], or NULL), which the kernel never clears (dynenv_icm_losses'
+ *       convention);
+ *   logp_g = log(clamp(probs_g[a_g], eps32, 1 - eps32)), evaluated in double and rounded once;
+ *   value = LayerNorm(leaky(f W1^T + b1; slope); bn, ln_eps) . w2 + b2.
+ * Outputs in the storage's layouts, EVERY element written exactly once: logp_dev float32 [T][G][P], probs_dev float32 [T][P][N] or NULL
+ * (not written, the others' bits unchanged), value_dev float32 [T][P].
+ * Arithmetic and order of sums: dynenv_policy_head's, by the SAME device function - for the action that dynenv_policy_head drew from
+ * the same feature row and weights, logp, probs and value are the bits that entry point produced.  A row's result depends on that row,
+ * its actions and the weights alone; the same call twice gives the same bits.
+ * Errors, DYNENV_ERR_ARG, all reported before a device is looked for: a NULL features_dev, actions_dev, w, nvec, logp_dev or value_dev,
+ * or one of w's eight pointers of the actor and the critic; T, P or K < 1; G outside 1..8, an n_g outside 1..16, N > 32, AD outside
+ * G..8; a dtype outside 0..2; a buffer not 16-byte aligned (critic_b2, status_dev: 4-byte); T * P > 2^30 (the launch limit).  Then what
+ * the kernel does not take: DYNENV_ARR_F32, a K other than 64 or 128: DYNENV_ERR_UNSUPPORTED, also before the device. */
+int dynenv_policy_eval(const float* features_dev, const float* actions_dev, int32_t T, int32_t P, int32_t K, int32_t w_dtype,
+                       const dynenv_policy_t* w, const int32_t* nvec, int32_t G, int32_t action_cols, float slope, float ln_eps,
+                       float* logp_dev, float* probs_dev, float* value_dev, int32_t* status_dev, void* stream);
+/* dynenv_policy_bwd_t: a second HOST struct of device pointers, the transposed copies that the two transposed products of the backward
+ * read (an operand of the matrix units is contiguous along the contraction); the caller keeps them in step with dynenv_policy_t.
+ * ALWAYS bf16, whatever w_dtype is: the operand beside them carries the upstream gradient and is bf16 (below). */
+typedef struct dynenv_policy_bwd {
+  const void *actor_w_t;   /* [K][32] actor_w transposed, columns from N on +0: d_features takes dl W_actor, contracted over the logits (bf16) */
+  const void *critic_w1_t; /* [K][K/2] critic_w1 transposed: d_features takes dh_pre W1, contracted over the hidden units (bf16) */
+  const void *actor_w_t_lo, *critic_w1_t_lo; /* the second halves of the two, read with w_dtype float16 only (else they may be NULL): bf16(w - bf16(w)) of the float32 weight w, in the same layouts */
+} dynenv_policy_bwd_t;
+/* dynenv_policy_grad_t: a HOST struct of float32 device pointers, the outputs, in the layouts of the forward's packed operands. */
+typedef struct dynenv_policy_grad {
+  float *d_actor_w;                       /* [32][K]; rows from N on +0 */
+  float *d_actor_b;                       /* [32]; +0 from N on */
+  float *d_critic_w1;                     /* [K/2][K] */
+  float *d_critic_b1, *d_critic_ln_w, *d_critic_ln_b; /* [K/2] */
+  float *d_critic_w2, *d_critic_b2;       /* [K/2], [1] */
+} dynenv_policy_grad_t;
+/* The backward walks blocks of DYNENV_POLICY_EVAL_ROWS rows of the T * P on a persistent grid of at most
+ * DYNENV_POLICY_EVAL_MAX_WORKGROUPS workgroups: workgroup b takes the blocks b, b + grid, ..., keeps its partial weight gradients in
+ * registers and writes ONE slice of the workspace. */
+#define DYNENV_POLICY_EVAL_ROWS 64
+#define DYNENV_POLICY_EVAL_MAX_WORKGROUPS 256
+/* dynenv_policy_eval_backward_workspace: host only, touches no device.  rows = T * P.  *bytes = min(ceil(rows / 64), 256) *
+ * (K K / 2 + 34 K + 36) * 4: at most 4 362 240 at K = 64 and 12 881 920 at K = 128.  DYNENV_ERR_ARG: bytes NULL, rows or K < 1, rows >
+ * 2^30; DYNENV_ERR_UNSUPPORTED: a K other than 64 or 128. */
+int dynenv_policy_eval_backward_workspace(int32_t rows, int32_t K, uint64_t* bytes);
+/* dynenv_policy_eval_backward, two launches, capturable (launches and nothing else: nothing is synchronised, allocated or copied).
+ * features_dev .. ln_eps are dynenv_policy_eval's arguments, unchanged.  Upstream: d_logp_dev float32 [T][G][P], d_probs_dev float32
+ * [T][P][N] or NULL (= all zeros, the same bits), d_value_dev float32 [T][P].  The forward saved NOTHING: a row's logits, probabilities
+ * and hidden layer are recomputed by dynenv_policy_eval's device function.  Per row, with onehot(a_g) the stored action's and
+ * eps32 <= probs_g[a_g] <= 1 - eps32 meaning "not clamped" (the clamp's gradient is 0 where it binds):
+ *   dl_g = d_logp_g [not clamped] (onehot(a_g) - probs_g) + probs_g (d_probs_g - <d_probs_g, probs_g>)   - exactly 0 for a group of one action
+ *   with h_pre = f W1^T + b1, h = leaky(h_pre), xh = (h - mean) rstd, y = xh ln_w + ln_b, c = w2 * ln_w (elementwise), m(.) the mean over K/2:
+ *   dh_pre = d_value (rstd (c - m(c) - xh m(c xh))) leaky'(h_pre), leaky' = 1 where h_pre > 0 and slope elsewhere (h_pre == 0 included:
+ *       torch's LeakyReLU backward)
+ *   d_actor_w = sum dl^T f,  d_actor_b = sum dl,  d_critic_w1 = sum dh_pre^T f,  d_critic_b1 = sum dh_pre,  d_critic_ln_w = sum d_value w2 xh,
+ *   d_critic_ln_b = sum d_value w2,  d_critic_w2 = sum d_value y,  d_critic_b2 = sum d_value       - the sums over all T * P rows
+ *   d_features[t][p] = dl W_actor + dh_pre W1
+ * Outputs: EVERY element of the eight buffers of grad is written exactly once per call and nothing is accumulated into; the rows of
+ * d_actor_w and d_actor_b from N on are +0.  d_features_dev float32 [T][P][K], or NULL where the features want no gradient (the eight
+ * are then the same bits): every element written exactly once.  Zero upstream gives +0 everywhere.  A clamped action ORs bit 0 into
+ * status_dev[0] (or NULL) and takes the nearest action's gradients.
+ * workspace_dev: workspace_bytes >= what dynenv_policy_eval_backward_workspace(T * P, K) gives, 16-byte aligned, contents irrelevant
+ * before and after the call.
+ * Arithmetic: the two recomputed products take 16-bit operands of w_dtype on the matrix units and accumulate in float32, as the
+ * forward does.  The four products of the backward - dl W_actor, dh_pre W1, dl^T f, dh_pre^T f - run on the matrix units with float32
+ * accumulation too, but a quantity that carries an upstream gradient (dl, dh_pre) is NEVER float16: the loss hands over values of order
+ * 1 / (T P G), which float16's range does not hold.  THE CHOICE: dl and dh_pre are rounded to bf16 whatever w_dtype is, and the operand
+ * beside them - the transposed weights of dynenv_policy_bwd_t, the feature rows - is bf16 too (with w_dtype float16 the recomputed
+ * forward alone uses float16).  One bf16 holds 8 significant bits, float16 holds 11: with w_dtype float16 every one of these operands
+ * is a PAIR of bf16, v = hi + lo with hi = bf16(v) and lo = bf16(v - hi) of the float32 v - 16 significant bits in bf16's range - and
+ * a product A B is the three products hi hi + hi lo + lo hi, accumulated in float32 in that order.  Everything else - softmax, dl, the LayerNorm's backward, the five bias-like sums - is float32.  Rounding
+ * to bf16 and float32 accumulation commute with a power of two: scaling all three upstream tensors by one scales every output by it
+ * exactly (while nothing underflows).  Every sum has one fixed order and there is no floating-point atomic: the same call twice gives
+ * the same bits.  A row of d_features depends on that row, its actions, the weights and its upstream alone.  The weight gradients are
+ * added per workgroup - over the blocks it walks, in order - then over the workgroups' slices in workgroup order by the second launch:
+ * their order depends on T * P (through the grid) and on nothing else.  Inputs that are not finite are outside the contract.
+ * Errors, DYNENV_ERR_ARG, all reported before a device is looked for: dynenv_policy_eval's for the shared arguments; a NULL d_logp_dev,
+ * d_value_dev, wt, grad or workspace_dev, or one of the 2 + 8 pointers in the two structs (with float16: 4 + 8); a buffer not 16-byte aligned (d_critic_b2:
+ * 4-byte); a workspace that is too small.  Then what the kernel does not take: DYNENV_ARR_F32, a K other than 64 or 128 (K = 256: the
+ * module takes its torch route): DYNENV_ERR_UNSUPPORTED, also before the device. */
+int dynenv_policy_eval_backward(const float* features_dev, const float* actions_dev, int32_t T, int32_t P, int32_t K, int32_t w_dtype,
+                                const dynenv_policy_t* w, const int32_t* nvec, int32_t G, int32_t action_cols, float slope, float ln_eps,
+                                const float* d_logp_dev, const float* d_probs_dev, const float* d_value_dev, const dynenv_policy_bwd_t* wt,
+                                const dynenv_policy_grad_t* grad, float* d_features_dev, void* workspace_dev, uint64_t workspace_bytes,
+                                int32_t* status_dev, void* stream);
+
 
 /* Device self-test of the deterministic math header: evaluates sincos/atan2/sqrt/div on n host-provided doubles and
  * returns the raw results so tests can compare them bit-for-bit with the host evaluation. out: [n,5]. */
