@@ -9,7 +9,7 @@ SRC = os.path.join(PKG, "csrc", "dynenv_capi.hip")      # the C ABI + RoboCup an
 SRC_DRV = os.path.join(PKG, "csrc", "driving_tu.hip")    # the Driving kernels and their host code, a translation unit of their own: -Os (csrc/driving_host.h)
 DEPS = [os.path.join(PKG, "csrc", f) for f in
         ("dynenv_capi.hip", "driving_tu.hip", "driving_kernels.hip", "driving_partial.hip", "robocup_kernels.hip", "robocup_partial.hip",
-         "arranger_kernels.hip", "arranger_cols_kernels.hip", "arranger_fixed_kernels.hip", "arranger_embed_kernels.hip", "attention_kernels.hip", "recurrent_kernels.hip", "policy_kernels.hip", "rollout_kernels.hip", "icm_kernels.hip", "icm_backward_kernels.hip", "policy_eval_kernels.hip", "driving_reset.hip", "robocup_reset.hip", "env_rows_kernels.hip", "driving_dev.h", "driving_host.h", "robocup_dev.h", "dev_common.h", "dynenv_host.h", "robocup_host.hip")] + \
+         "arranger_kernels.hip", "arranger_cols_kernels.hip", "arranger_fixed_kernels.hip", "arranger_embed_kernels.hip", "attention_kernels.hip", "recurrent_kernels.hip", "policy_kernels.hip", "rollout_kernels.hip", "icm_kernels.hip", "icm_backward_kernels.hip", "policy_eval_kernels.hip", "driving_reset.hip", "robocup_reset.hip", "env_rows_kernels.hip", "driving_dev.h", "driving_host.h", "robocup_dev.h", "dev_common.h", "dynenv_host.h", "mma_tiles.h", "robocup_host.hip")] + \
        [os.path.join(ROOT, "include", f) for f in ("dynenv.h", "dynenv_math.h", "dynenv_math_probe.h")]
 UNITS = ((SRC, ("-O3",)), (SRC_DRV, ("-Os",)))
 

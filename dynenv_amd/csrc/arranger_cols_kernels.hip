@@ -47,6 +47,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dynenv.h"
+#include "mma_tiles.h"
 
 #ifndef ARR_PAD_NT_LOAD
 #define ARR_PAD_NT_LOAD 0
@@ -62,11 +63,6 @@
 #endif
 
 // ARR_BLOCK and arr_f4 are arranger_kernels.hip's.
-typedef unsigned arr_u4 __attribute__((ext_vector_type(4)));
-typedef float arr_f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 arr_bf2 __attribute__((ext_vector_type(2)));
-typedef _Float16 arr_h2 __attribute__((ext_vector_type(2)));
-
 struct ArrFixedRows { int rows[DYNENV_ARR_MAX_TYPES]; };   // rows[i] of the fixed mode, by value
 
 // (NT a template argument, not a function's: two loads that differ only in the hint are merged, hint lost, before the call is inlined)
@@ -78,24 +74,6 @@ template <bool NT, class V> __device__ __forceinline__ void arr_st(V* p, V v) {
   if constexpr (NT) __builtin_nontemporal_store(v, p);
   else *p = v;
 }
-
-struct ArrBf16 {
-  static __device__ __forceinline__ unsigned pack(float a, float b) {
-    const arr_f2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, arr_bf2));
-  }
-  static __device__ __forceinline__ arr_f2 widen(unsigned w) {
-    const arr_f2 v = {__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
-    return v;
-  }
-};
-struct ArrF16 {
-  static __device__ __forceinline__ unsigned pack(float a, float b) {
-    const arr_f2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, arr_h2));
-  }
-  static __device__ __forceinline__ arr_f2 widen(unsigned w) { return __builtin_convertvector(__builtin_bit_cast(arr_h2, w), arr_f2); }
-};
 
 // The widening backward writes 32 bytes per unit it reads.  Stored by the thread that read the unit - two 16-byte stores 16 bytes apart -
 // every store instruction of a wave covers every other 16 bytes of 2 KB: half lines, which non-temporal stores do not merge (measured,

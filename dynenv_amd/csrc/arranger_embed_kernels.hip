@@ -22,11 +22,11 @@
 // float32 throughout (the unit is built with -ffp-contract=off: every fma is written).  The store goes through LDS: the lanes of a wave
 // stage ARE_STAGE rows at a time and the wave writes them back with 16 bytes per lane, so that each store instruction covers whole
 // contiguous padded rows (two rows of 512 bytes at F = 128 float32); the 16-bit conversion (round to nearest even: ArrBf16 / ArrF16 of
-// arranger_cols_kernels.hip) is applied to the float32 result before it is staged.  The workgroups of type 0 also write the +0.0 behind
+// mma_tiles.h) is applied to the float32 result before it is staged.  The workgroups of type 0 also write the +0.0 behind
 // each player's last object, rows of consecutive players side by side.  A type whose weights are NULL writes +0.0 into its slots.
 #include <hip/hip_runtime.h>
-#include <stdint.h>
 #include "dynenv.h"
+#include "mma_tiles.h"
 
 #define ARE_PLAYERS ARR_BLOCK   // (t, p) per workgroup: one thread each in the scan
 #define ARE_STAGE 8             // rows a wave stages per round of the store
@@ -38,7 +38,7 @@
 #define ARE_MIN_WAVES 2
 #endif
 
-// ARR_BLOCK, ArrTypes, arr_f4 and arr_block_scan are arranger_kernels.hip's; arr_u4, arr_st, ArrBf16 and ArrF16 arranger_cols_kernels.hip's.
+// ARR_BLOCK, ArrTypes, arr_f4 and arr_block_scan are arranger_kernels.hip's; arr_st is arranger_cols_kernels.hip's.
 struct AreBlocks {   // dynenv_embed_block_t per type, by value
   const float* w1[DYNENV_ARR_MAX_TYPES];
   const float* ln1w[DYNENV_ARR_MAX_TYPES];

@@ -30,50 +30,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dynenv.h"
+#include "mma_tiles.h"
 
 #define ATP_BLOCK 256
 #define ATP_WAVES (ATP_BLOCK / 64)
-
-// arr_u4, arr_f2, ArrBf16 and ArrF16 are arranger_cols_kernels.hip's.
-typedef unsigned short atp_h;   // a 16-bit element, whichever type
-typedef float atp_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned atp_u2 __attribute__((ext_vector_type(2)));
-typedef __bf16 atp_bf8 __attribute__((ext_vector_type(8)));
-typedef _Float16 atp_h8 __attribute__((ext_vector_type(8)));
 
 struct AtpMha {   // dynenv_mha_t by value
   const atp_h *in_w, *out_w, *bias_k, *bias_v;
   const float *in_b, *out_b;
 };
 
-template <class CV> struct AtpMma;
-template <> struct AtpMma<ArrBf16> {
-  static __device__ __forceinline__ atp_f4 mma(arr_u4 a, arr_u4 b, atp_f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(atp_bf8, a), __builtin_bit_cast(atp_bf8, b), c, 0, 0, 0);
-  }
-};
-template <> struct AtpMma<ArrF16> {
-  static __device__ __forceinline__ atp_f4 mma(arr_u4 a, arr_u4 b, atp_f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(atp_h8, a), __builtin_bit_cast(atp_h8, b), c, 0, 0, 0);
-  }
-};
-
-__device__ __forceinline__ arr_u4 atp_ld16(const atp_h* p) { return *reinterpret_cast<const arr_u4*>(p); }
-template <class CV> __device__ __forceinline__ void atp_st4(atp_h* p, atp_f4 v) {   // four consecutive elements, rounded to nearest even
-  const atp_u2 w = {CV::pack(v.x, v.y), CV::pack(v.z, v.w)};
-  *reinterpret_cast<atp_u2*>(p) = w;
-}
-template <class CV> __device__ __forceinline__ atp_f4 atp_ld4(const atp_h* p) {      // ... widened exactly
-  const atp_u2 w = *reinterpret_cast<const atp_u2*>(p);
-  const arr_f2 lo = CV::widen(w.x), hi = CV::widen(w.y);
-  const atp_f4 v = {lo.x, lo.y, hi.x, hi.y};
-  return v;
-}
-template <class CV> __device__ __forceinline__ atp_f4 atp_round4(atp_f4 v) {         // what the 16-bit store keeps of v
-  const arr_f2 lo = CV::widen(CV::pack(v.x, v.y)), hi = CV::widen(CV::pack(v.z, v.w));
-  const atp_f4 r = {lo.x, lo.y, hi.x, hi.y};
-  return r;
-}
 // the lanes of a wave hand rows to each other through the wave's LDS buffer: LDS operations of one wave complete in order, the fence
 // keeps the compiler from moving an access across the hand-over
 __device__ __forceinline__ void atp_wave_sync() {
@@ -81,18 +47,6 @@ __device__ __forceinline__ void atp_wave_sync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-// the sum over a player row: this lane's part, then the three other quarters of the wave (same lane & 15)
-__device__ __forceinline__ float atp_row_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-__device__ __forceinline__ float atp_row_max(float v) {
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  v = fmaxf(v, __shfl_xor(v, 32, 64));
-  return v;
-}
-__device__ __forceinline__ float atp_sum4(atp_f4 v) { return (v.x + v.y) + (v.z + v.w); }
 
 // phase 1: kb[key][:] = src[key] Wk^T + bk and vt[:][key] = src[key] Wv^T + bv for the keys 0 .. 16 * ceil(c / 16) - 1; a unit is 16 keys, K or V,
 // and one half of the features, so that few keys still occupy the four waves
@@ -337,7 +291,7 @@ __device__ __forceinline__ void atp_body(const atp_h* __restrict__ padded, const
     for (int ft = 0; ft < F / 16; ++ft) *reinterpret_cast<atp_f4*>(&part[wave][16 * ft + 4 * lq]) = pooled[ft];
   }
   __syncthreads();
-  for (int f = tid; f < F; f += ATP_BLOCK) out[(size_t)p * F + f] = (((part[0][f] + part[1][f]) + part[2][f]) + part[3][f]) / (float)n;
+  for (int f = tid; f < F; f += ATP_BLOCK) out[(size_t)p * F + f] = mt_wave_sum4(&part[0][f], F) / (float)n;
 }
 
 #define ATP_KERNEL(NAME, F, CV, NT)                                                                                                      \
@@ -381,10 +335,9 @@ extern "C" int dynenv_attend_pool(const void* padded_dev, int32_t padded_dtype, 
   if (!atp_mha_complete(obj_att) || !atp_mha_complete(temp_att)) return fail(DYNENV_ERR_ARG, "attention: an attention has all six of its pointers");
   if (T < 1 || P < 1 || F < 1 || M < 0) return fail(DYNENV_ERR_ARG, "attention: bad shape");
   if (padded_dtype < DYNENV_ARR_F32 || padded_dtype > DYNENV_ARR_F16) return fail(DYNENV_ERR_ARG, "attention: unknown dtype (DYNENV_ARR_BF16 or _F16)");
-  const void* aligned[] = {padded_dev, out_dev, ln_w_dev, ln_b_dev, conf_w_dev, obj_att->in_w, obj_att->out_w, obj_att->in_b, obj_att->out_b,
-                           temp_att->in_w, temp_att->out_w, temp_att->in_b, temp_att->out_b};
-  for (const void* q : aligned)
-    if ((uintptr_t)q % 16) return fail(DYNENV_ERR_ARG, "attention: buffers must be 16-byte aligned");
+  if (int rc = model_aligned("attention", {padded_dev, out_dev, ln_w_dev, ln_b_dev, conf_w_dev, obj_att->in_w, obj_att->out_w, obj_att->in_b, obj_att->out_b,
+                                           temp_att->in_w, temp_att->out_w, temp_att->in_b, temp_att->out_b}, 16))
+    return rc;
   const void* aligned8[] = {obj_att->bias_k, obj_att->bias_v, temp_att->bias_k, temp_att->bias_v};
   for (const void* q : aligned8)
     if ((uintptr_t)q % 8) return fail(DYNENV_ERR_ARG, "attention: bias_k and bias_v must be 8-byte aligned");

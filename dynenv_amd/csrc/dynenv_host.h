@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -36,6 +37,43 @@ struct DeviceGuard {
       return fail(DYNENV_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                 \
   } while (0)
 static inline int launched() { HIP_OK(hipGetLastError()); return DYNENV_OK; }  // behind an entry point's (last) kernel launch
+
+// The argument checks the model kernels' entry points share; `who` opens the message ("policy head: ...").  Each entry point calls them
+// in its own order: argument errors, then what the kernel does not take, then the device.
+// The discrete action groups of nvec[0 .. G-1] (G checked by the caller), packed as the kernels take them (mt_group, mma_tiles.h); C: the
+// outputs that share the 32 rows with the N logits (the policy head's Box block), -1 where the call has none and its message names N alone.
+struct ModelGroups {
+  unsigned long long off = 0;   // 8 bits per group: the first logit of group g
+  unsigned n = 0;               // 4 bits per group: n_g - 1
+  int N = 0;
+};
+static inline int model_groups(const char* who, const int32_t* nvec, int G, int action_cols, ModelGroups& out, int C = -1) {
+  out = ModelGroups();
+  for (int g = 0; g < G; ++g) {
+    if (nvec[g] < 1 || nvec[g] > 16) return fail(DYNENV_ERR_ARG, std::string(who) + ": a group has 1..16 actions");
+    out.off |= (unsigned long long)out.N << (8 * g);
+    out.n |= (unsigned)(nvec[g] - 1) << (4 * g);
+    out.N += nvec[g];
+  }
+  if (out.N + (C < 0 ? 0 : C) > DYNENV_POLICY_ROWS) return fail(DYNENV_ERR_ARG, std::string(who) + (C < 0 ? ": N is at most 32" : ": N + C is at most 32"));
+  if (action_cols < G || action_cols > 8) return fail(DYNENV_ERR_ARG, std::string(who) + ": action_cols is G..8");
+  return DYNENV_OK;
+}
+static inline int model_aligned(const char* who, std::initializer_list<const void*> ptrs, unsigned bytes) {   // (NULL passes)
+  for (const void* q : ptrs)
+    if ((uintptr_t)q % bytes) return fail(DYNENV_ERR_ARG, std::string(who) + ": buffers must be " + std::to_string(bytes) + "-byte aligned");
+  return DYNENV_OK;
+}
+// the operands' type: an argument error unless it is one of the three, ...
+static inline int model_operand_dtype(const char* who, int32_t w_dtype) {
+  if (w_dtype < DYNENV_ARR_F32 || w_dtype > DYNENV_ARR_F16) return fail(DYNENV_ERR_ARG, std::string(who) + ": unknown dtype (DYNENV_ARR_BF16 or _F16)");
+  return DYNENV_OK;
+}
+// ... and, behind the argument errors, unsupported where it is float32; `fused`: "layer" or "backward"
+static inline int model_operand_16bit(const char* who, int32_t w_dtype, const char* fused) {
+  if (w_dtype == DYNENV_ARR_F32) return fail(DYNENV_ERR_UNSUPPORTED, std::string(who) + ": the fused " + fused + " takes bf16 or fp16 operands");
+  return DYNENV_OK;
+}
 
 // One description of a handle's per-environment rows: every checkpointed array of the shape [fields][E][row], in allocation order
 // (alloc_rows below).  env_rows_save_kernel / env_rows_load_kernel (env_rows_kernels.hip, in the dynenv_capi.hip unit) take it by value

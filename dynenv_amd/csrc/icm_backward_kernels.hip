@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dynenv.h"
+#include "mma_tiles.h"
 
 #define ICB_BLOCK 256
 #define ICB_WAVES (ICB_BLOCK / 64)
@@ -77,35 +78,14 @@ __device__ __forceinline__ void icb_scales(const float* count, const float* upst
   beta = n > 0.f ? upstream[1] / (n * (float)G) : 0.f;
 }
 
-template <class CV> __device__ __forceinline__ atp_h icb_h(float v) { return (atp_h)(CV::pack(v, 0.f) & 0xffffu); }
-
-// four consecutive elements of row r: row-major into rm, and into column r of the transposed tile
-template <class CV> __device__ __forceinline__ void icb_st4_both(atp_h* rm, atp_h* tr, int r, atp_f4 v) {
-  const unsigned lo = CV::pack(v.x, v.y), hi = CV::pack(v.z, v.w);
-  const atp_u2 w = {lo, hi};
-  *reinterpret_cast<atp_u2*>(rm) = w;
-  tr[r] = (atp_h)(lo & 0xffffu); tr[ICB_RS + r] = (atp_h)(lo >> 16);
-  tr[2 * ICB_RS + r] = (atp_h)(hi & 0xffffu); tr[3 * ICB_RS + r] = (atp_h)(hi >> 16);
-}
-
 template <int K, class CV>
 __device__ __forceinline__ void icb_load_tile(atp_h* xb, atp_h* xt, const float* src, int row0, int P, int tid) {
   constexpr int XS = K + 8;
   const atp_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
   for (int i = tid; i < ICB_ROWS * (K / 4); i += ICB_BLOCK) {
     const int r = i / (K / 4), col = 4 * (i % (K / 4)), p = row0 + r;
-    icb_st4_both<CV>(xb + r * XS + col, xt + col * ICB_RS, r, p < P ? rh_ldf4(src + (size_t)p * K + col) : zero4);
+    mt_st4_both<CV, ICB_RS>(xb + r * XS + col, xt + col * ICB_RS, r, p < P ? mt_ldf4(src + (size_t)p * K + col) : zero4);
   }
-}
-
-__device__ __forceinline__ atp_f4 icb_sum16(atp_f4 v) {   // over the 16 lanes of equal lane >> 4, in one fixed order
-#pragma unroll
-  for (int m = 1; m < 16; m <<= 1) {
-    atp_f4 o;
-    o.x = __shfl_xor(v.x, m, 64); o.y = __shfl_xor(v.y, m, 64); o.z = __shfl_xor(v.z, m, 64); o.w = __shfl_xor(v.w, m, 64);
-    v += o;
-  }
-  return v;
 }
 
 template <int K, class CV>
@@ -134,7 +114,7 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
   const int P = a.P, G = a.G;
   const atp_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const bool inv_wave = wave >= 2;   // tiles 10 and 11, the logits, are the third tile of waves 2 and 3
-  const atp_h one = icb_h<CV>(1.0f);
+  const atp_h one = mt_h<CV>(1.0f);
   float alpha, beta;
   icb_scales(a.count, a.upstream, K, G, alpha, beta);
 
@@ -173,15 +153,9 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
       bool clamped = false;
       for (int i = tid; i < ICB_ROWS * G; i += ICB_BLOCK) {
         const int g = i / ICB_ROWS, r = i % ICB_ROWS, p = row0 + r;
-        const int off = (int)((a.group_off >> (8 * g)) & 255u), last = (int)((a.group_n >> (4 * g)) & 15u);
-        int act = 0;
-        if (p < P) {
-          const float v = rintf(a.actions[((size_t)t * a.AD + g) * P + p]);
-          const bool ok = v >= 0.f && v <= (float)last;
-          act = ok ? (int)v : v > (float)last ? last : 0;
-          clamped |= !ok;
-        }
-        acts[r * 8 + g] = off + act;
+        const MtGroup gr = mt_group(a.group_off, a.group_n, g);
+        const int off = gr.off, n = gr.n;
+        acts[r * 8 + g] = off + (p < P ? mt_stored_action(a.actions[((size_t)t * a.AD + g) * P + p], n - 1, clamped) : 0);
       }
       if (clamped && a.status) atomicOr(a.status, 1);
       if (tid < ICB_ROWS) {
@@ -207,10 +181,10 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
           const int tile = wave + ICB_WAVES * j;
           atp_f4 b;
           if (tile < HT) {
-            b = rh_ldf4(a.b1 + 16 * tile + 4 * lq);
+            b = mt_ldf4(a.b1 + 16 * tile + 4 * lq);
             wrow[j] = a.w1 + (size_t)(16 * tile + lr) * K;
           } else {
-            b = rh_ldf4(a.binv + 16 * (tile - HT) + 4 * lq);
+            b = mt_ldf4(a.binv + 16 * (tile - HT) + 4 * lq);
             wrow[j] = a.winv + (size_t)(16 * (tile - HT) + lr) * (2 * K);
           }
 #pragma unroll
@@ -245,19 +219,13 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
             for (int s = 0; s < S; ++s) {
               const int r = 16 * s + lr;
               atp_f4 v = y[j][s];
-              for (int g = 0; g < G; ++g) v += rh_ldf4(a.w1_act + (size_t)acts[r * 8 + g] * ICB_HID + 16 * tile + 4 * lq);
-              const unsigned m = (v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u);
-              pos |= m << (4 * (j * S + s));
-              v.x = v.x > 0.f ? v.x : v.x * a.slope; v.y = v.y > 0.f ? v.y : v.y * a.slope;
-              v.z = v.z > 0.f ? v.z : v.z * a.slope; v.w = v.w > 0.f ? v.w : v.w * a.slope;
-              icb_st4_both<CV>(hb + r * HS + 16 * tile + 4 * lq, ht + (16 * tile + 4 * lq) * RS, r, v);
+              for (int g = 0; g < G; ++g) v += mt_ldf4(a.w1_act + (size_t)acts[r * 8 + g] * ICB_HID + 16 * tile + 4 * lq);
+              pos |= mt_pos4(v) << (4 * (j * S + s));
+              mt_st4_both<CV, ICB_RS>(hb + r * HS + 16 * tile + 4 * lq, ht + (16 * tile + 4 * lq) * RS, r, mt_leaky4(v, a.slope));
             }
           } else {
 #pragma unroll
-            for (int s = 0; s < S; ++s) {
-              float* q = lg + (16 * s + lr) * ICB_LS + 16 * (tile - HT) + 4 * lq;
-              q[0] = y[j][s].x; q[1] = y[j][s].y; q[2] = y[j][s].z; q[3] = y[j][s].w;
-            }
+            for (int s = 0; s < S; ++s) mt_st_f4(lg + (16 * s + lr) * ICB_LS + 16 * (tile - HT) + 4 * lq, y[j][s]);
           }
         }
       }
@@ -271,7 +239,7 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
 #pragma unroll
         for (int j = 0; j < OPW; ++j) {
           const int tile = wave + ICB_WAVES * j;
-          const atp_f4 b = rh_ldf4(a.b2 + 16 * tile + 4 * lq);
+          const atp_f4 b = mt_ldf4(a.b2 + 16 * tile + 4 * lq);
           wrow[j] = a.w2 + (size_t)(16 * tile + lr) * ICB_HID;
 #pragma unroll
           for (int s = 0; s < S; ++s) z[j][s] = b;
@@ -295,10 +263,10 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
 #pragma unroll
           for (int j = 0; j < OPW; ++j) {
             const int col = 16 * (wave + ICB_WAVES * j) + 4 * lq;
-            const atp_f4 e = live ? z[j][s] - rh_ldf4(next32 + (size_t)p * K + col) : zero4;
+            const atp_f4 e = live ? z[j][s] - mt_ldf4(next32 + (size_t)p * K + col) : zero4;
             db2[j] += e;
             carryn[j][s] = zero4 - alpha * e;
-            icb_st4_both<CV>(eb + r * XS + col, et + col * RS, r, e);
+            mt_st4_both<CV, ICB_RS>(eb + r * XS + col, et + col * RS, r, e);
           }
         }
       }
@@ -306,7 +274,8 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
         const int r = tid & 31, g = tid >> 5;
         if (g < G) {
           float* L = lg + r * ICB_LS;
-          const int off = (int)((a.group_off >> (8 * g)) & 255u), n = (int)((a.group_n >> (4 * g)) & 15u) + 1;
+          const MtGroup gr = mt_group(a.group_off, a.group_n, g);
+          const int off = gr.off, n = gr.n;
           const int taken = acts[r * 8 + g];
           const bool live = on[r] != 0;
           float m = L[off];
@@ -317,7 +286,7 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
             const float sm = expf(L[off + j] - m) / sum;   // a group of one action: exp(0) / 1 - 1 = 0
             const float q = live ? sm - (off + j == taken ? 1.0f : 0.0f) : 0.0f;
             L[off + j] = q;
-            const atp_h q16 = icb_h<CV>(q);
+            const atp_h q16 = mt_h<CV>(q);
             qb[r * QS + off + j] = q16;
             qt[(off + j) * RS + r] = q16;
           }
@@ -357,11 +326,8 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
           }
 #pragma unroll
           for (int s = 0; s < S; ++s) {
-            const unsigned m = pos >> (4 * (j * S + s));
-            atp_f4& v = d[j][s];
-            v.x = (m & 1u) ? v.x : v.x * a.slope; v.y = (m & 2u) ? v.y : v.y * a.slope;
-            v.z = (m & 4u) ? v.z : v.z * a.slope; v.w = (m & 8u) ? v.w : v.w * a.slope;
-            db1[j] += v;
+            d[j][s] = mt_leaky_grad4(d[j][s], pos >> (4 * (j * S + s)), a.slope);
+            db1[j] += d[j][s];
           }
         }
       }
@@ -371,7 +337,7 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
         const int tile = wave + ICB_WAVES * j;
         if (tile < HT) {
 #pragma unroll
-          for (int s = 0; s < S; ++s) icb_st4_both<CV>(hb + (16 * s + lr) * HS + 16 * tile + 4 * lq, ht + (16 * tile + 4 * lq) * RS, 16 * s + lr, d[j][s]);
+          for (int s = 0; s < S; ++s) mt_st4_both<CV, ICB_RS>(hb + (16 * s + lr) * HS + 16 * tile + 4 * lq, ht + (16 * tile + 4 * lq) * RS, 16 * s + lr, d[j][s]);
         }
       }
       __syncthreads();
@@ -454,7 +420,7 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
       *reinterpret_cast<atp_f4*>(part + icb_off_w1(K) + (16 * h + lr) * K + 16 * kt + 4 * lq) = gW1[j][h];
       *reinterpret_cast<atp_f4*>(part + icb_off_w2(K) + (16 * kt + lr) * ICB_HID + 16 * h + 4 * lq) = gW2[j][h];
     }
-    const atp_f4 b = icb_sum16(db2[j]);
+    const atp_f4 b = mt_sum16(db2[j]);
     if (lr == 0) *reinterpret_cast<atp_f4*>(part + icb_off_b2(K) + 16 * kt + 4 * lq) = b;
   }
 #pragma unroll
@@ -471,7 +437,7 @@ __device__ __forceinline__ void icb_body(const IcbArgs& a) {
 #pragma unroll
   for (int j = 0; j < TPW; ++j) {
     const int tile = wave + ICB_WAVES * j;
-    const atp_f4 b = icb_sum16(db1[j]);
+    const atp_f4 b = mt_sum16(db1[j]);
     if (tile < HT && lr == 0) *reinterpret_cast<atp_f4*>(part + icb_off_b1(K) + 16 * tile + 4 * lq) = b;
   }
   if (tid < 32) part[icb_off_ib(K) + tid] = dbi;
@@ -533,29 +499,19 @@ extern "C" int dynenv_icm_backward(const float* features_dev, const float* actio
     return fail(DYNENV_ERR_ARG, "icm backward: the seven gradients have their pointers");
   if (T < 1 || P < 1 || K < 1) return fail(DYNENV_ERR_ARG, "icm backward: bad shape");
   if (G < 1 || G > DYNENV_POLICY_MAX_GROUPS) return fail(DYNENV_ERR_ARG, "icm backward: G is 1..8");
-  int N = 0;
-  unsigned long long group_off = 0;
-  unsigned group_n = 0;
-  for (int g = 0; g < G; ++g) {
-    if (nvec[g] < 1 || nvec[g] > 16) return fail(DYNENV_ERR_ARG, "icm backward: a group has 1..16 actions");
-    group_off |= (unsigned long long)N << (8 * g);
-    group_n |= (unsigned)(nvec[g] - 1) << (4 * g);
-    N += nvec[g];
-  }
-  if (N > DYNENV_POLICY_ROWS) return fail(DYNENV_ERR_ARG, "icm backward: N is at most 32");
-  if (action_cols < G || action_cols > 8) return fail(DYNENV_ERR_ARG, "icm backward: action_cols is G..8");
-  if (w_dtype < DYNENV_ARR_F32 || w_dtype > DYNENV_ARR_F16) return fail(DYNENV_ERR_ARG, "icm backward: unknown dtype (DYNENV_ARR_BF16 or _F16)");
-  const void* aligned[] = {features_dev, actions_dev, finished_dev, d_features_dev, workspace_dev, w->fwd_w1, w->fwd_w1_act, w->fwd_b1, w->fwd_w2, w->fwd_b2,
-                           w->inv_w, w->inv_b, wt->fwd_w2_t, wt->fwd_w1_t, wt->inv_w_t, grad->d_fwd_w1, grad->d_fwd_w1_act, grad->d_fwd_b1, grad->d_fwd_w2,
-                           grad->d_fwd_b2, grad->d_inv_w, grad->d_inv_b};
-  for (const void* q : aligned)
-    if ((uintptr_t)q % 16) return fail(DYNENV_ERR_ARG, "icm backward: buffers must be 16-byte aligned");
+  ModelGroups gr;
+  if (int rc = model_groups("icm backward", nvec, G, action_cols, gr)) return rc;
+  if (int rc = model_operand_dtype("icm backward", w_dtype)) return rc;
+  if (int rc = model_aligned("icm backward", {features_dev, actions_dev, finished_dev, d_features_dev, workspace_dev, w->fwd_w1, w->fwd_w1_act, w->fwd_b1,
+                                              w->fwd_w2, w->fwd_b2, w->inv_w, w->inv_b, wt->fwd_w2_t, wt->fwd_w1_t, wt->inv_w_t, grad->d_fwd_w1,
+                                              grad->d_fwd_w1_act, grad->d_fwd_b1, grad->d_fwd_w2, grad->d_fwd_b2, grad->d_inv_w, grad->d_inv_b}, 16))
+    return rc;
   if ((uintptr_t)count_dev % 4 || (uintptr_t)upstream_dev % 4 || (uintptr_t)status_dev % 4)
     return fail(DYNENV_ERR_ARG, "icm backward: count_dev, upstream_dev and status_dev are 4-byte aligned");
   if (((int64_t)T + 1) * P > (int64_t)1 << 30) return fail(DYNENV_ERR_ARG, "icm backward: (T + 1) * P too large for one launch");
   if ((K == 64 || K == 128) && workspace_bytes < (uint64_t)icb_groups(P) * (uint64_t)icb_part(K) * 4u)
     return fail(DYNENV_ERR_ARG, "icm backward: the workspace is smaller than dynenv_icm_backward_workspace asks for");
-  if (w_dtype == DYNENV_ARR_F32) return fail(DYNENV_ERR_UNSUPPORTED, "icm backward: the fused backward takes bf16 or fp16 operands");
+  if (int rc = model_operand_16bit("icm backward", w_dtype, "backward")) return rc;
   if (K != 64 && K != 128) return fail(DYNENV_ERR_UNSUPPORTED, "icm backward: the fused backward takes K = 64 or 128");
   if (int rc = have_device()) return rc;
   IcbArgs k;
@@ -564,7 +520,7 @@ extern "C" int dynenv_icm_backward(const float* features_dev, const float* actio
   k.w2t = static_cast<const atp_h*>(wt->fwd_w2_t); k.w1t = static_cast<const atp_h*>(wt->fwd_w1_t); k.winvt = static_cast<const atp_h*>(wt->inv_w_t);
   k.w1_act = w->fwd_w1_act; k.b1 = w->fwd_b1; k.b2 = w->fwd_b2; k.binv = w->inv_b;
   k.count = count_dev; k.upstream = upstream_dev;
-  k.group_off = group_off; k.group_n = group_n;
+  k.group_off = gr.off; k.group_n = gr.n;
   k.T = T; k.P = P; k.G = G; k.AD = action_cols; k.nblocks = (P + ICB_ROWS - 1) / ICB_ROWS; k.slope = slope;
   k.dfeat = d_features_dev; k.part = static_cast<float*>(workspace_dev); k.status = status_dev;
   const int groups = icb_groups(P);
@@ -572,6 +528,6 @@ extern "C" int dynenv_icm_backward(const float* features_dev, const float* actio
   hipLaunchKernelGGL(kernels[K == 128][w_dtype == DYNENV_ARR_F16], dim3((unsigned)groups), dim3(ICB_BLOCK), 0, (hipStream_t)stream, k);
   IcbGrad o = {grad->d_fwd_w1, grad->d_fwd_w1_act, grad->d_fwd_b1, grad->d_fwd_w2, grad->d_fwd_b2, grad->d_inv_w, grad->d_inv_b};
   hipLaunchKernelGGL(icm_bwd_reduce_kernel, dim3((unsigned)((icb_part(K) + ICB_RED_BLOCK - 1) / ICB_RED_BLOCK)), dim3(ICB_RED_BLOCK), 0, (hipStream_t)stream,
-                     (const float*)workspace_dev, groups, (int)K, (int)G, N, count_dev, upstream_dev, o);
+                     (const float*)workspace_dev, groups, (int)K, (int)G, gr.N, count_dev, upstream_dev, o);
   return launched();
 }

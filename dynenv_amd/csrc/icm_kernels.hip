@@ -12,7 +12,7 @@
 //
 // Work.  One workgroup of four waves owns ICM_ROWS = 64 players - four strips of 16, policy_kernels.hip's shape - and walks t = 0 .. T-1:
 // the tile features[t + 1][64 players] is read from memory once, rounded into LDS, and serves as `next` of step t and as `cur` of step
-// t + 1 (two LDS tiles that swap roles).  16x16x32 MFMAs with float32 accumulators in the orientation D^T = W X^T, so that a lane's
+// t + 1 (two LDS tiles that swap roles).  The products are the tile toolkit's (mma_tiles.h; DESIGN.md, "The tile toolkit"): a lane's
 // accumulator holds four consecutive outputs of one row; a wave computes its output tiles for ALL FOUR strips, so every weight fragment
 // it fetches (16 contiguous bytes per lane, from L2) feeds four MFMAs and the workgroup streams the weights once per 64 players and step.
 //   phase 0: features[t + 1] of the 64 players rounded into LDS (t = 0: features[0] too); the rows' action indices into LDS
@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dynenv.h"
+#include "mma_tiles.h"
 
 #define ICM_BLOCK 256
 #define ICM_WAVES (ICM_BLOCK / 64)
@@ -36,9 +37,6 @@
 #define ICM_HID DYNENV_ICM_HIDDEN_PAD   // 160: the forward net's 140 hidden units padded to the k step of the second product
 #define ICM_LS 33                       // floats per LDS row of the 32 logits: a lane per row reads without bank conflicts
 #define ICM_RED_BLOCK 1024
-
-// arr_u4, ArrBf16, ArrF16: arranger_cols_kernels.hip's.  atp_h, atp_f4, AtpMma, atp_ld16, atp_st4, atp_row_sum, atp_sum4: attention_kernels.hip's.
-// rh_ldf4: recurrent_kernels.hip's.
 
 struct IcmArgs {   // dynenv_icm_t by value, the buffers and the sizes
   const float *features, *actions;
@@ -58,7 +56,7 @@ __device__ __forceinline__ void icm_load_tile(atp_h* xb, const float* src, int r
   const atp_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
   for (int i = tid; i < ICM_ROWS * (K / 4); i += ICM_BLOCK) {
     const int r = i / (K / 4), col = 4 * (i % (K / 4)), p = row0 + r;
-    atp_st4<CV>(xb + r * XS + col, p < P ? rh_ldf4(src + (size_t)p * K + col) : zero4);
+    atp_st4<CV>(xb + r * XS + col, p < P ? mt_ldf4(src + (size_t)p * K + col) : zero4);
   }
 }
 
@@ -89,15 +87,9 @@ __device__ __forceinline__ void icm_body(const IcmArgs& a) {
     bool clamped = false;
     for (int i = tid; i < ICM_ROWS * G; i += ICM_BLOCK) {
       const int g = i / ICM_ROWS, r = i % ICM_ROWS, p = row0 + r;
-      const int off = (int)((a.group_off >> (8 * g)) & 255u), last = (int)((a.group_n >> (4 * g)) & 15u);
-      int act = 0;
-      if (p < P) {
-        const float v = rintf(a.actions[((size_t)t * a.AD + g) * P + p]);
-        const bool ok = v >= 0.f && v <= (float)last;
-        act = ok ? (int)v : v > (float)last ? last : 0;
-        clamped |= !ok;
-      }
-      acts[r * 8 + g] = off + act;
+      const MtGroup gr = mt_group(a.group_off, a.group_n, g);
+      const int off = gr.off, n = gr.n;
+      acts[r * 8 + g] = off + (p < P ? mt_stored_action(a.actions[((size_t)t * a.AD + g) * P + p], n - 1, clamped) : 0);
     }
     if (clamped && a.status) atomicOr(a.status, 1);
     __syncthreads();
@@ -111,10 +103,10 @@ __device__ __forceinline__ void icm_body(const IcmArgs& a) {
         const int tile = wave + ICM_WAVES * j;
         atp_f4 b;
         if (tile < HT) {
-          b = rh_ldf4(a.b1 + 16 * tile + 4 * lq);
+          b = mt_ldf4(a.b1 + 16 * tile + 4 * lq);
           wrow[j] = a.w1 + (size_t)(16 * tile + lr) * K;
         } else {
-          b = rh_ldf4(a.binv + 16 * (tile - HT) + 4 * lq);
+          b = mt_ldf4(a.binv + 16 * (tile - HT) + 4 * lq);
           wrow[j] = a.winv + (size_t)(16 * (tile - HT) + lr) * (2 * K);
         }
 #pragma unroll
@@ -149,17 +141,12 @@ __device__ __forceinline__ void icm_body(const IcmArgs& a) {
           for (int s = 0; s < ICM_STRIPS; ++s) {
             const int r = 16 * s + lr;
             atp_f4 v = y[j][s];
-            for (int g = 0; g < G; ++g) v += rh_ldf4(a.w1_act + (size_t)acts[r * 8 + g] * ICM_HID + 16 * tile + 4 * lq);
-            v.x = v.x > 0.f ? v.x : v.x * a.slope; v.y = v.y > 0.f ? v.y : v.y * a.slope;
-            v.z = v.z > 0.f ? v.z : v.z * a.slope; v.w = v.w > 0.f ? v.w : v.w * a.slope;
-            atp_st4<CV>(hb + r * HS + 16 * tile + 4 * lq, v);
+            for (int g = 0; g < G; ++g) v += mt_ldf4(a.w1_act + (size_t)acts[r * 8 + g] * ICM_HID + 16 * tile + 4 * lq);
+            atp_st4<CV>(hb + r * HS + 16 * tile + 4 * lq, mt_leaky4(v, a.slope));
           }
         } else {
 #pragma unroll
-          for (int s = 0; s < ICM_STRIPS; ++s) {
-            float* q = lg + (16 * s + lr) * ICM_LS + 16 * (tile - HT) + 4 * lq;
-            q[0] = y[j][s].x; q[1] = y[j][s].y; q[2] = y[j][s].z; q[3] = y[j][s].w;
-          }
+          for (int s = 0; s < ICM_STRIPS; ++s) mt_st_f4(lg + (16 * s + lr) * ICM_LS + 16 * (tile - HT) + 4 * lq, y[j][s]);
         }
       }
     }
@@ -172,7 +159,7 @@ __device__ __forceinline__ void icm_body(const IcmArgs& a) {
 #pragma unroll
       for (int j = 0; j < OPW; ++j) {
         const int tile = wave + ICM_WAVES * j;
-        const atp_f4 b = rh_ldf4(a.b2 + 16 * tile + 4 * lq);
+        const atp_f4 b = mt_ldf4(a.b2 + 16 * tile + 4 * lq);
         wrow[j] = a.w2 + (size_t)(16 * tile + lr) * ICM_HID;
 #pragma unroll
         for (int s = 0; s < ICM_STRIPS; ++s) z[j][s] = b;
@@ -195,7 +182,7 @@ __device__ __forceinline__ void icm_body(const IcmArgs& a) {
         float v = 0.f;
 #pragma unroll
         for (int j = 0; j < OPW; ++j) {
-          const atp_f4 d = z[j][s] - (p < P ? rh_ldf4(next32 + (size_t)p * K + 16 * (wave + ICM_WAVES * j) + 4 * lq) : zero4);
+          const atp_f4 d = z[j][s] - (p < P ? mt_ldf4(next32 + (size_t)p * K + 16 * (wave + ICM_WAVES * j) + 4 * lq) : zero4);
           v += atp_sum4(d * d);
         }
         v = atp_row_sum(v);
@@ -207,7 +194,8 @@ __device__ __forceinline__ void icm_body(const IcmArgs& a) {
       const int r = lane, p = row0 + r;
       const float* L = lg + r * ICM_LS;
       for (int g = wave; g < G; g += ICM_WAVES) {
-        const int off = (int)((a.group_off >> (8 * g)) & 255u), n = (int)((a.group_n >> (4 * g)) & 15u) + 1;
+        const MtGroup gr = mt_group(a.group_off, a.group_n, g);
+        const int off = gr.off, n = gr.n;
         float m = L[off];
         for (int j = 1; j < n; ++j) m = fmaxf(m, L[off + j]);
         float sum = 0.f;
@@ -219,8 +207,7 @@ __device__ __forceinline__ void icm_body(const IcmArgs& a) {
 
     // ---- phase 3
     if (tid < ICM_ROWS && row0 + tid < P) {
-      const float* q = part + tid;
-      a.curiosity[(size_t)t * P + row0 + tid] = (((q[0] + q[ICM_ROWS]) + q[2 * ICM_ROWS]) + q[3 * ICM_ROWS]) * (1.0f / K);
+      a.curiosity[(size_t)t * P + row0 + tid] = mt_wave_sum4(part + tid, ICM_ROWS) * (1.0f / K);
     }
     // (no barrier here: what the next step writes first - the tile `cur`, acts - was last read before the barrier above; part, hb and lg
     // are written behind the next step's first barrier)
@@ -320,32 +307,22 @@ extern "C" int dynenv_icm_losses(const float* features_dev, const float* actions
     return fail(DYNENV_ERR_ARG, "icm losses: the forward and the inverse net have all seven of their pointers");
   if (T < 1 || P < 1 || K < 1) return fail(DYNENV_ERR_ARG, "icm losses: bad shape");
   if (G < 1 || G > DYNENV_POLICY_MAX_GROUPS) return fail(DYNENV_ERR_ARG, "icm losses: G is 1..8");
-  int N = 0;
-  unsigned long long group_off = 0;
-  unsigned group_n = 0;
-  for (int g = 0; g < G; ++g) {
-    if (nvec[g] < 1 || nvec[g] > 16) return fail(DYNENV_ERR_ARG, "icm losses: a group has 1..16 actions");
-    group_off |= (unsigned long long)N << (8 * g);
-    group_n |= (unsigned)(nvec[g] - 1) << (4 * g);
-    N += nvec[g];
-  }
-  if (N > DYNENV_POLICY_ROWS) return fail(DYNENV_ERR_ARG, "icm losses: N is at most 32");
-  if (action_cols < G || action_cols > 8) return fail(DYNENV_ERR_ARG, "icm losses: action_cols is G..8");
-  if (w_dtype < DYNENV_ARR_F32 || w_dtype > DYNENV_ARR_F16) return fail(DYNENV_ERR_ARG, "icm losses: unknown dtype (DYNENV_ARR_BF16 or _F16)");
-  const void* aligned[] = {features_dev, actions_dev, finished_dev, curiosity_dev, inverse_ce_dev, w->fwd_w1, w->fwd_w1_act, w->fwd_b1, w->fwd_w2,
-                           w->fwd_b2, w->inv_w, w->inv_b};
-  for (const void* q : aligned)
-    if ((uintptr_t)q % 16) return fail(DYNENV_ERR_ARG, "icm losses: buffers must be 16-byte aligned");
+  ModelGroups gr;
+  if (int rc = model_groups("icm losses", nvec, G, action_cols, gr)) return rc;
+  if (int rc = model_operand_dtype("icm losses", w_dtype)) return rc;
+  if (int rc = model_aligned("icm losses", {features_dev, actions_dev, finished_dev, curiosity_dev, inverse_ce_dev, w->fwd_w1, w->fwd_w1_act, w->fwd_b1,
+                                            w->fwd_w2, w->fwd_b2, w->inv_w, w->inv_b}, 16))
+    return rc;
   if ((uintptr_t)losses_dev % 4 || (uintptr_t)status_dev % 4) return fail(DYNENV_ERR_ARG, "icm losses: losses_dev and status_dev are 4-byte aligned");
   if (((int64_t)T + 1) * P > (int64_t)1 << 30) return fail(DYNENV_ERR_ARG, "icm losses: (T + 1) * P too large for one launch");
-  if (w_dtype == DYNENV_ARR_F32) return fail(DYNENV_ERR_UNSUPPORTED, "icm losses: the fused layer takes bf16 or fp16 operands");
+  if (int rc = model_operand_16bit("icm losses", w_dtype, "layer")) return rc;
   if (K != 64 && K != 128 && K != 256) return fail(DYNENV_ERR_UNSUPPORTED, "icm losses: the fused layer takes K = 64, 128 or 256");
   if (int rc = have_device()) return rc;
   IcmArgs k;
   k.features = features_dev; k.actions = actions_dev;
   k.w1 = static_cast<const atp_h*>(w->fwd_w1); k.w2 = static_cast<const atp_h*>(w->fwd_w2); k.winv = static_cast<const atp_h*>(w->inv_w);
   k.w1_act = w->fwd_w1_act; k.b1 = w->fwd_b1; k.b2 = w->fwd_b2; k.binv = w->inv_b;
-  k.group_off = group_off; k.group_n = group_n;
+  k.group_off = gr.off; k.group_n = gr.n;
   k.T = T; k.P = P; k.G = G; k.AD = action_cols; k.slope = slope;
   k.curiosity = curiosity_dev; k.ce = inverse_ce_dev; k.status = status_dev;
   static decltype(&icm_64_bf16_kernel) const kernels[3][2] = {{icm_64_bf16_kernel, icm_64_f16_kernel}, {icm_128_bf16_kernel, icm_128_f16_kernel},

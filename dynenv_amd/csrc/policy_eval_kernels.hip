@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dynenv.h"
+#include "mma_tiles.h"
 
 #define PE_QS 40   // elements per LDS row of the row-major dl tile (32 logits): 16 bytes of padding
 #define PE_MAX_GRID DYNENV_POLICY_EVAL_MAX_WORKGROUPS
@@ -50,26 +51,9 @@ struct PeArgs {
   int nblocks;
 };
 
-typedef ArrBf16 PeG;   // the type of the operands that carry an upstream gradient, and of those beside them
+// the operands that carry an upstream gradient, and those beside them, are bf16: mt_split and mt_mma_split (mma_tiles.h)
 template <class CV> struct PeSplit { static constexpr bool on = false; };
 template <> struct PeSplit<ArrF16> { static constexpr bool on = true; };   // w_dtype float16: every bf16 operand of the backward's products is a pair
-
-// a = hi + lo to 16 significant bits, both bf16 (two values at once): the rounding and what it left, rounded
-__device__ __forceinline__ void pe_split(float a, float b, unsigned& hi, unsigned& lo) {
-  hi = PeG::pack(a, b);
-  const arr_f2 w = PeG::widen(hi);
-  lo = PeG::pack(a - w.x, b - w.y);
-}
-// acc + A B with the operands as pairs: (ah + al)(bh + bl) without al bl, which lies 16 bits below the product
-template <bool SPLIT>
-__device__ __forceinline__ atp_f4 pe_mma(arr_u4 ah, arr_u4 al, arr_u4 bh, arr_u4 bl, atp_f4 acc) {
-  acc = AtpMma<PeG>::mma(ah, bh, acc);
-  if constexpr (SPLIT) {
-    acc = AtpMma<PeG>::mma(ah, bl, acc);
-    acc = AtpMma<PeG>::mma(al, bh, acc);
-  }
-  return acc;
-}
 
 template <int K, class CV>
 __device__ __forceinline__ void pe_bwd_body(const PeArgs& a) {
@@ -106,7 +90,7 @@ __device__ __forceinline__ void pe_bwd_body(const PeArgs& a) {
   const bool critic = wave < CT;
   atp_f4 lnw4 = zero4, lnb4 = zero4, w24 = zero4;
   if (critic) {
-    lnw4 = rh_ldf4(a.f.ln_w + 16 * wave + 4 * lq); lnb4 = rh_ldf4(a.f.ln_b + 16 * wave + 4 * lq); w24 = rh_ldf4(a.f.w2 + 16 * wave + 4 * lq);
+    lnw4 = mt_ldf4(a.f.ln_w + 16 * wave + 4 * lq); lnb4 = mt_ldf4(a.f.ln_b + 16 * wave + 4 * lq); w24 = mt_ldf4(a.f.w2 + 16 * wave + 4 * lq);
   }
   const atp_f4 c4 = w24 * lnw4;
 
@@ -126,7 +110,8 @@ __device__ __forceinline__ void pe_bwd_body(const PeArgs& a) {
       const float* D = dp + r * PH_LS;
       bool clamped = false;
       for (int g = q; g < G; g += PH_WAVES) {
-        const int off = (int)((a.f.group_off >> (8 * g)) & 255u), n = (int)((a.f.group_n >> (4 * g)) & 15u) + 1;
+        const MtGroup gr = mt_group(a.f.group_off, a.f.group_n, g);
+        const int off = gr.off, n = gr.n;
         ph_softmax(L, off, n);
         int act = 0;
         float up = 0.f;
@@ -148,7 +133,7 @@ __device__ __forceinline__ void pe_bwd_body(const PeArgs& a) {
           const float dl = t1 + t2;
           L[off + j] = dl;
           unsigned hi16, lo16;
-          pe_split(dl, 0.f, hi16, lo16);
+          mt_split(dl, 0.f, hi16, lo16);
           dlb[r * PE_QS + off + j] = (atp_h)(hi16 & 0xffffu);
           dlt[(off + j) * TS + r] = (atp_h)(hi16 & 0xffffu);
           if constexpr (SP) {
@@ -190,32 +175,19 @@ __device__ __forceinline__ void pe_bwd_body(const PeArgs& a) {
     if (critic) {
 #pragma unroll
       for (int s = 0; s < S; ++s) {
-        const float *q1 = part + 16 * s + lr, *q2 = part2 + 16 * s + lr;
-        const float m1 = (((q1[0] + q1[PH_ROWS]) + q1[2 * PH_ROWS]) + q1[3 * PH_ROWS]) * (1.0f / H);
-        const float m2 = (((q2[0] + q2[PH_ROWS]) + q2[2 * PH_ROWS]) + q2[3 * PH_ROWS]) * (1.0f / H);
+        const float m1 = mt_wave_sum4(part + 16 * s + lr, PH_ROWS) * (1.0f / H), m2 = mt_wave_sum4(part2 + 16 * s + lr, PH_ROWS) * (1.0f / H);
         const atp_f4 u = rstd[s] * ((c4 - m1) - xh[s] * m2);
-        atp_f4 d = dv[s] * u;
-        const unsigned m = pos >> (4 * s);
-        d.x = (m & 1u) ? d.x : d.x * a.f.slope; d.y = (m & 2u) ? d.y : d.y * a.f.slope;
-        d.z = (m & 4u) ? d.z : d.z * a.f.slope; d.w = (m & 8u) ? d.w : d.w * a.f.slope;
+        const atp_f4 d = mt_leaky_grad4(dv[s] * u, pos >> (4 * s), a.f.slope);
         db1 += d;
         dlnw += dv[s] * (w24 * xh[s]);
         dlnb += dv[s] * w24;
         dw2 += dv[s] * (xh[s] * lnw4 + lnb4);
         const int r = 16 * s + lr;
         unsigned lo, hi, llo, lhi;
-        pe_split(d.x, d.y, lo, llo);
-        pe_split(d.z, d.w, hi, lhi);
-        const atp_u2 w = {lo, hi};
-        *reinterpret_cast<atp_u2*>(dhb + r * HS + 16 * wave + 4 * lq) = w;
-        atp_h* t = dht + (16 * wave + 4 * lq) * TS + r;
-        t[0] = (atp_h)(lo & 0xffffu); t[TS] = (atp_h)(lo >> 16); t[2 * TS] = (atp_h)(hi & 0xffffu); t[3 * TS] = (atp_h)(hi >> 16);
-        if constexpr (SP) {
-          const atp_u2 wl = {llo, lhi};
-          *reinterpret_cast<atp_u2*>(dhbl + r * HS + 16 * wave + 4 * lq) = wl;
-          atp_h* u = dhtl + (16 * wave + 4 * lq) * TS + r;
-          u[0] = (atp_h)(llo & 0xffffu); u[TS] = (atp_h)(llo >> 16); u[2 * TS] = (atp_h)(lhi & 0xffffu); u[3 * TS] = (atp_h)(lhi >> 16);
-        }
+        mt_split(d.x, d.y, lo, llo);
+        mt_split(d.z, d.w, hi, lhi);
+        mt_st_both<TS>(dhb + r * HS + 16 * wave + 4 * lq, dht + (16 * wave + 4 * lq) * TS, r, lo, hi);
+        if constexpr (SP) mt_st_both<TS>(dhbl + r * HS + 16 * wave + 4 * lq, dhtl + (16 * wave + 4 * lq) * TS, r, llo, lhi);
       }
     }
 #pragma unroll
@@ -240,11 +212,11 @@ __device__ __forceinline__ void pe_bwd_body(const PeArgs& a) {
 #pragma unroll
       for (int s = 0; s < S; ++s) {
         const int at = (16 * s + lr) * PE_QS + 8 * lq;
-        atp_f4 acc = pe_mma<SP>(wa, wal, atp_ld16(dlb + at), atp_ld16(dlbl + LO * at), zero4);
+        atp_f4 acc = mt_mma_split<SP>(wa, wal, atp_ld16(dlb + at), atp_ld16(dlbl + LO * at), zero4);
 #pragma unroll
         for (int ks = 0; ks < HKS; ++ks) {
           const int ah = (16 * s + lr) * HS + 32 * ks + 8 * lq;
-          acc = pe_mma<SP>(w1f[ks], w1l[ks], atp_ld16(dhb + ah), atp_ld16(dhbl + LO * ah), acc);
+          acc = mt_mma_split<SP>(w1f[ks], w1l[ks], atp_ld16(dhb + ah), atp_ld16(dhbl + LO * ah), acc);
         }
         const int p = row0 + 16 * s + lr;
         if (a.dfeat && p < R) *reinterpret_cast<atp_f4*>(a.dfeat + (size_t)p * K + 16 * kt + 4 * lq) = acc + zero4;   // (+ 0: no -0 leaves)
@@ -265,14 +237,14 @@ __device__ __forceinline__ void pe_bwd_body(const PeArgs& a) {
         const int at = (16 * h + lr) * TS + 32 * ks + 8 * lq;
         const arr_u4 df = atp_ld16(dlt + at), dl2 = atp_ld16(dltl + LO * at);
 #pragma unroll
-        for (int j = 0; j < OPW; ++j) gA[j][h] = pe_mma<SP>(xf[j], xl[j], df, dl2, gA[j][h]);
+        for (int j = 0; j < OPW; ++j) gA[j][h] = mt_mma_split<SP>(xf[j], xl[j], df, dl2, gA[j][h]);
       }
 #pragma unroll
       for (int c = 0; c < CT; ++c) {
         const int at = (16 * c + lr) * TS + 32 * ks + 8 * lq;
         const arr_u4 df = atp_ld16(dht + at), dh2 = atp_ld16(dhtl + LO * at);
 #pragma unroll
-        for (int j = 0; j < OPW; ++j) gC[j][c] = pe_mma<SP>(xf[j], xl[j], df, dh2, gC[j][c]);
+        for (int j = 0; j < OPW; ++j) gC[j][c] = mt_mma_split<SP>(xf[j], xl[j], df, dh2, gC[j][c]);
       }
     }
     __syncthreads();   // the next block's phase 0 overwrites the tiles
@@ -289,16 +261,14 @@ __device__ __forceinline__ void pe_bwd_body(const PeArgs& a) {
     for (int c = 0; c < CT; ++c) *reinterpret_cast<atp_f4*>(out + pe_off_w1(K) + (16 * c + lr) * K + 16 * kt + 4 * lq) = gC[j][c];
   }
   {
-    const atp_f4 s1 = icb_sum16(db1), s2 = icb_sum16(dlnw), s3 = icb_sum16(dlnb), s4 = icb_sum16(dw2);
+    const atp_f4 s1 = mt_sum16(db1), s2 = mt_sum16(dlnw), s3 = mt_sum16(dlnb), s4 = mt_sum16(dw2);
     if (critic && lr == 0) {
       *reinterpret_cast<atp_f4*>(out + pe_off_b1(K) + 16 * wave + 4 * lq) = s1;
       *reinterpret_cast<atp_f4*>(out + pe_off_lnw(K) + 16 * wave + 4 * lq) = s2;
       *reinterpret_cast<atp_f4*>(out + pe_off_lnb(K) + 16 * wave + 4 * lq) = s3;
       *reinterpret_cast<atp_f4*>(out + pe_off_w2(K) + 16 * wave + 4 * lq) = s4;
     }
-    float v = db2;   // over the rows of a strip: the 16 lanes of equal lane >> 4, in one fixed order
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, 64);
+    const float v = mt_sum16(db2);
     if (tid < 4) out[pe_off_b2(K) + tid] = tid == 0 ? v : 0.f;
   }
   if (tid < 32) out[pe_off_ab(K) + tid] = dab;
@@ -352,29 +322,19 @@ static int pe_common(const char* who, const float* features_dev, const float* ac
     return say(DYNENV_ERR_ARG, "the actor and the critic have all eight of their pointers");
   if (T < 1 || P < 1 || K < 1) return say(DYNENV_ERR_ARG, "bad shape");
   if (G < 1 || G > DYNENV_POLICY_MAX_GROUPS) return say(DYNENV_ERR_ARG, "G is 1..8");
-  int N = 0;
-  unsigned long long group_off = 0;
-  unsigned group_n = 0;
-  for (int g = 0; g < G; ++g) {
-    if (nvec[g] < 1 || nvec[g] > 16) return say(DYNENV_ERR_ARG, "a group has 1..16 actions");
-    group_off |= (unsigned long long)N << (8 * g);
-    group_n |= (unsigned)(nvec[g] - 1) << (4 * g);
-    N += nvec[g];
-  }
-  if (N > DYNENV_POLICY_ROWS) return say(DYNENV_ERR_ARG, "N is at most 32");
-  if (action_cols < G || action_cols > 8) return say(DYNENV_ERR_ARG, "action_cols is G..8");
-  if (w_dtype < DYNENV_ARR_F32 || w_dtype > DYNENV_ARR_F16) return say(DYNENV_ERR_ARG, "unknown dtype (DYNENV_ARR_BF16 or _F16)");
-  const void* aligned[] = {features_dev, actions_dev, w->actor_w, w->actor_b, w->critic_w1, w->critic_b1, w->critic_ln_w, w->critic_ln_b, w->critic_w2};
-  for (const void* q : aligned)
-    if ((uintptr_t)q % 16) return say(DYNENV_ERR_ARG, "buffers must be 16-byte aligned");
+  ModelGroups gr;
+  if (int rc = model_groups(who, nvec, G, action_cols, gr)) return rc;
+  if (int rc = model_operand_dtype(who, w_dtype)) return rc;
+  if (int rc = model_aligned(who, {features_dev, actions_dev, w->actor_w, w->actor_b, w->critic_w1, w->critic_b1, w->critic_ln_w, w->critic_ln_b, w->critic_w2}, 16))
+    return rc;
   if ((uintptr_t)w->critic_b2 % 4 || (uintptr_t)status_dev % 4) return say(DYNENV_ERR_ARG, "critic_b2 and status_dev are 4-byte aligned");
   if ((int64_t)T * P > (int64_t)1 << 30) return say(DYNENV_ERR_ARG, "T * P too large for one launch");
   k = PhArgs{};
   k.feat0 = features_dev; k.feat1 = nullptr;
   k.actor_w = static_cast<const atp_h*>(w->actor_w); k.w1 = static_cast<const atp_h*>(w->critic_w1);
   k.actor_b = w->actor_b; k.b1 = w->critic_b1; k.ln_w = w->critic_ln_w; k.ln_b = w->critic_ln_b; k.w2 = w->critic_w2; k.b2 = w->critic_b2;
-  k.group_off = group_off; k.group_n = group_n;
-  k.P = T * P; k.G = G; k.N = N; k.C = 0; k.AD = action_cols;
+  k.group_off = gr.off; k.group_n = gr.n;
+  k.P = T * P; k.G = G; k.N = gr.N; k.C = 0; k.AD = action_cols;
   k.slope = slope; k.eps = ln_eps;
   k.ev_actions = actions_dev; k.ev_P = P; k.status = status_dev;
   return 0;
@@ -386,8 +346,8 @@ extern "C" int dynenv_policy_eval(const float* features_dev, const float* action
   PhArgs k;
   if (!logp_dev || !value_dev) return fail(DYNENV_ERR_ARG, "policy eval: null argument");
   if (int rc = pe_common("policy eval", features_dev, actions_dev, T, P, K, w_dtype, w, nvec, G, action_cols, slope, ln_eps, status_dev, k)) return rc;
-  if ((uintptr_t)logp_dev % 16 || (uintptr_t)probs_dev % 16 || (uintptr_t)value_dev % 16) return fail(DYNENV_ERR_ARG, "policy eval: buffers must be 16-byte aligned");
-  if (w_dtype == DYNENV_ARR_F32) return fail(DYNENV_ERR_UNSUPPORTED, "policy eval: the fused layer takes bf16 or fp16 operands");
+  if (int rc = model_aligned("policy eval", {logp_dev, probs_dev, value_dev}, 16)) return rc;
+  if (int rc = model_operand_16bit("policy eval", w_dtype, "layer")) return rc;
   if (K != 64 && K != 128) return fail(DYNENV_ERR_UNSUPPORTED, "policy eval: the fused layer takes K = 64 or 128");
   if (int rc = have_device()) return rc;
   k.logp = logp_dev; k.probs = probs_dev; k.value = value_dev;
@@ -419,15 +379,15 @@ extern "C" int dynenv_policy_eval_backward(const float* features_dev, const floa
   if (!grad->d_actor_w || !grad->d_actor_b || !grad->d_critic_w1 || !grad->d_critic_b1 || !grad->d_critic_ln_w || !grad->d_critic_ln_b || !grad->d_critic_w2 ||
       !grad->d_critic_b2)
     return fail(DYNENV_ERR_ARG, "policy eval backward: the eight gradients have their pointers");
-  const void* aligned[] = {d_logp_dev, d_probs_dev, d_value_dev, d_features_dev, workspace_dev, wt->actor_w_t, wt->critic_w1_t, wt->actor_w_t_lo, wt->critic_w1_t_lo, grad->d_actor_w, grad->d_actor_b,
-                           grad->d_critic_w1, grad->d_critic_b1, grad->d_critic_ln_w, grad->d_critic_ln_b, grad->d_critic_w2};
-  for (const void* q : aligned)
-    if ((uintptr_t)q % 16) return fail(DYNENV_ERR_ARG, "policy eval backward: buffers must be 16-byte aligned");
+  if (int rc = model_aligned("policy eval backward", {d_logp_dev, d_probs_dev, d_value_dev, d_features_dev, workspace_dev, wt->actor_w_t, wt->critic_w1_t,
+                                                      wt->actor_w_t_lo, wt->critic_w1_t_lo, grad->d_actor_w, grad->d_actor_b, grad->d_critic_w1,
+                                                      grad->d_critic_b1, grad->d_critic_ln_w, grad->d_critic_ln_b, grad->d_critic_w2}, 16))
+    return rc;
   if ((uintptr_t)grad->d_critic_b2 % 4) return fail(DYNENV_ERR_ARG, "policy eval backward: d_critic_b2 is 4-byte aligned");
   const int groups = pe_groups((int64_t)T * P);
   if ((K == 64 || K == 128) && workspace_bytes < (uint64_t)groups * (uint64_t)pe_part(K) * 4u)
     return fail(DYNENV_ERR_ARG, "policy eval backward: the workspace is smaller than dynenv_policy_eval_backward_workspace asks for");
-  if (w_dtype == DYNENV_ARR_F32) return fail(DYNENV_ERR_UNSUPPORTED, "policy eval backward: the fused backward takes bf16 or fp16 operands");
+  if (int rc = model_operand_16bit("policy eval backward", w_dtype, "backward")) return rc;
   if (K != 64 && K != 128) return fail(DYNENV_ERR_UNSUPPORTED, "policy eval backward: the fused backward takes K = 64 or 128");
   if (int rc = have_device()) return rc;
   k.d_logp = d_logp_dev; k.d_probs = d_probs_dev; k.d_value = d_value_dev;

@@ -10,8 +10,8 @@
 //   value = LayerNorm(leaky(cat W1^T + b1)) . w2 + b2
 //   u_g from Philox4x32-10 keyed by (seed; row_base + p, draw, purpose + g / 4);  action_g = #{j < n_g - 1: c_j <= u_g c_{n-1}}
 //
-// Work.  One workgroup of four waves per PH_ROWS = 64 rows = four strips of 16, recurrent_kernels.hip's shape: 16x16x32 MFMAs with
-// float32 accumulators in the orientation D^T = W X^T, so that a lane's accumulator holds four consecutive outputs of one row.  The
+// Work.  One workgroup of four waves per PH_ROWS = 64 rows = four strips of 16, recurrent_kernels.hip's shape, on the tile toolkit
+// (mma_tiles.h; DESIGN.md, "The tile toolkit"): a lane's accumulator holds four consecutive outputs of one row.  The
 // output tiles of 16 - K / 32 of the critic's Layer1, then the two of the actor - are dealt to the waves round robin (tile = wave +
 // 4 t); a wave computes its tiles for ALL FOUR strips, so every weight fragment it fetches (16 contiguous bytes per lane, from L2)
 // feeds four MFMAs and the workgroup streams the weights once per 64 rows.  The B operands come from the 64 rows in LDS, 16 bit wide.
@@ -27,15 +27,13 @@
 #include <stdint.h>
 #include "dynenv.h"
 #include "dynenv_math.h"
+#include "mma_tiles.h"
 
 #define PH_BLOCK 256
 #define PH_WAVES (PH_BLOCK / 64)
 #define PH_STRIPS 4
 #define PH_ROWS (16 * PH_STRIPS)
 #define PH_LS 33   // floats per LDS row of the 32 actor outputs: a lane per row reads without bank conflicts
-
-// arr_u4, ArrBf16, ArrF16: arranger_cols_kernels.hip's.  atp_h, atp_f4, AtpMma, atp_ld16, atp_st4, atp_row_sum, atp_sum4: attention_kernels.hip's.
-// rh_ldf4, rh_sigmoid: recurrent_kernels.hip's.
 
 struct PhArgs {   // dynenv_policy_t by value, the outputs and the sizes
   const float *feat0, *feat1;
@@ -80,17 +78,16 @@ __device__ __forceinline__ void ph_forward(const PhArgs& a, int row0, atp_h* xb,
   for (int i = tid; i < PH_ROWS * (K / 4); i += PH_BLOCK) {
     const int r = i / (K / 4), col = 4 * (i % (K / 4)), p = row0 + r;
     atp_f4 v = zero4;
-    if (p < P) v = col < F ? rh_ldf4(a.feat0 + (size_t)p * F + col) : rh_ldf4(a.feat1 + (size_t)p * F + (col - F));
+    if (p < P) v = col < F ? mt_ldf4(a.feat0 + (size_t)p * F + col) : mt_ldf4(a.feat1 + (size_t)p * F + (col - F));
     atp_st4<CV>(xb + r * XS + col, v);
     if constexpr (TR) {
       const unsigned lo = ArrBf16::pack(v.x, v.y), hi = ArrBf16::pack(v.z, v.w);
-      atp_h* t = xt + col * PH_TS + r;
-      t[0] = (atp_h)(lo & 0xffffu); t[PH_TS] = (atp_h)(lo >> 16); t[2 * PH_TS] = (atp_h)(hi & 0xffffu); t[3 * PH_TS] = (atp_h)(hi >> 16);
-      if (xtl) {   // what the rounding to bf16 left, rounded to bf16: xt + xtl holds 16 significant bits of the row
+      mt_st_tr<PH_TS>(xt + col * PH_TS + r, lo, hi);
+      if (xtl) {   // what the rounding to bf16 left, rounded to bf16: xt + xtl holds 16 significant bits of the row (mt_split's arithmetic,
+                   // written out: with two calls of it the float16 backward kernels are scheduled differently)
         const arr_f2 w0 = ArrBf16::widen(lo), w1 = ArrBf16::widen(hi);
         const unsigned l0 = ArrBf16::pack(v.x - w0.x, v.y - w0.y), l1 = ArrBf16::pack(v.z - w1.x, v.w - w1.y);
-        atp_h* u = xtl + col * PH_TS + r;
-        u[0] = (atp_h)(l0 & 0xffffu); u[PH_TS] = (atp_h)(l0 >> 16); u[2 * PH_TS] = (atp_h)(l1 & 0xffffu); u[3 * PH_TS] = (atp_h)(l1 >> 16);
+        mt_st_tr<PH_TS>(xtl + col * PH_TS + r, l0, l1);
       }
     }
   }
@@ -104,10 +101,10 @@ __device__ __forceinline__ void ph_forward(const PhArgs& a, int row0, atp_h* xb,
     atp_f4 b = zero4;
     wrow[t] = a.w1;
     if (tile < CT) {
-      b = rh_ldf4(a.b1 + 16 * tile + 4 * lq);
+      b = mt_ldf4(a.b1 + 16 * tile + 4 * lq);
       wrow[t] = a.w1 + (size_t)(16 * tile + lr) * K;
     } else if (tile < T) {
-      b = rh_ldf4(a.actor_b + 16 * (tile - CT) + 4 * lq);
+      b = mt_ldf4(a.actor_b + 16 * (tile - CT) + 4 * lq);
       wrow[t] = a.actor_w + (size_t)(16 * (tile - CT) + lr) * K;
     }
 #pragma unroll
@@ -133,18 +130,12 @@ __device__ __forceinline__ void ph_forward(const PhArgs& a, int row0, atp_h* xb,
     if (tile < CT) {
 #pragma unroll
       for (int s = 0; s < PH_STRIPS; ++s) {
-        atp_f4& v = y[t][s];
-        if constexpr (TR)
-          pos |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u)) << (4 * (t * PH_STRIPS + s));
-        v.x = v.x > 0.f ? v.x : v.x * a.slope; v.y = v.y > 0.f ? v.y : v.y * a.slope;
-        v.z = v.z > 0.f ? v.z : v.z * a.slope; v.w = v.w > 0.f ? v.w : v.w * a.slope;
+        if constexpr (TR) pos |= mt_pos4(y[t][s]) << (4 * (t * PH_STRIPS + s));
+        y[t][s] = mt_leaky4(y[t][s], a.slope);
       }
     } else if (tile < T) {
 #pragma unroll
-      for (int s = 0; s < PH_STRIPS; ++s) {
-        float* q = lg + (16 * s + lr) * PH_LS + 16 * (tile - CT) + 4 * lq;
-        q[0] = y[t][s].x; q[1] = y[t][s].y; q[2] = y[t][s].z; q[3] = y[t][s].w;
-      }
+      for (int s = 0; s < PH_STRIPS; ++s) mt_st_f4(lg + (16 * s + lr) * PH_LS + 16 * (tile - CT) + 4 * lq, y[t][s]);
     }
   }
   // torch's LayerNorm (biased variance, two passes) over the H critic features of a row, which lie in up to four waves, and the dot
@@ -162,7 +153,7 @@ __device__ __forceinline__ void ph_forward(const PhArgs& a, int row0, atp_h* xb,
 #pragma unroll
   for (int s = 0; s < PH_STRIPS; ++s) {
     const float* q = part + 16 * s + lr;
-    mean[s] = (((q[0] + q[PH_ROWS]) + q[2 * PH_ROWS]) + q[3 * PH_ROWS]) * (1.0f / H);
+    mean[s] = mt_wave_sum4(q, PH_ROWS) * (1.0f / H);
   }
   float* part2 = part + PH_WAVES * PH_ROWS;
 #pragma unroll
@@ -178,7 +169,7 @@ __device__ __forceinline__ void ph_forward(const PhArgs& a, int row0, atp_h* xb,
 #pragma unroll
   for (int s = 0; s < PH_STRIPS; ++s) {
     const float* q = part2 + 16 * s + lr;
-    rstd[s] = 1.0f / sqrtf((((q[0] + q[PH_ROWS]) + q[2 * PH_ROWS]) + q[3 * PH_ROWS]) * (1.0f / H) + a.eps);
+    rstd[s] = 1.0f / sqrtf(mt_wave_sum4(q, PH_ROWS) * (1.0f / H) + a.eps);
   }
   float* part3 = part + 2 * PH_WAVES * PH_ROWS;
   {
@@ -187,7 +178,7 @@ __device__ __forceinline__ void ph_forward(const PhArgs& a, int row0, atp_h* xb,
     for (int t = 0; t < TPW; ++t) {
       const int tile = wave + PH_WAVES * t;
       if (tile < CT) {
-        const atp_f4 g = rh_ldf4(a.ln_w + 16 * tile + 4 * lq), b = rh_ldf4(a.ln_b + 16 * tile + 4 * lq), w2 = rh_ldf4(a.w2 + 16 * tile + 4 * lq);
+        const atp_f4 g = mt_ldf4(a.ln_w + 16 * tile + 4 * lq), b = mt_ldf4(a.ln_b + 16 * tile + 4 * lq), w2 = mt_ldf4(a.w2 + 16 * tile + 4 * lq);
 #pragma unroll
         for (int s = 0; s < PH_STRIPS; ++s) dot[s] += atp_sum4(((y[t][s] - mean[s]) * rstd[s] * g + b) * w2);
       }
@@ -220,13 +211,10 @@ __device__ __forceinline__ float ph_softmax(float* L, int off, int n) {
   return last;
 }
 
-// a stored action of group g (n_g - 1 = last) for row p = t ev_P + pp: rounded to the nearest integer and clamped into the group
+// the stored action of group g (n_g - 1 = last) for row p = t ev_P + pp
 __device__ __forceinline__ int ph_stored_action(const PhArgs& a, int p, int g, int last, bool& clamped) {
   const int t = p / a.ev_P, pp = p - t * a.ev_P;
-  const float v = rintf(a.ev_actions[((size_t)t * a.AD + g) * a.ev_P + pp]);
-  const bool ok = v >= 0.f && v <= (float)last;
-  clamped |= !ok;
-  return ok ? (int)v : v > (float)last ? last : 0;
+  return mt_stored_action(a.ev_actions[((size_t)t * a.AD + g) * a.ev_P + pp], last, clamped);
 }
 
 // EVAL: dynenv_policy_eval - the stored action in place of the draw, log_probs in the storage's layout [T][G][ev_P], probs optional,
@@ -247,7 +235,7 @@ __device__ __forceinline__ void ph_body(const PhArgs& a) {
   ph_forward<K, CV, false>(a, row0, xb, nullptr, nullptr, lg, part, y, mean, rstd, pos);
   if (tid < PH_ROWS && row0 + tid < P) {
     const float* q = part + 2 * PH_WAVES * PH_ROWS + tid;
-    a.value[row0 + tid] = (((q[0] + q[PH_ROWS]) + q[2 * PH_ROWS]) + q[3 * PH_ROWS]) + a.b2[0];
+    a.value[row0 + tid] = mt_wave_sum4(q, PH_ROWS) + a.b2[0];
   }
 
   // ---- phase 2: row r's groups g = q, q + 4 and its Box output c = q, by thread (r, q); q is the wave, so a group's size is uniform
@@ -257,7 +245,8 @@ __device__ __forceinline__ void ph_body(const PhArgs& a) {
     const unsigned long long draw = !EVAL && a.draw ? a.draw[0] : 0ull, row = a.row_base + (unsigned long long)p;
     bool clamped = false;
     for (int g = q; g < a.G; g += PH_WAVES) {
-      const int off = (int)((a.group_off >> (8 * g)) & 255u), n = (int)((a.group_n >> (4 * g)) & 15u) + 1;
+      const MtGroup gr = mt_group(a.group_off, a.group_n, g);
+      const int off = gr.off, n = gr.n;
       const float last = ph_softmax(L, off, n);   // c_{n-1}
       int act = 0;
       if constexpr (EVAL) {
@@ -288,7 +277,7 @@ __device__ __forceinline__ void ph_body(const PhArgs& a) {
     }
     if (EVAL && clamped && a.status) atomicOr(a.status, 1);
     if (!EVAL && q < a.C && p < P) {
-      const float v = (rh_sigmoid(L[a.N + q]) - 0.5f) * a.cont_scale[q] + a.cont_mean[q];
+      const float v = (mt_sigmoid(L[a.N + q]) - 0.5f) * a.cont_scale[q] + a.cont_mean[q];
       a.cont[(size_t)p * a.C + q] = (double)v;
     }
   }
@@ -341,28 +330,18 @@ extern "C" int dynenv_policy_head(const float* feat0_dev, const float* feat1_dev
     return fail(DYNENV_ERR_ARG, "policy head: the actor and the critic have all eight of their pointers");
   if (E < 1 || A < 1 || F < 1) return fail(DYNENV_ERR_ARG, "policy head: bad shape");
   if (G < 1 || G > DYNENV_POLICY_MAX_GROUPS || C < 0 || C > DYNENV_POLICY_MAX_CONT) return fail(DYNENV_ERR_ARG, "policy head: G is 1..8 and C 0..4");
-  int N = 0;
-  unsigned long long group_off = 0;
-  unsigned group_n = 0;
-  for (int g = 0; g < G; ++g) {
-    if (nvec[g] < 1 || nvec[g] > 16) return fail(DYNENV_ERR_ARG, "policy head: a group has 1..16 actions");
-    group_off |= (unsigned long long)N << (8 * g);
-    group_n |= (unsigned)(nvec[g] - 1) << (4 * g);
-    N += nvec[g];
-  }
-  if (N + C > DYNENV_POLICY_ROWS) return fail(DYNENV_ERR_ARG, "policy head: N + C is at most 32");
-  if (action_cols < G || action_cols > 8) return fail(DYNENV_ERR_ARG, "policy head: action_cols is G..8");
+  ModelGroups gr;
+  if (int rc = model_groups("policy head", nvec, G, action_cols, gr, C)) return rc;
   if ((C > 0) != (cont_dev != nullptr)) return fail(DYNENV_ERR_ARG, "policy head: cont_dev is NULL exactly when C == 0");
   if (C > 0 && (!w->cont_scale || !w->cont_mean)) return fail(DYNENV_ERR_ARG, "policy head: C > 0 takes cont_scale and cont_mean");
-  if (w_dtype < DYNENV_ARR_F32 || w_dtype > DYNENV_ARR_F16) return fail(DYNENV_ERR_ARG, "policy head: unknown dtype (DYNENV_ARR_BF16 or _F16)");
-  const void* aligned[] = {feat0_dev, feat1_dev, w->actor_w, w->actor_b, w->critic_w1, w->critic_b1, w->critic_ln_w, w->critic_ln_b, w->critic_w2,
-                           actions_dev, cont_dev, probs_dev, logp_dev, value_dev, next_ext_dev};
-  for (const void* q : aligned)
-    if ((uintptr_t)q % 16) return fail(DYNENV_ERR_ARG, "policy head: buffers must be 16-byte aligned");
+  if (int rc = model_operand_dtype("policy head", w_dtype)) return rc;
+  if (int rc = model_aligned("policy head", {feat0_dev, feat1_dev, w->actor_w, w->actor_b, w->critic_w1, w->critic_b1, w->critic_ln_w, w->critic_ln_b,
+                                             w->critic_w2, actions_dev, cont_dev, probs_dev, logp_dev, value_dev, next_ext_dev}, 16))
+    return rc;
   if ((uintptr_t)w->critic_b2 % 4 || (uintptr_t)w->cont_scale % 4 || (uintptr_t)w->cont_mean % 4 || (uintptr_t)draw_dev % 8)
     return fail(DYNENV_ERR_ARG, "policy head: critic_b2, cont_scale and cont_mean are 4-byte, draw_dev 8-byte aligned");
   if ((int64_t)E * A > (int64_t)1 << 30) return fail(DYNENV_ERR_ARG, "policy head: E * A too large for one launch");
-  if (w_dtype == DYNENV_ARR_F32) return fail(DYNENV_ERR_UNSUPPORTED, "policy head: the fused layer takes bf16 or fp16 operands");
+  if (int rc = model_operand_16bit("policy head", w_dtype, "layer")) return rc;
   if (F != 64 && F != 128) return fail(DYNENV_ERR_UNSUPPORTED, "policy head: the fused layer takes F = 64 or 128");
   if (int rc = have_device()) return rc;
   PhArgs k;
@@ -370,8 +349,8 @@ extern "C" int dynenv_policy_head(const float* feat0_dev, const float* feat1_dev
   k.actor_w = static_cast<const atp_h*>(w->actor_w); k.w1 = static_cast<const atp_h*>(w->critic_w1);
   k.actor_b = w->actor_b; k.cont_scale = w->cont_scale; k.cont_mean = w->cont_mean; k.b1 = w->critic_b1; k.ln_w = w->critic_ln_w;
   k.ln_b = w->critic_ln_b; k.w2 = w->critic_w2; k.b2 = w->critic_b2;
-  k.draw = reinterpret_cast<const unsigned long long*>(draw_dev); k.seed = seed; k.row_base = row_base; k.group_off = group_off; k.group_n = group_n;
-  k.P = E * A; k.G = G; k.N = N; k.C = C; k.AD = action_cols; k.discrete_turn = discrete_turn != 0;
+  k.draw = reinterpret_cast<const unsigned long long*>(draw_dev); k.seed = seed; k.row_base = row_base; k.group_off = gr.off; k.group_n = gr.n;
+  k.P = E * A; k.G = G; k.N = gr.N; k.C = C; k.AD = action_cols; k.discrete_turn = discrete_turn != 0;
   k.slope = slope; k.eps = ln_eps;
   k.actions = actions_dev; k.cont = cont_dev; k.probs = probs_dev; k.logp = logp_dev; k.value = value_dev; k.next_ext = next_ext_dev;
   k.ev_actions = nullptr; k.ev_P = 0; k.status = nullptr;

@@ -9,11 +9,10 @@
 //   h, c = +0.0 WITHOUT being read where reset_env[p / A] != 0, else read
 //   g = x W_ih^T + b_ih + h W_hh^T + b_hh;  c' = sigmoid(g_f) c + sigmoid(g_i) tanh(g_g);  h' = sigmoid(g_o) tanh(c');  out = LayerNorm(h')
 //
-// Work.  One workgroup of four waves per RH_ROWS = 64 rows = four strips of 16.  The products are attention_kernels.hip's: 16x16x32
-// MFMAs with float32 accumulators in the orientation D^T = W X^T - 16 weight rows the A operand, fetched from global memory (L2) as 16
-// contiguous bytes per lane, 16 rows of the batch the B operand - so that a lane's accumulator holds four consecutive features of one
-// row.  WEIGHT SHARING: a wave owns a quarter of the feature tiles (F / 64 tiles of 16 features) and ALL FOUR strips of the workgroup:
-// every weight fragment it fetches feeds four MFMAs, one per strip, whose B operands (the 64 rows' x and h, 16 bit wide) it holds in
+// Work.  One workgroup of four waves per RH_ROWS = 64 rows = four strips of 16.  The products are the tile toolkit's (mma_tiles.h;
+// DESIGN.md, "The tile toolkit"): the weight rows, fetched from global memory (L2), are the A operand, and a lane's accumulator holds
+// four consecutive features of one row.  WEIGHT SHARING: a wave owns a quarter of the feature tiles (F / 64 tiles of 16 features) and
+// ALL FOUR strips of the workgroup: every weight fragment it fetches feeds four MFMAs, one per strip, whose B operands (the 64 rows' x and h, 16 bit wide) it holds in
 // registers.  A workgroup therefore streams the weights once per 64 rows, and no weight element is fetched by two waves of it.  For one
 // feature tile the wave holds the four gates i, f, g, o of those features of all 64 rows (16 accumulators), so the cell is evaluated in
 // place; c of those features was loaded before anything was written.
@@ -27,21 +26,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dynenv.h"
+#include "mma_tiles.h"
 
 #define RH_BLOCK 256
 #define RH_WAVES (RH_BLOCK / 64)
 #define RH_STRIPS 4
 #define RH_ROWS (16 * RH_STRIPS)
 
-// arr_u4, ArrBf16, ArrF16: arranger_cols_kernels.hip's.  atp_h, atp_f4, AtpMma, atp_ld16, atp_st4, atp_row_sum, atp_sum4: attention_kernels.hip's.
-
 struct RhW {   // dynenv_rhead_t by value
   const atp_h *tr_w, *w_ih, *w_hh;
   const float *tr_b, *tr_ln_w, *tr_ln_b, *b_ih, *b_hh, *ln_w, *ln_b;
 };
-
-__device__ __forceinline__ float rh_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
-__device__ __forceinline__ atp_f4 rh_ldf4(const float* p) { return *reinterpret_cast<const atp_f4*>(p); }
 
 // torch's LayerNorm (biased variance, two passes) of the rows whose features y[tile][strip] are spread over the four waves; part: [2][RH_WAVES][RH_ROWS]
 template <int F, int TPW>
@@ -60,7 +55,7 @@ __device__ __forceinline__ void rh_layer_norm(atp_f4 (&y)[TPW][RH_STRIPS], float
 #pragma unroll
   for (int s = 0; s < RH_STRIPS; ++s) {
     const float* q = part + 16 * s + lr;
-    mean[s] = (((q[0] + q[RH_ROWS]) + q[2 * RH_ROWS]) + q[3 * RH_ROWS]) * (1.0f / F);
+    mean[s] = mt_wave_sum4(q, RH_ROWS) * (1.0f / F);
   }
   float* part2 = part + RH_WAVES * RH_ROWS;
 #pragma unroll
@@ -75,11 +70,11 @@ __device__ __forceinline__ void rh_layer_norm(atp_f4 (&y)[TPW][RH_STRIPS], float
 #pragma unroll
   for (int s = 0; s < RH_STRIPS; ++s) {
     const float* q = part2 + 16 * s + lr;
-    rstd[s] = 1.0f / sqrtf((((q[0] + q[RH_ROWS]) + q[2 * RH_ROWS]) + q[3 * RH_ROWS]) * (1.0f / F) + eps);
+    rstd[s] = 1.0f / sqrtf(mt_wave_sum4(q, RH_ROWS) * (1.0f / F) + eps);
   }
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
-    const atp_f4 g = rh_ldf4(lnw + 16 * (ft0 + t) + 4 * lq), b = rh_ldf4(lnb + 16 * (ft0 + t) + 4 * lq);
+    const atp_f4 g = mt_ldf4(lnw + 16 * (ft0 + t) + 4 * lq), b = mt_ldf4(lnb + 16 * (ft0 + t) + 4 * lq);
 #pragma unroll
     for (int s = 0; s < RH_STRIPS; ++s) y[t][s] = (y[t][s] - mean[s]) * rstd[s] * g + b;
   }
@@ -107,8 +102,8 @@ __device__ __forceinline__ void rh_body(const float* __restrict__ feat, const fl
     const int r = i / (F / 4), q = i % (F / 4), p = row0 + r;
     atp_f4 v = zero4, hv = zero4;
     if (p < P) {
-      v = rh_ldf4(feat + (size_t)p * F + 4 * q);
-      if (!(reset_env && reset_env[p / A])) hv = rh_ldf4(h_io + (size_t)p * F + 4 * q);
+      v = mt_ldf4(feat + (size_t)p * F + 4 * q);
+      if (!(reset_env && reset_env[p / A])) hv = mt_ldf4(h_io + (size_t)p * F + 4 * q);
     }
     atp_st4<CV>((TR ? cb + r * CS : xb + r * XS) + 4 * q, v);
     atp_st4<CV>(hb + r * XS + 4 * q, hv);
@@ -127,7 +122,7 @@ __device__ __forceinline__ void rh_body(const float* __restrict__ feat, const fl
     for (int s = 0; s < RH_STRIPS; ++s) {
       const int p = row0 + 16 * s + lr;
       cell[t][s] = zero4;
-      if (p < P && !(reset_env && reset_env[p / A])) cell[t][s] = rh_ldf4(c_io + (size_t)p * F + 16 * (ft0 + t) + 4 * lq);
+      if (p < P && !(reset_env && reset_env[p / A])) cell[t][s] = mt_ldf4(c_io + (size_t)p * F + 16 * (ft0 + t) + 4 * lq);
     }
   __syncthreads();
 
@@ -142,7 +137,7 @@ __device__ __forceinline__ void rh_body(const float* __restrict__ feat, const fl
     atp_f4 y[TPW][RH_STRIPS];
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
-      const atp_f4 b = rh_ldf4(w.tr_b + 16 * (ft0 + t) + 4 * lq);
+      const atp_f4 b = mt_ldf4(w.tr_b + 16 * (ft0 + t) + 4 * lq);
 #pragma unroll
       for (int s = 0; s < RH_STRIPS; ++s) y[t][s] = b;
 #pragma unroll
@@ -152,11 +147,7 @@ __device__ __forceinline__ void rh_body(const float* __restrict__ feat, const fl
         for (int s = 0; s < RH_STRIPS; ++s) y[t][s] = AtpMma<CV>::mma(a, cf[s][ks], y[t][s]);
       }
 #pragma unroll
-      for (int s = 0; s < RH_STRIPS; ++s) {
-        atp_f4& v = y[t][s];
-        v.x = v.x > 0.f ? v.x : v.x * slope; v.y = v.y > 0.f ? v.y : v.y * slope;
-        v.z = v.z > 0.f ? v.z : v.z * slope; v.w = v.w > 0.f ? v.w : v.w * slope;
-      }
+      for (int s = 0; s < RH_STRIPS; ++s) y[t][s] = mt_leaky4(y[t][s], slope);
     }
     rh_layer_norm<F, TPW>(y, part, w.tr_ln_w, w.tr_ln_b, tr_eps, wave, ft0, lr, lq);
 #pragma unroll
@@ -182,7 +173,7 @@ __device__ __forceinline__ void rh_body(const float* __restrict__ feat, const fl
     atp_f4 g[4][RH_STRIPS];   // torch's gate order: i, f, g, o
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const atp_f4 b = rh_ldf4(w.b_ih + k * F + f + 4 * lq) + rh_ldf4(w.b_hh + k * F + f + 4 * lq);
+      const atp_f4 b = mt_ldf4(w.b_ih + k * F + f + 4 * lq) + mt_ldf4(w.b_hh + k * F + f + 4 * lq);
 #pragma unroll
       for (int s = 0; s < RH_STRIPS; ++s) g[k][s] = b;
 #pragma unroll
@@ -201,12 +192,12 @@ __device__ __forceinline__ void rh_body(const float* __restrict__ feat, const fl
 #pragma unroll
     for (int s = 0; s < RH_STRIPS; ++s) {
       atp_f4 c = cell[t][s], h;
-      c.x = rh_sigmoid(g[1][s].x) * c.x + rh_sigmoid(g[0][s].x) * tanhf(g[2][s].x);
-      c.y = rh_sigmoid(g[1][s].y) * c.y + rh_sigmoid(g[0][s].y) * tanhf(g[2][s].y);
-      c.z = rh_sigmoid(g[1][s].z) * c.z + rh_sigmoid(g[0][s].z) * tanhf(g[2][s].z);
-      c.w = rh_sigmoid(g[1][s].w) * c.w + rh_sigmoid(g[0][s].w) * tanhf(g[2][s].w);
-      h.x = rh_sigmoid(g[3][s].x) * tanhf(c.x); h.y = rh_sigmoid(g[3][s].y) * tanhf(c.y);
-      h.z = rh_sigmoid(g[3][s].z) * tanhf(c.z); h.w = rh_sigmoid(g[3][s].w) * tanhf(c.w);
+      c.x = mt_sigmoid(g[1][s].x) * c.x + mt_sigmoid(g[0][s].x) * tanhf(g[2][s].x);
+      c.y = mt_sigmoid(g[1][s].y) * c.y + mt_sigmoid(g[0][s].y) * tanhf(g[2][s].y);
+      c.z = mt_sigmoid(g[1][s].z) * c.z + mt_sigmoid(g[0][s].z) * tanhf(g[2][s].z);
+      c.w = mt_sigmoid(g[1][s].w) * c.w + mt_sigmoid(g[0][s].w) * tanhf(g[2][s].w);
+      h.x = mt_sigmoid(g[3][s].x) * tanhf(c.x); h.y = mt_sigmoid(g[3][s].y) * tanhf(c.y);
+      h.z = mt_sigmoid(g[3][s].z) * tanhf(c.z); h.w = mt_sigmoid(g[3][s].w) * tanhf(c.w);
       hn[t][s] = h;
       const int p = row0 + 16 * s + lr;
       if (p < P) {
@@ -252,17 +243,12 @@ extern "C" int dynenv_recurrent_head(const float* feat_dev, const float* ext_dev
   if ((X > 0) != (ext_dev != nullptr)) return fail(DYNENV_ERR_ARG, "recurrent head: ext_dev is NULL exactly when X == 0");
   if (X > 0 && (!w->tr_w || !w->tr_b || !w->tr_ln_w || !w->tr_ln_b))
     return fail(DYNENV_ERR_ARG, "recurrent head: X > 0 takes the four pointers of the transform");
-  if (w_dtype < DYNENV_ARR_F32 || w_dtype > DYNENV_ARR_F16) return fail(DYNENV_ERR_ARG, "recurrent head: unknown dtype (DYNENV_ARR_BF16 or _F16)");
-  const void* aligned[] = {feat_dev, h_dev, c_dev, out_dev, w->w_ih, w->w_hh, w->b_ih, w->b_hh, w->ln_w, w->ln_b};
-  for (const void* q : aligned)
-    if ((uintptr_t)q % 16) return fail(DYNENV_ERR_ARG, "recurrent head: buffers must be 16-byte aligned");
-  if (X > 0) {
-    const void* aligned_tr[] = {w->tr_w, w->tr_b, w->tr_ln_w, w->tr_ln_b};
-    for (const void* q : aligned_tr)
-      if ((uintptr_t)q % 16) return fail(DYNENV_ERR_ARG, "recurrent head: buffers must be 16-byte aligned");
-  }
+  if (int rc = model_operand_dtype("recurrent head", w_dtype)) return rc;
+  if (int rc = model_aligned("recurrent head", {feat_dev, h_dev, c_dev, out_dev, w->w_ih, w->w_hh, w->b_ih, w->b_hh, w->ln_w, w->ln_b}, 16)) return rc;
+  if (X > 0)
+    if (int rc = model_aligned("recurrent head", {w->tr_w, w->tr_b, w->tr_ln_w, w->tr_ln_b}, 16)) return rc;
   if ((int64_t)E * A > (int64_t)1 << 30) return fail(DYNENV_ERR_ARG, "recurrent head: E * A too large for one launch");
-  if (w_dtype == DYNENV_ARR_F32) return fail(DYNENV_ERR_UNSUPPORTED, "recurrent head: the fused layer takes bf16 or fp16 operands");
+  if (int rc = model_operand_16bit("recurrent head", w_dtype, "layer")) return rc;
   if (F != 64 && F != 128) return fail(DYNENV_ERR_UNSUPPORTED, "recurrent head: the fused layer takes F = 64 or 128");
   if (X > 32) return fail(DYNENV_ERR_UNSUPPORTED, "recurrent head: the fused layer takes X <= 32");
   if (int rc = have_device()) return rc;

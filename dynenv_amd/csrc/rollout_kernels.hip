@@ -23,14 +23,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dynenv.h"
+#include "mma_tiles.h"
 
 #define RI_BLOCK 256
 #define RI_ROWS 64
 #define RI_PER 4
 #define RI_CHUNK (RI_BLOCK * RI_PER)
 #define RR_BLOCK 256
-
-// atp_f4: attention_kernels.hip's.  rh_ldf4: recurrent_kernels.hip's.
 
 struct RiArgs {
   const int* cursor;
@@ -63,9 +62,9 @@ extern "C" __global__ void __launch_bounds__(RI_BLOCK) rollout_insert_kernel(RiA
       if (i < total) {
         if (a.feat1) {
           const unsigned r = i / K4, col = 4 * (i - r * K4);
-          v[j] = col < F ? rh_ldf4(a.feat0 + (size_t)r * F + col) : rh_ldf4(a.feat1 + (size_t)r * F + (col - F));
+          v[j] = col < F ? mt_ldf4(a.feat0 + (size_t)r * F + col) : mt_ldf4(a.feat1 + (size_t)r * F + (col - F));
         } else {
-          v[j] = rh_ldf4(a.feat0 + 4 * (size_t)i);
+          v[j] = mt_ldf4(a.feat0 + 4 * (size_t)i);
         }
       }
     }
@@ -197,9 +196,7 @@ extern "C" int dynenv_rollout_returns(const float* rewards_dev, const float* val
   if ((mode == DYNENV_RETURNS_GAE || advantages_dev) && !values_dev) return fail(DYNENV_ERR_ARG, "rollout returns: GAE and advantages_dev take values_dev");
   if (T < 1 || E < 1 || A < 1) return fail(DYNENV_ERR_ARG, "rollout returns: bad shape");
   if (T > (1 << 24) || (int64_t)E * A > (int64_t)1 << 30) return fail(DYNENV_ERR_ARG, "rollout returns: T above 2^24 or E * A above 2^30");
-  const void* words[] = {rewards_dev, values_dev, dones_dev, final_value_dev, returns_dev, advantages_dev};
-  for (const void* q : words)
-    if ((uintptr_t)q % 4) return fail(DYNENV_ERR_ARG, "rollout returns: buffers must be 4-byte aligned");
+  if (int rc = model_aligned("rollout returns", {rewards_dev, values_dev, dones_dev, final_value_dev, returns_dev, advantages_dev}, 4)) return rc;
   if (int rc = have_device()) return rc;
   RrArgs k;
   k.rewards = rewards_dev; k.values = values_dev; k.dones = dones_dev; k.final_value = final_value_dev; k.returns = returns_dev; k.advantages = advantages_dev;
